@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X-native R2-Gaussian hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats M] [--dump-outputs DIR]
 
 Metric (BASELINE.json): rasterized X-ray views/s (forward + backward) at 300k Gaussians on a 512^2 cone-beam
 detector, plus voxelizer GVoxel/s at 300k Gaussians / 256^3 (reported in the same JSON line).
@@ -16,9 +16,15 @@ per-GPU work fixed).  `value` is the SYNCHRONOUS mode: the all-reduce of step k 
 (what a trainer that applies every step's gradients needs, and what a PSNR study would be run with); `overlapped` in the
 same line is the pipelined mode (the reduction of step k runs while step k+1 renders; gradients arrive one step late).
 
-Timing: W untimed warm-up steps, then M (--repeats) regions of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` = all views of all ranks / the MEDIAN
-region (min / max / spread are in `timing`): a 20-step driver run is then 25 samples, not one 5 ms sample.
+Timing: W untimed warm-up steps, then EXACTLY K timed steps, split into M (--repeats; default one per 20 steps, at most
+25) consecutive regions, each bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX over
+ranks; `ms_per_step` = the MEDIAN over the regions of region time / its steps, `value` = views of all ranks per second at
+that step time (min / max / spread are in `timing`).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the LAST timed step computed -- what a caller of the drop-in
+surface receives: image, radii, and the gradients of means3D / means2D / opacities / scales / rotations (summed over ranks
+when N > 1) -- as DIR/<name>.npy in float32.  The inputs are seeded, so the same arguments give the same inputs on every run.
+Above 64 MB in all, each array is replaced by a fixed seeded sample of its elements (flattened) plus <name>_index.npy.
 
 The JSON line also carries
   roofline       dominant kernel (picked from an instrumented pre-pass): algorithmic bytes per launch / its HIP-event duration
@@ -145,11 +151,18 @@ class StepRunner:
                 self.pending[i] = None
 
 
-def timed_regions(runner, steps, repeats, first_step, barrier, max_over_ranks):
-    """`repeats` regions of exactly `steps` steps, each bracketed by barrier + synchronize; -> per-region seconds (max over ranks)."""
+def split_steps(total, regions):
+    """`total` timed steps as `regions` consecutive regions whose sizes differ by at most one (no empty region)."""
+    n = max(1, min(regions, total))
+    return [total // n + (1 if i < total % n else 0) for i in range(n)]
+
+
+def timed_regions(runner, sizes, first_step, barrier, max_over_ranks):
+    """One region per entry of `sizes`, of exactly that many steps, each bracketed by barrier + synchronize;
+    -> per-region seconds (max over ranks)."""
     out = []
     k = first_step
-    for _ in range(repeats):
+    for steps in sizes:
         barrier()
         t0 = time.perf_counter()
         for _i in range(steps):
@@ -161,12 +174,43 @@ def timed_regions(runner, steps, repeats, first_step, barrier, max_over_ranks):
     return out, k
 
 
-def summarize(region_s, steps, world):
-    med = statistics.median(region_s)
-    return {"value": round(steps * world / med, 2), "ms_per_step": round(1e3 * med / steps, 4),
-            "regions": len(region_s), "ms_per_step_min": round(1e3 * min(region_s) / steps, 4),
-            "ms_per_step_max": round(1e3 * max(region_s) / steps, 4),
-            "spread": round((max(region_s) - min(region_s)) / med, 4)}
+def summarize(region_s, sizes, world):
+    """`sizes`: steps of each region, or one count shared by all of them."""
+    if isinstance(sizes, int):
+        sizes = [sizes] * len(region_s)
+    per_step = [t / n for t, n in zip(region_s, sizes)]
+    med = statistics.median(per_step)
+    return {"value": round(world / med, 2), "ms_per_step": round(1e3 * med, 4),
+            "regions": len(region_s), "timed_steps": sum(sizes), "ms_per_step_min": round(1e3 * min(per_step), 4),
+            "ms_per_step_max": round(1e3 * max(per_step), 4),
+            "spread": round((max(per_step) - min(per_step)) / med, 4)}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write {name: array} as out_dir/<name>.npy in float32.  When the whole exceeds DUMP_BUDGET_BYTES, every array is cut to
+    the same fraction of its elements: a sorted sample drawn with a fixed seed, saved flat, with the flat element indices
+    beside it as <name>_index.npy (float64: exact).  -> {name: shape written}."""
+    import numpy as np
+    arrays = {n: np.ascontiguousarray(a, dtype=np.float32) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    room = DUMP_BUDGET_BYTES - 2 * 1024 * len(arrays)   # minus the .npy headers (~128 B per file)
+    # a sampled element costs 4 B of value + 8 B of index: 3x its float32 share
+    frac = 1.0 if total <= room else room / (3.0 * total)
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    shapes = {}
+    for name, a in arrays.items():
+        if frac < 1.0:
+            idx = np.sort(rng.choice(a.size, int(a.size * frac), replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
 
 def inv_softplus(x):
     import torch
@@ -321,7 +365,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps steps (default: 25, or 5 when steps >= 500)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="regions the --steps timed steps are split into (default: one per 20 steps, at most 25); also the "
+                         "region count of the sections that time their own step counts (default: 25, or 5 when steps >= 500)")
     ap.add_argument("--gaussians", type=int, default=300000)
     ap.add_argument("--detector", type=int, default=512)
     ap.add_argument("--views", type=int, default=50)
@@ -339,11 +385,17 @@ def main():
                          "trained through tests/trained_cloud.py).  --gaussians is then the cloud's own size")
     ap.add_argument("--headline-only", action="store_true",
                     help="the single-view step and nothing else (profiler passes: every kernel row is the headline step)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (image, radii, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.headline_only:
         args.no_voxel = args.no_batched = args.no_streams = args.no_forward_only = args.no_cpu_baseline = True
         args.no_train_iteration = args.no_densify_pattern = True
     repeats = args.repeats or (5 if args.steps >= 500 else 25)
+    # the headline measurement: exactly --steps timed steps, in regions of at least 20 steps unless --repeats says otherwise
+    head = split_steps(args.steps, args.repeats or min(25, args.steps // 20))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
@@ -385,6 +437,7 @@ def main():
     P, HW = args.gaussians, args.detector
     views = S.make_views(args.views, (HW, HW))
     stats = {"R": 0}
+    last = {}   # what the latest step computed, for --dump-outputs (references only: nothing is copied inside the timed steps)
     flats = [torch.empty((P, r2dist.GRAD_WIDTH), dtype=torch.float32, device=dev) for _ in range(2)]
 
     if stub:
@@ -395,6 +448,7 @@ def main():
                 flats[i].add_(torch.rand(P, r2dist.GRAD_WIDTH, generator=g))
             else:
                 flats[i].copy_(torch.rand(P, r2dist.GRAD_WIDTH, generator=g))
+            last["blk"] = flats[i]
             return flats[i]
         _lib = None
         cloud = S.make_cloud(P, seed=0)
@@ -435,7 +489,8 @@ def main():
 
         def render(k, i, accumulate=False):
             vi = r2dist.view_for(k, len(views), rank_=rank, world_=world)
-            img, _radii = rasterizers[vi](means3D=xyz, means2D=means2D, opacities=dens, scales=scal, rotations=rot)
+            img, radii = rasterizers[vi](means3D=xyz, means2D=means2D, opacities=dens, scales=scal, rotations=rot)
+            last.update(view=vi, img=img, radii=radii, blk=None)
             means2D.grad = None
             if not accumulate:   # accumulate: autograd adds this view's gradients into the previous view's .grad block
                 for p in params:
@@ -448,6 +503,7 @@ def main():
             if blk is None:
                 blk = r2dist.pack_grads(xyz.grad, dens.grad, scal.grad, rot.grad, out=flats[i])
             stats["zero_copy"] = blk is not flats[i]
+            last["blk"] = blk
             return blk
 
     def allreduce(blk):
@@ -495,7 +551,20 @@ def main():
         _lib.sync_wait_stats(reset=True)
 
     # ---- the measurement: NO instrumentation inside these regions
-    region_s, k = timed_regions(sync_runner, args.steps, repeats, k, barrier, max_over_ranks)
+    region_s, k = timed_regions(sync_runner, head, k, barrier, max_over_ranks)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if stub:
+            arrays = {"grad_block": last["blk"]}
+        else:
+            g3, gd, gs, gr = xyz.grad, dens.grad, scal.grad, rot.grad
+            if any(last["blk"] is f for f in flats):
+                g3, gd, gs, gr = r2dist.unpack_grads(last["blk"])   # packed copy: the sums over ranks are in the block
+            arrays = {"image": last["img"], "radii": last["radii"], "grad_means3D": g3, "grad_means2D": means2D.grad,
+                      "grad_opacities": gd, "grad_scales": gs, "grad_rotations": gr}
+        arrays = {n: t.detach().cpu().numpy() for n, t in arrays.items()}
+        dumped = {"dir": args.dump_outputs, "step": k - 1, "view": last.get("view"),
+                  "arrays": dump_outputs(args.dump_outputs, arrays)}
     dom, wait_us, wait_n = (0.0, 0), 0.0, 0
     dom_regions = None
     if not stub:
@@ -505,11 +574,11 @@ def main():
         # the two measurements can be told apart -- round 2 bracketed the kernel inside the regions that produced `value`)
         _lib.profile_read(reset=True)
         _lib.profile_enable([DOMINANT])
-        dom_s, k = timed_regions(sync_runner, args.steps, min(repeats, 5), k, barrier, max_over_ranks)
+        dom_s, k = timed_regions(sync_runner, head, k, barrier, max_over_ranks)
         dom = _lib.profile_read(reset=True).get(DOMINANT, (0.0, 0))
         _lib.profile_enable([])
-        dom_regions = summarize(dom_s, args.steps, world)
-    main_t = summarize(region_s, args.steps, world)
+        dom_regions = summarize(dom_s, head, world)
+    main_t = summarize(region_s, head, world)
     overlapped = None
     if use_comm:   # the pipelined mode, labelled as such, next to the synchronous number
         ov_runner = StepRunner(render, allreduce, use_comm, "overlap")
@@ -517,10 +586,10 @@ def main():
             ov_runner.step(k)
             k += 1
         ov_runner.drain()
-        ov_s, k = timed_regions(ov_runner, args.steps, repeats, k, barrier, max_over_ranks)
-        overlapped = summarize(ov_s, args.steps, world)
+        ov_s, k = timed_regions(ov_runner, head, k, barrier, max_over_ranks)
+        overlapped = summarize(ov_s, head, world)
         overlapped["note"] = "all-reduce of step k overlaps the render of step k+1: gradients are consumed one step late"
-    dt_step = statistics.median(region_s) / args.steps
+    dt_step = main_t["ms_per_step"] / 1e3
     two_view = None
     if use_comm:   # synchronous data parallelism with two views per rank and step (StepRunner docstring): views/s of each
         two_view = {}
@@ -531,7 +600,7 @@ def main():
                 k += 1
             rn.drain()
             n2 = max(1, args.steps // 2)
-            s2, k = timed_regions(rn, n2, repeats, k, barrier, max_over_ranks)
+            s2, k = timed_regions(rn, [n2] * repeats, k, barrier, max_over_ranks)
             two_view[mode2] = summarize(s2, 2 * n2, world)
         two_view["note"] = ("two views per rank and optimiser step, parameters updated once, no stale gradients; sync2 = all-reduce "
                             "of view A behind the render of view B + exposed all-reduce of B; accum2 = local accumulation + ONE "
@@ -561,10 +630,10 @@ def main():
             _lib.sync_wait_stats(reset=True)
             stq = (_ctq.c_longlong * 3)()
             Lq.r2_defer_count_stats(stq, 1)
-            dq_s, k = timed_regions(sync_runner, args.steps, repeats, k, barrier, max_over_ranks)
+            dq_s, k = timed_regions(sync_runner, head, k, barrier, max_over_ranks)
             wq_us, wq_n = _lib.sync_wait_stats(reset=True)
             Lq.r2_defer_count_stats(stq, 1)
-            deferred = summarize(dq_s, args.steps, 1)
+            deferred = summarize(dq_s, head, 1)
             deferred.update(host_wait_us_per_step=round(wq_us / max(wq_n, 1), 1), forwards_with_token=int(stq[0]),
                             forwards_that_waited_for_a_slot=int(stq[1]), predictions_short=int(stq[2]),
                             note="R2_DEFER_COUNT mode: state sized by the prediction + 50 %, no wait in the forward, the autograd "
@@ -598,7 +667,7 @@ def main():
             ti.step(k)
             k += 1
         nti = max(2, min(args.steps, 200))
-        tr_s, k = timed_regions(ti, nti, min(repeats, 5), k, barrier, max_over_ranks)
+        tr_s, k = timed_regions(ti, [nti] * min(repeats, 5), k, barrier, max_over_ranks)
         train_it = summarize(tr_s, nti, 1)
         train_it.update(unit="iterations/s", views_per_iteration=world, views_per_s=round(train_it["value"] * world, 2),
                         what="one optimiser step of the data-parallel trainer: activations, raster fwd+bwd of this rank's view, "
@@ -612,7 +681,7 @@ def main():
                     ti.step(k)
                     k += 1
                 _lib.sync_wait_stats(reset=True)
-                trd_s, k = timed_regions(ti, nti, min(repeats, 5), k, barrier, max_over_ranks)
+                trd_s, k = timed_regions(ti, [nti] * min(repeats, 5), k, barrier, max_over_ranks)
                 wd_us, wd_n = _lib.sync_wait_stats(reset=True)
                 train_it["deferred_count"] = dict(summarize(trd_s, nti, 1), unit="iterations/s",
                                                   host_wait_us_per_iteration=round(wd_us / max(nti * min(repeats, 5), 1), 1))
@@ -641,7 +710,7 @@ def main():
             tiw.step(k)
             k += 1
         ntw = max(2, min(args.steps // 4, 50))
-        trw_s, k = timed_regions(tiw, ntw, min(repeats, 5), k, barrier, max_over_ranks)
+        trw_s, k = timed_regions(tiw, [ntw] * min(repeats, 5), k, barrier, max_over_ranks)
         train_it_w8 = summarize(trw_s, ntw, 1)
         train_it_w8.update(unit="iterations/s", views_per_iteration=Ww, views_per_call=BVw,
                            views_per_s=round(train_it_w8["value"] * Ww, 2),
@@ -682,7 +751,7 @@ def main():
                                          "comm_zero_copy": False, "parallelism": "stub"},
                               "timing": main_t, "overlapped": overlapped, "two_views_per_step": two_view,
                               "sync_modes": sync_modes, "train_iteration": train_it,
-                              "voxelizer": {"sharded": sharded}}))
+                              "voxelizer": {"sharded": sharded}, "outputs": dumped}))
         if use_comm:
             dist.barrier()
             dist.destroy_process_group()
@@ -1163,8 +1232,9 @@ def main():
                        "comm_zero_copy": stats.get("zero_copy") if use_comm else None},
             "cloud_stats": cloud_stats,
             "paths": {k_: v_ for k_, v_ in _lib.path_stats().items() if v_},   # every forward of this process, by chain and reason
-            "timing": dict(main_t, note="median of %d regions of exactly %d steps, each between barrier + synchronize, "
-                                        "max over ranks" % (repeats, args.steps)),
+            "timing": dict(main_t, note="%d timed steps in %d regions of %s steps, each between barrier + synchronize, max over "
+                                        "ranks; ms_per_step = median over the regions" % (
+                                            args.steps, len(head), "/".join(str(n) for n in sorted(set(head))))),
             "overlapped": overlapped,
             "two_views_per_step": two_view,
             "sync_modes": sync_modes,
@@ -1195,6 +1265,7 @@ def main():
             "kernels": kernels,
             "voxelizer": (dict(gvox or {}, sharded=sharded) if (gvox or sharded) else None),
             "simple_knn_ms": knn_t,
+            "outputs": dumped,
         }
         print(json.dumps(out))
     if dist.is_initialized():

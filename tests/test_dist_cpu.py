@@ -194,6 +194,61 @@ def test_bench_gpus_n_launches_its_own_ranks():
     assert r2.returncode != 0 and "launcher started 1 ranks" in (r2.stderr + r2.stdout)
 
 
+@pytest.mark.timeout(300)
+def test_bench_steps_and_dump_outputs(tmp_path):
+    """--steps K times exactly K steps (split into regions), the line carries ms_per_step, and --dump-outputs DIR writes what the
+    last timed step computed as float32 .npy files -- the same arrays on a second run with the same arguments (stub renderer)."""
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, R2_BENCH_STUB="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("run%d" % run))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "45", "--warmup", "3",
+                            "--gaussians", "257", "--dump-outputs", d], env=env, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _bench_line(r.stdout)
+        assert line["steps"] == 45 and line["timing"]["timed_steps"] == 45 and line["timing"]["regions"] == 2
+        assert line["ms_per_step"] > 0 and line["ms_per_step"] == line["timing"]["ms_per_step"]
+        assert line["outputs"]["step"] == 3 + 45 - 1 and line["outputs"]["arrays"] == {"grad_block": [257, 11]}
+        a = np.load(os.path.join(d, "grad_block.npy"))
+        assert a.dtype == np.float32 and a.shape == (257, 11)
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+    # the stub renders step k as the k-th draw of torch.rand from a generator seeded with the rank: the dump must be the draw
+    # of the last timed step (3 warm-up + 45 timed steps), not of any earlier one
+    g = torch.Generator().manual_seed(0)
+    for _ in range(3 + 45):
+        want = torch.rand(257, 11, generator=g)
+    assert np.array_equal(dumps[0], want.numpy())
+
+
+def test_bench_dump_outputs_stays_within_budget(tmp_path):
+    """Above 64 MB the dump is a seeded sample of every array plus its flat element indices, and stays under 64 MB."""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    big = np.arange(20_000_000, dtype=np.float32).reshape(-1, 4)
+    arrays = {"big": big, "image": np.ones((1, 64, 64)), "radii": np.arange(10, dtype=np.int32)}
+    shapes = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert shapes[0] == shapes[1]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET_BYTES
+    v, i = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "a" / "big_index.npy"))
+    assert v.dtype == np.float32 and i.dtype == np.float64 and 0 < v.size < big.size
+    assert np.array_equal(v, big.reshape(-1)[i.astype(np.int64)])
+    assert np.array_equal(i, np.load(str(tmp_path / "b" / "big_index.npy")))
+    # under the budget everything is written whole, in float32
+    small = bench.dump_outputs(str(tmp_path / "c"), {"radii": arrays["radii"]})
+    assert small == {"radii": [10]} and np.load(str(tmp_path / "c" / "radii.npy")).dtype == np.float32
+
+
 def test_bench_step_runner_sync_and_overlap_order():
     """sync: every step's reduction is waited for before the step returns.  overlap: it is waited for two steps later, before
     its buffer is rendered into again, and drain() waits for whatever is left."""
