@@ -337,7 +337,7 @@ R2_API void r2_depth_hint_control(int mode);
  * calling thread can predict from its recent calls with the same P and detector size skip the global depth order -- instances
  * are counted and scattered per tile and every tile list is sorted on (depth, id) on its own -- and size the binning / image
  * state by that prediction (the exact count is still returned; a prediction that falls short only costs a second pass).
- * point_list, ranges, images and gradients are identical on both chains.  mode 0: never, 1: when applicable (default; the
+ * point_list, ranges, the render kernels' block masks, images and gradients are identical on both chains.  mode 0: never, 1: when applicable (default; the
  * environment variable R2_TILE_FIRST=0 also switches it off), 2: forget the calling thread's predictions (its next call of any
  * size takes the general chain). */
 R2_API void r2_tile_first_control(int mode);
@@ -351,8 +351,16 @@ R2_API void r2_tile_first_control(int mode);
  * the mode off), and callers that use the returned value as a count must not.  Forwards the chain does not take (first call of a
  * size, debug mode), and all voxelizer calls, wait as before.  mode 0: off (default). */
 R2_API void r2_defer_count_control(int mode);
-/* out[0] forwards that returned a token, [1] forwards that had to wait because 64 tokens were outstanding, [2] backwards that
- * found the prediction short.  out may be NULL (reset only). */
+/* A deferred forward's token -> its true num_rendered, for callers that run no backward (evaluation under no_grad): waits for
+ * the forward's control words like the backward does (stream: the forward's, for the drained-stream check).  R2_ERR_INVALID
+ * with the backward's "sized for" message when the prediction fell short (the forward's image and state are invalid).  Repeat
+ * calls are harmless and give the same answer: the token stays valid for its backward, until that backward has run or 64 later
+ * deferred forwards have recycled its slot (then: a stale-token error).  A forward that fell short leaves nothing behind either
+ * way -- the next forwards on its stream are exact whether or not anybody resolves its token. */
+R2_API int r2_defer_count_resolve(int token, int *num_rendered, void *stream);
+/* out[0] forwards that returned a token, [1] forwards that had to wait because 64 tokens were outstanding, [2] deferred forwards
+ * whose prediction fell short -- each counted once, whether the forward thread's next forward, r2_defer_count_resolve or the
+ * backward finds it.  out may be NULL (reset only). */
 R2_API void r2_defer_count_stats(long long out[3], int reset);
 /* process-wide counts since the last reset: out[0] forwards that took the tile-first chain, [1] forwards that did not (no
  * prediction yet, or beyond its limits), [2] chains enqueued a second time because the prediction fell short, [3] renders

@@ -335,6 +335,19 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     return present
 
 
+def defer_count_resolve(token, device=None):
+    """A deferred forward's token (r2_defer_count_control) -> its true num_rendered, for forwards that get no backward.  Raises
+    R2HipError ("sized for ...") when the forward's prediction fell short: its image is invalid.  Repeat calls are harmless and the
+    token stays valid for its backward (include/r2hip.h: r2_defer_count_resolve)."""
+    import ctypes
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n = ctypes.c_int(0)
+    with _on_device(dev):
+        rc = _lib.lib().r2_defer_count_resolve(int(token), ctypes.byref(n), _stream(dev))
+    _lib.check(rc, "r2_defer_count_resolve")
+    return n.value
+
+
 TILE3D = 8
 
 

@@ -242,7 +242,7 @@ static int mailbox_spin(uint32_t *words, uint32_t seq, uint32_t *out, int n, hip
 // under no_grad) is recycled, least recently used first.
 namespace {
 constexpr int DEFER_SLOTS = 64;
-struct DeferSlot { uint32_t seq = 0; uint32_t cap = 0; bool busy = false; unsigned long long used = 0; };
+struct DeferSlot { uint32_t seq = 0; uint32_t cap = 0; bool busy = false; bool short_seen = false; unsigned long long used = 0; };
 std::mutex g_defer_mu;
 uint32_t *g_defer_words = nullptr;   // [DEFER_SLOTS][16] pinned, never freed (process lifetime: tokens may outlive any thread)
 DeferSlot g_defer[DEFER_SLOTS];
@@ -273,7 +273,7 @@ int defer_acquire(uint32_t **mailbox, uint32_t *seq, uint32_t cap)
         if (pick < 0) return -1;   // none: the caller falls back to the waiting forward
     }
     if (++g_defer_seq == 0u) ++g_defer_seq;
-    g_defer[pick] = DeferSlot{g_defer_seq, cap, true, ++g_defer_tick};
+    g_defer[pick] = DeferSlot{g_defer_seq, cap, true, false, ++g_defer_tick};
     *mailbox = g_defer_words + pick * 16;
     *seq = g_defer_seq;
     return DEFER_TOKEN_FLAG | (pick << 16) | (int)(g_defer_seq & 0xFFFFu);
@@ -302,8 +302,9 @@ int defer_resolve(int token, uint32_t *out, int n, uint32_t *cap, hipStream_t s,
     return rc;
 }
 
-// non-blocking: have the words of this token arrived?  (the forward's own thread keeps its predictions current with it)
-bool defer_peek(int token, uint32_t *out, int n)
+// non-blocking: have the words of this token arrived?  (the forward's own thread keeps its predictions current with it) -> the
+// words and the capacity the forward was launched with
+bool defer_peek(int token, uint32_t *out, int n, uint32_t *cap)
 {
     const int slot = (token >> 16) & (DEFER_SLOTS - 1);
     std::lock_guard<std::mutex> lk(g_defer_mu);
@@ -311,6 +312,18 @@ bool defer_peek(int token, uint32_t *out, int n)
     uint32_t *w = g_defer_words + slot * 16;
     if (__atomic_load_n(&w[15], __ATOMIC_ACQUIRE) != g_defer[slot].seq) return false;
     for (int i = 0; i < n; ++i) out[i] = w[i];
+    *cap = g_defer[slot].cap;
+    return true;
+}
+
+// true the first time it is called for a token (of the slot's current forward): a short count is reported once per forward,
+// whoever finds it first
+bool defer_first_short(int token)
+{
+    const int slot = (token >> 16) & (DEFER_SLOTS - 1);
+    std::lock_guard<std::mutex> lk(g_defer_mu);
+    if ((g_defer[slot].seq & 0xFFFFu) != (uint32_t)(token & 0xFFFF) || g_defer[slot].short_seen) return false;
+    g_defer[slot].short_seen = true;
     return true;
 }
 

@@ -291,7 +291,8 @@ void host_words_release();   // the calling thread's pinned words (r2_thread_rel
 constexpr int DEFER_TOKEN_FLAG = 0x40000000;
 int defer_acquire(uint32_t **mailbox, uint32_t *seq, uint32_t cap);
 int defer_resolve(int token, uint32_t *out, int n, uint32_t *cap, hipStream_t s, bool release);
-bool defer_peek(int token, uint32_t *out, int n);
+bool defer_peek(int token, uint32_t *out, int n, uint32_t *cap);
+bool defer_first_short(int token);
 // tile ranges of the sorted list + point_list[k] = vals_unsorted[perm[k]] in the same pass
 int tile_ranges(const uint32_t *tiles_sorted, const uint32_t *perm, const uint32_t *vals_unsorted, uint32_t *point_list,
                 size_t R, uint2 *ranges, size_t T, hipStream_t s, bool ranges_zeroed = false);

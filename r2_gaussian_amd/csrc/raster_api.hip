@@ -219,7 +219,7 @@ static int raster_backward_impl(
     }
     if (R >= DEFER_TOKEN_FLAG) {   // a deferred forward's token (r2_defer_count_control): the count is on its way, or long here
         uint32_t true_R = 0;
-        const int rc = raster_resolve_deferred(what, R, s, &true_R);
+        const int rc = raster_resolve_deferred(what, R, s, &true_R, true);
         if (rc) return rc;
         R = (int)true_R;
     }
@@ -333,6 +333,7 @@ extern "C" long long r2_raster_state_offset(int which, int P, long long R, int w
     case 13: p = (char *)b.inv; buf = 1; break;
     case 14: p = (char *)g.op_mu; buf = 0; break;
     case 15: p = (char *)g.host_words; buf = 0; break;
+    case 16: p = (char *)b.masked; buf = 1; break;
     default: return -1;
     }
     if (buffer_id) *buffer_id = buf;

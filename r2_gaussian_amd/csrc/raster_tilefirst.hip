@@ -250,29 +250,39 @@ __global__ void __launch_bounds__(TFS_THREADS) raster_tf_scatter_kernel(
             // from 13.9 to 16.5 us, from 30 to 37 us on the 331k trained cloud with its 9 instances per Gaussian).  block_live is a
             // product of an x and a y test against INTEGER pixel bounds: px - hx <= X + 7 <=> ceil(px - hx) <= X + 7, and
             // px + hx >= X <=> floor(px + hx) >= X.  So the 8-pixel blocks the box touches, counted from the rectangle's first tile, are
-            // the range [(A - X0) >> 3, (B - X0) >> 3] (A = ceil(px - hx), B = floor(px + hx), X0 = the rectangle's first pixel;
-            // arithmetic shifts): one bit mask per axis and Gaussian, two bit-field extracts and a multiply per instance -- the same
-            // masks, bit for bit.  Blocks beyond the 32nd of a rectangle (more than 16 tiles across) count as live: a mask may
-            // name a block the box misses (the render kernels then evaluate pixels that all fail the cut-off), never miss one.
+            // the range [(A - X0) >> 3, (B - X0) >> 3] (A = ceil(px - hx), B = floor(px + hx), X0 = the first pixel of the mask's
+            // window; arithmetic shifts): one 32-bit mask per axis covers a window of 16 tiles, two bit-field extracts and a multiply
+            // per instance -- the same masks, bit for bit.  A rectangle more than 16 tiles across or down (up to 256) takes a new
+            // window every 16 tiles, from the same integer bounds: an integer mask per 16 tiles, no float test (rounds 1-6 counted
+            // the blocks beyond the 32nd as live, so the masked list, and with it the image, differed from the general chain's).
             const uint32_t idw = g_idx[it] << MASK_BITS;
             // (stacked views: the rectangle's rows count from the top of the stack, the record's pixel coordinates from its view's)
             const uint32_t yoff = Pv == P ? 0u : (g_idx[it] / (uint32_t)Pv) * (uint32_t)gy;
-            auto axis_mask = [](float c, float hw, int origin) -> uint32_t {
-                const float lim = 1048576.0f;   // (+-inf half-widths: never / always live)
-                const int A = (int)fminf(fmaxf(ceilf(c - hw), -lim), lim), B = (int)fminf(fmaxf(floorf(c + hw), -lim), lim);
+            const float lim = 1048576.0f;   // (+-inf half-widths: never / always live)
+            const int Ax = (int)fminf(fmaxf(ceilf(g_box[it].x - g_box[it].z), -lim), lim);
+            const int Bx = (int)fminf(fmaxf(floorf(g_box[it].x + g_box[it].z), -lim), lim);
+            const int Ay = (int)fminf(fmaxf(ceilf(g_box[it].y - g_box[it].w), -lim), lim);
+            const int By = (int)fminf(fmaxf(floorf(g_box[it].y + g_box[it].w), -lim), lim);
+            auto axis_mask = [](int A, int B, int origin) -> uint32_t {   // blocks [0, 32) of the window from pixel `origin`
                 const int lo = max((A - origin) >> 3, 0), hi = min((B - origin) >> 3, 31);
                 return lo > hi ? 0u : ((0xFFFFFFFFu >> (31 - hi)) & (0xFFFFFFFFu << lo));
             };
-            const uint32_t xm = axis_mask(g_box[it].x, g_box[it].z, (int)(x0 * (uint32_t)TILE2D));
-            const uint32_t ym = axis_mask(g_box[it].y, g_box[it].w, (int)((y0 - yoff) * (uint32_t)TILE2D));
+            const int X0 = (int)(x0 * (uint32_t)TILE2D), Y0 = (int)((y0 - yoff) * (uint32_t)TILE2D);
+            const uint32_t xm0 = axis_mask(Ax, Bx, X0);
+            uint32_t ym = 0u;
             for (uint32_t r = 0; r < h; ++r) {
                 const uint32_t row = ((y0 + r) * (uint32_t)gx + x0) * nsl + sl;
-                const uint32_t yb = r < 16u ? (ym >> (2u * r)) & 3u : 3u;
+                if ((r & 15u) == 0u) ym = axis_mask(Ay, By, Y0 + (int)(r * (uint32_t)TILE2D));
+                const uint32_t yb = (ym >> (2u * (r & 15u))) & 3u;
                 const uint32_t ymul = (yb & 1u) | ((yb & 2u) << 1);   // y block 0 owns mask bits 0-1, y block 1 bits 2-3
-                for (uint32_t c = 0; c < w; ++c) {
-                    const uint32_t xb = c < 16u ? (xm >> (2u * c)) & 3u : 3u;
-                    const uint32_t pos = atomicAdd(&s_pos[row + c * nsl], 1u);
-                    pairs[pos] = make_uint2(key, idw | (xb * ymul));
+                for (uint32_t c0 = 0; c0 < w; c0 += 16u) {
+                    const uint32_t xm = c0 == 0u ? xm0 : axis_mask(Ax, Bx, X0 + (int)(c0 * (uint32_t)TILE2D));
+                    const uint32_t c1 = min(w, c0 + 16u);
+                    for (uint32_t c = c0; c < c1; ++c) {
+                        const uint32_t xb = (xm >> (2u * (c - c0))) & 3u;
+                        const uint32_t pos = atomicAdd(&s_pos[row + c * nsl], 1u);
+                        pairs[pos] = make_uint2(key, idw | (xb * ymul));
+                    }
                 }
             }
         }
@@ -393,7 +403,7 @@ __device__ __forceinline__ void tf_sort_group(unsigned long long (&mine)[PER], u
 __global__ void __launch_bounds__(TFK_THREADS, 8) raster_tf_sort_kernel(
     const uint4 *__restrict__ big_parts, uint32_t big_cap, const uint4 *__restrict__ small_tiles, const uint32_t *__restrict__ nparts,
     const uint2 *__restrict__ pairs, uint32_t *__restrict__ point_list, TFCounters *__restrict__ ctr,
-    const uint32_t *__restrict__ words, uint32_t cap)
+    const uint32_t *__restrict__ words, uint32_t cap, uint32_t clear_lists)
 {
     extern __shared__ unsigned long long tfk_lds[];
     __shared__ uint32_t s_mm[2][TFK_THREADS / 64], s_wsum[TFK_THREADS / 64], s_cnt, s_off;
@@ -405,9 +415,18 @@ __global__ void __launch_bounds__(TFK_THREADS, 8) raster_tf_sort_kernel(
     R2_TS_AT(tilefirst, 3);
     // the scalar counters have been read for the last time by the scatter kernel: ready for the next call -- unless the state was
     // too small for this one, in which case the scatter kernel will want them again
-    if (p == 0u && tid == 0 && words[DW_TOTAL] <= cap) {
+    const bool fits = words[DW_TOTAL] <= cap;
+    if (p == 0u && tid == 0 && (fits || clear_lists != 0u)) {
         __hip_atomic_store(&ctr->total, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&ctr->thin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!fits) {
+        // nothing to sort (the scatter kernel did nothing and posted no parts).  A deferred forward (clear_lists = its lists) gets
+        // no second pass: its tile counts are cleared here, on the device, so that the next forward on this stream starts from
+        // zero whether or not the host has seen this one's count by then.  The grid has a workgroup per TFK_GROUPS lists.
+        if ((uint32_t)tid < (uint32_t)TFK_GROUPS && p * (uint32_t)TFK_GROUPS + (uint32_t)tid < clear_lists)
+            tile_count[p * (uint32_t)TFK_GROUPS + (uint32_t)tid] = 0u;
+        return;
     }
     // the descriptor is requested together with the counts that say whether it exists (one round trip, not two): the big-part
     // list has a slot for every workgroup below its capacity; the short list is indexed behind the big count, so it waits
@@ -612,10 +631,9 @@ __global__ void __launch_bounds__(TFK_THREADS, 8) raster_tf_sort_kernel(
 // self-resetting, so no zero-fill launch precedes the forward.  Owned by the thread: freed when it exits (or on
 // r2_thread_release()); a thread that cycles through more streams than the table holds evicts the least recently used entry
 // (round 4: never freed, and the fast path silently switched itself off after 64 streams -- ADVICE r4).
-struct TFWorkspace { int dev; hipStream_t stream; TFCounters *ctr; uint32_t *nparts; bool dirty; unsigned long long used; int epoch; };
-// a deferred forward whose prediction fell short leaves its counters behind (nobody re-runs the chain): every workspace is then
-// cleaned before its next use (the backward that finds out runs on another thread: a process-wide epoch)
-std::atomic<int> g_tf_clean_epoch{0};
+// (a deferred forward whose prediction fell short gets no second pass: its sort kernel clears the counters it leaves behind --
+// the host may not know of the short count before the next forward on the stream is enqueued)
+struct TFWorkspace { int dev; hipStream_t stream; TFCounters *ctr; uint32_t *nparts; bool dirty; unsigned long long used; };
 struct TFWorkspaces {
     std::vector<TFWorkspace> v;
     unsigned long long tick = 0;
@@ -655,8 +673,7 @@ TFWorkspace *tf_workspace(int dev, hipStream_t s)
         (void)hipGetLastError();
         return nullptr;
     }
-    t.v.push_back(TFWorkspace{dev, s, reinterpret_cast<TFCounters *>(p), reinterpret_cast<uint32_t *>(p + sizeof(TFCounters)), true, t.tick,
-                              g_tf_clean_epoch.load(std::memory_order_relaxed)});
+    t.v.push_back(TFWorkspace{dev, s, reinterpret_cast<TFCounters *>(p), reinterpret_cast<uint32_t *>(p + sizeof(TFCounters)), true, t.tick});
     return &t.v.back();
 }
 
@@ -704,6 +721,15 @@ std::atomic<long long> g_tf_taken{0}, g_tf_declined{0}, g_tf_rerun{0}, g_tf_rere
 std::atomic<int> g_tf_mode{-1};   // -1: not decided yet (environment), 0: off, 1: on
 std::atomic<int> g_defer_mode{-1};   // deferred num_rendered (r2_defer_count_control): -1 environment, 0 off (default), 1 on
 std::atomic<long long> g_defer_taken{0}, g_defer_no_slot{0}, g_defer_short{0};
+
+// the one comparison of a deferred forward's true count with the capacity it was launched with: the forward thread's pending
+// poll, r2_defer_count_resolve and the backward all come here, and a short forward is counted once, whoever finds it first
+bool defer_count_short(int token, uint32_t count, uint32_t cap)
+{
+    if (count <= cap) return false;
+    if (defer_first_short(token)) g_defer_short.fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
 
 bool defer_enabled()
 {
@@ -780,9 +806,10 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     }
     const int PV = (int)PVs;
     for (size_t i = 0; i < g_tf_pending.size();) {
-        uint32_t pw[DW_COUNT];
+        uint32_t pw[DW_COUNT], pcap = 0;
         const TFPending pn = g_tf_pending[i];
-        if (defer_peek(pn.token, pw, DW_COUNT)) {
+        if (defer_peek(pn.token, pw, DW_COUNT, &pcap)) {
+            (void)defer_count_short(pn.token, pw[DW_TOTAL], pcap);   // (its counters were cleared on the device: counted only)
             raster_tilefirst_note(pn.P, pn.V, pn.W, pn.H, pw[DW_TOTAL], pw[DW_USER] != 0u, pw[DW_NMAX], ~pw[DW_NNMAX]);
             g_tf_pending.erase(g_tf_pending.begin() + (long)i);
         } else if (g_tf_pending.size() > 16) {
@@ -850,11 +877,9 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
         return R2_ERR_ALLOC;
     }
     const RasterGeom geom = RasterGeom::carve(gchunk, PV, TL, wgs);
-    const int epoch = g_tf_clean_epoch.load(std::memory_order_relaxed);
-    if (ws->dirty || ws->epoch != epoch)   // first use, a call that failed half way, or a deferred forward that fell short
+    if (ws->dirty)   // first use, or a call that failed half way
         R2_HIP_TRY(hipMemsetAsync(ws->ctr, 0, sizeof(TFCounters) + 64, s));
     ws->dirty = true;
-    ws->epoch = epoch;
     uint32_t *mailbox = nullptr, mailbox_seq = 0;
     int rc = 0, token = -1;
     if (defer && cap < (size_t)DEFER_TOKEN_FLAG) {
@@ -901,7 +926,7 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
             { StageScope t(ST_RAS_SORT, s);
             raster_tf_sort_kernel<<<dim3((unsigned)(img.NP + (TL + TFK_GROUPS - 1) / TFK_GROUPS)), dim3(TFK_THREADS), TFK_LDS, s>>>(
                 img.tf_parts, (uint32_t)img.NP, img.tf_parts + img.NP, ws->nparts, pairs, bin.point_list, ws->ctr, geom.host_words,
-                (uint32_t)std::min<size_t>(capacity, 0x7FFFFFFFu)); }
+                (uint32_t)std::min<size_t>(capacity, 0x7FFFFFFFu), token >= 0 ? (uint32_t)TL : 0u); }
             R2_HIP_TRY(hipGetLastError());
         } else {
             R2_HIP_TRY(hipMemsetAsync(img.tile_done, 0, 4 * T * sizeof(uint32_t), s));   // the first render left its arrivals behind
@@ -917,7 +942,7 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     if (rc) return rc;
     if (token >= 0) {
         // ---- deferred: no wait.  The token goes back as num_rendered; the backward resolves it (raster_backward_impl)
-        ws->dirty = false;   // (a count beyond the capacity is found by the backward, which bumps the clean epoch)
+        ws->dirty = false;   // (a count beyond the capacity: the sort kernel has cleared the counters -- clear_lists)
         g_tf_taken.fetch_add(1, std::memory_order_relaxed);
         g_defer_taken.fetch_add(1, std::memory_order_relaxed);
         path_count(PS_RAS_EVENT_DEFERRED);
@@ -950,16 +975,15 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
 
 void raster_tilefirst_release() { g_tf_ws.release(); g_tf_hints.clear(); g_tf_pending.clear(); }
 
-// the backward's side of a deferred forward: token -> the true instance count (waits for the control words, which the forward's
-// second kernel posted long ago); a count beyond the capacity the forward was launched with is an ERROR -- its kernels did nothing
-int raster_resolve_deferred(const char *what, int token, hipStream_t s, uint32_t *num_rendered)
+// the backward's side of a deferred forward (and r2_defer_count_resolve's, which keeps the slot: release = false): token -> the
+// true instance count (waits for the control words, which the forward's second kernel posted long ago); a count beyond the
+// capacity the forward was launched with is an ERROR -- its kernels did nothing
+int raster_resolve_deferred(const char *what, int token, hipStream_t s, uint32_t *num_rendered, bool release)
 {
     uint32_t hw[DW_COUNT] = { 0 }, cap = 0;
-    const int rc = defer_resolve(token, hw, DW_COUNT, &cap, s, true);
+    const int rc = defer_resolve(token, hw, DW_COUNT, &cap, s, release);
     if (rc) return rc;
-    if (hw[DW_TOTAL] > cap) {
-        g_defer_short.fetch_add(1, std::memory_order_relaxed);
-        g_tf_clean_epoch.fetch_add(1, std::memory_order_relaxed);
+    if (defer_count_short(token, hw[DW_TOTAL], cap)) {
         set_error("%s: the deferred forward's state was sized for %u instances, the scene has %u: its image and state are invalid "
                   "(R2_DEFER_COUNT / r2_defer_count_control trade the exact second pass for the missing wait; render this view again "
                   "with the mode off)", what, cap, hw[DW_TOTAL]);
@@ -983,6 +1007,19 @@ extern "C" void r2_tile_first_stats(long long *out, int reset)
 extern "C" void r2_defer_count_control(int mode)
 {
     if (mode == 0 || mode == 1) r2::g_defer_mode.store(mode, std::memory_order_relaxed);
+}
+
+extern "C" int r2_defer_count_resolve(int token, int *num_rendered, void *stream)
+{
+    if (token < r2::DEFER_TOKEN_FLAG || !num_rendered) {
+        r2::set_error("r2_defer_count_resolve: invalid argument (not a deferred forward's token)");
+        return R2_ERR_INVALID;
+    }
+    uint32_t n = 0;
+    const int rc = r2::raster_resolve_deferred("r2_defer_count_resolve", token, (hipStream_t)stream, &n, false);
+    if (rc) return rc;
+    *num_rendered = (int)n;
+    return 0;
 }
 
 extern "C" void r2_defer_count_stats(long long *out, int reset)

@@ -85,6 +85,7 @@ def hip_raster(c, v, dev, debug=False, cov3D_precomp=None, scale_modifier=1.0, c
     out["tiles_unsorted"] = read(2, np.uint32, R)
     out["vals_unsorted"] = read(3, np.uint32, R)
     out["point_list"] = read(5, np.uint32, R)
+    out["masked"] = read(16, np.uint32, R)   # what the render kernels read: point_list[k] << 4 | the instance's 8x8-block mask
     out["ranges"] = read(6, np.uint32, 2 * T).reshape(T, 2)
     out["tiles"] = tiles_from_ranges(out["ranges"], R)
     out["cov3D"] = read(7, np.float32, 6 * P).reshape(P, 6)

@@ -329,3 +329,106 @@ def test_gaussians_on_both_sides_of_the_recurrence_tier_match_the_oracle(L, orac
     dL = S.make_pixel_grad(192, 192).numpy()
     gh = Hh.hip_raster_backward(t, c, v, dL, gpu)
     Hh.parity_raster_grads(oracle, o, gh, c, v, dL, "both sides of item_tier")
+
+
+def test_deferred_forwards_without_a_backward(L, oracle, gpu):
+    """Forward-only deferred calls (evaluation under no_grad, a dropped step).  r2_defer_count_resolve turns a good token into the
+    waiting mode's num_rendered (repeat calls give the same answer and leave the token to its backward) and refuses a short one with
+    the backward's "sized for" error.  A short deferred forward that nobody resolves leaves nothing behind: the next forwards on the
+    thread and stream, waiting or deferred, are bit for bit a fresh waiting-mode render and the oracle's lists -- also when they are
+    enqueued before the host can have seen the short count.  Each short forward is counted once in r2_defer_count_stats()[2],
+    whether the thread's next forward, the resolve call or the backward finds it."""
+    import ctypes as C
+    from r2_gaussian_amd import _C, _lib
+    P = 30000
+    small = S.make_cloud(P, seed=12, scale_mult=0.5)
+    big = S.make_cloud(P, seed=12, scale_mult=3.0)
+    v = S.make_views(8, (256, 256))[3]
+    dL = S.make_pixel_grad(256, 256).numpy()
+    Hh.hip_raster(small, v, gpu)                          # a first call of this size: the general chain leaves the prediction
+    ref = Hh.hip_raster(small, v, gpu)                    # waiting mode, tile-first chain
+    assert Hh.took_tile_first(ref)
+    gref = Hh.hip_raster_backward(ref, small, v, dL, gpu)
+    o = Hh.oracle_raster(oracle, small, v, render=False)
+    Hh.check_binning(ref, o)
+    e = torch.empty(0)
+    bargs = (big.xyz.to(gpu), big.density.to(gpu), big.scales.to(gpu), big.rotations.to(gpu), 1.0, e, v.world_view_transform.to(gpu),
+             v.full_proj_transform.to(gpu), v.tanfovx, v.tanfovy, v.image_height, v.image_width, v.camera_center.to(gpu), False,
+             v.mode, False)
+
+    def short_forward(sync):
+        """a deferred forward of the big cloud on a prediction made from the small one: short (its state is not read back)"""
+        torch.cuda.synchronize()
+        Hh.hip_raster(small, v, gpu)                      # polls the thread's earlier tokens (their counts join the history) ...
+        L.r2_tile_first_control(2)                        # ... which is then forgotten:
+        Hh.hip_raster(small, v, gpu)                      # the general chain seeds the prediction with the small count
+        L.r2_defer_count_control(1)
+        R, _c, radii, gb, bb, ib = _C.rasterize_gaussians(*bargs)
+        L.r2_defer_count_control(0)
+        assert R >= 0x40000000, "the forward did not return a token"
+        if sync:
+            torch.cuda.synchronize()
+        return R, (radii, gb, bb, ib)
+
+    def same_as_ref(h):
+        assert np.array_equal(h["color"].view(np.uint32), ref["color"].view(np.uint32))
+        assert np.array_equal(h["radii"], ref["radii"])
+        assert np.array_equal(h["point_list"], ref["point_list"]) and np.array_equal(h["ranges"], ref["ranges"])
+        Hh.check_binning(h if h["num_rendered"] < 0x40000000 else dict(h, num_rendered=ref["num_rendered"]), o)
+
+    st = (C.c_longlong * 3)()
+    L.r2_defer_count_stats(st, 1)
+    try:
+        # ---- a good token: resolved to the waiting mode's count, twice; its backward still resolves it afterwards
+        L.r2_defer_count_control(1)
+        t = Hh.hip_raster(small, v, gpu, count_of=ref["num_rendered"])
+        L.r2_defer_count_control(0)
+        assert t["num_rendered"] >= 0x40000000
+        assert _C.defer_count_resolve(t["num_rendered"]) == ref["num_rendered"]
+        assert _C.defer_count_resolve(t["num_rendered"]) == ref["num_rendered"]
+        same_as_ref(t)
+        g = Hh.hip_raster_backward(t, small, v, dL, gpu)
+        for k in gref:
+            assert np.array_equal(g[k].view(np.uint32), gref[k].view(np.uint32)), k
+        with pytest.raises(_lib.R2HipError, match="stale token"):   # ... which released it
+            _C.defer_count_resolve(t["num_rendered"])
+        L.r2_defer_count_stats(st, 0)
+        assert st[2] == 0, list(st)
+        # ---- a short token: the resolve call refuses it, as often as asked, and counts it once
+        R1, _s1 = short_forward(sync=True)
+        for _ in range(2):
+            with pytest.raises(_lib.R2HipError, match="sized for"):
+                _C.defer_count_resolve(R1)
+        L.r2_defer_count_stats(st, 0)
+        assert st[2] == 1, list(st)
+        # ---- a short token nobody resolves, then a WAITING forward enqueued at once (the host cannot have seen the count)
+        R2, _s2 = short_forward(sync=False)
+        w = Hh.hip_raster(small, v, gpu)
+        assert Hh.took_tile_first(w)
+        same_as_ref(w)
+        # ---- ... then a DEFERRED forward right behind another short one; its backward resolves cleanly
+        R3, _s3 = short_forward(sync=False)
+        L.r2_defer_count_control(1)
+        d = Hh.hip_raster(small, v, gpu, count_of=None)
+        L.r2_defer_count_control(0)
+        assert d["num_rendered"] >= 0x40000000 and int(d["host_words"][0]) == ref["num_rendered"]
+        same_as_ref(d)
+        g = Hh.hip_raster_backward(d, small, v, dL, gpu)
+        for k in gref:
+            assert np.array_equal(g[k].view(np.uint32), gref[k].view(np.uint32)), k
+        # the thread's forwards have polled the two short tokens by now (or will: one more forward of the size)
+        Hh.hip_raster(small, v, gpu)
+        L.r2_defer_count_stats(st, 0)
+        assert st[2] == 3, list(st)
+        # ---- the short tokens' late backward and resolve calls: refused, counted no more
+        for R, (radii_b, gb, bb, ib) in ((R2, _s2), (R3, _s3)):
+            with pytest.raises(_lib.R2HipError, match="sized for"):
+                _C.defer_count_resolve(R)
+            with pytest.raises(_lib.R2HipError, match="sized for"):
+                _C.rasterize_gaussians_backward(bargs[0], radii_b, bargs[2], bargs[3], 1.0, e, bargs[6], bargs[7], bargs[8], bargs[9],
+                                                torch.as_tensor(dL).to(gpu), bargs[12], gb, R, bb, ib, v.mode, False)
+        torch.cuda.synchronize()
+        L.r2_defer_count_stats(st, 0)
+        assert st[2] == 3, list(st)
+    finally:
+        L.r2_defer_count_control(0)
