@@ -177,6 +177,21 @@ R2_API size_t r2_loss_tv3d_scratch_floats(int nx, int ny, int nz);
 R2_API int r2_loss_tv3d(int nx, int ny, int nz, const float *vol, float weight, float *dL_dvol, float *scratch,
                         float *scalars /* [2] */, void *stream);
 
+/* ---- evaluation metrics (r2_gaussian/utils/image_utils.py:90-184: metric_vol, metric_proj; forward only) ----
+ * r2_metric_slices: for every 2D slice of a C-contiguous float32 [n0,n1,n2] array taken along `axis` (slice i of axis 1 is
+ * a[:, i, :], rows n0, columns n2; of axis 2 a[:, :, i], rows n0, columns n1), per_slice[i] = {mean of the SSIM map (11x11
+ * Gaussian window, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2), sum (gt - pred)^2, max gt, max pred}, written on the
+ * device.  flags: R2_METRIC_SSIM computes the SSIM field (NaN without it: an SSE / maximum pass only); R2_METRIC_NORMALIZE
+ * divides each slice of both inputs by its own maximum first, as metric_proj does (the maxima fields stay those of the
+ * inputs).  No host synchronisation; sums are formed in a fixed order, in double per slice (bit-reproducible).  scratch:
+ * device floats, 16-byte aligned, at least r2_metric_slices_scratch_floats(n0, n1, n2, axis) (axis 2 includes a transposed
+ * copy of both inputs).  At most 65535 slices. */
+#define R2_METRIC_SSIM      1
+#define R2_METRIC_NORMALIZE 2
+R2_API size_t r2_metric_slices_scratch_floats(int n0, int n1, int n2, int axis);
+R2_API int r2_metric_slices(int n0, int n1, int n2, int axis, const float *gt, const float *pred, int flags,
+                            float *per_slice /* [n_axis][4] */, float *scratch, void *stream);
+
 /* ---- adaptive density control on the device (r2_gaussian/gaussian/gaussian_model.py:320-556, train.py:151-168) ----
  * r2_densify_stats: max_radii2D / xyz_gradient_accum / denom update of one rendered view (in place, one launch).
  * r2_densify_classify + r2_densify_emit: densify_and_prune -- clone (small Gaussians with a large view-space gradient; both

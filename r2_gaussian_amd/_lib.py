@@ -15,6 +15,8 @@ ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
 R2_ABI_VERSION = 3
 R2_ERR_INVALID = -10001
 R2_ERR_ALLOC = -10002
+R2_METRIC_SSIM = 1
+R2_METRIC_NORMALIZE = 2
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -61,6 +63,8 @@ _SIGNATURES = {
     "r2_loss_l1_ssim": (C.c_int, [_i, _i, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
     "r2_loss_tv3d_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "r2_loss_tv3d": (C.c_int, [_i, _i, _i, _fp, _f, _fp, _fp, _fp, _p]),
+    "r2_metric_slices_scratch_floats": (C.c_size_t, [_i, _i, _i, _i]),
+    "r2_metric_slices": (C.c_int, [_i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _p]),
     "r2_fdk_filter": (C.c_int, [_i, _i, _i, _fp, _fp, _f, _i, _f, _f, _f, _fp, _p]),
     "r2_fdk_backproject": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),

@@ -41,6 +41,7 @@ SOURCES = {
     "voxel_sticks.hip": FAST,
     "knn.hip": EXACT,
     "loss_ops.hip": FAST,
+    "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,
     "fdk.hip": FAST,
     "dispatch.hip": FAST,

@@ -12,18 +12,14 @@
 //   S = (2 m1 m2 + C1)(2 s12 + C2) / ((m1^2 + m2^2 + C1)(s1 + s2 + C2)),  m = W*x, s1 = W*x^2 - m1^2, s12 = W*xy - m1 m2
 //   dL/dx(p) = -lambda/N sum_q W(q-p) [ D1(q) + 2 x(p) D2(q) + y(p) D3(q) ] + sign(x - y)/N,
 //   D1 = dS/dm1 (with s1, s12 depending on m1), D2 = dS/d(W*x^2), D3 = dS/d(W*xy).
-#include "r2_common.hpp"
-#include <math.h>
+#include "ssim_window.hpp"
 
 namespace r2 {
 
 namespace {
 
-constexpr int LT = 16;              // output tile
-constexpr int WIN = 11, HALO = WIN / 2;
-constexpr int LR = LT + 2 * HALO;   // staged region: 26 x 26
-
-struct Window { float w[WIN]; };
+constexpr int LT = SSIM_LT, WIN = SSIM_WIN, HALO = SSIM_HALO, LR = SSIM_LR;
+using Window = SsimWindow;
 
 __device__ __forceinline__ float load_or_zero(const float *__restrict__ p, int x, int y, int W, int H)
 {
@@ -200,15 +196,6 @@ __global__ void __launch_bounds__(256) tv3d_finish_kernel(const float *__restric
     }
 }
 
-Window make_window()
-{
-    Window w;
-    double g[WIN], s = 0.0;
-    for (int i = 0; i < WIN; ++i) { g[i] = exp(-(double)((i - HALO) * (i - HALO)) / (2.0 * 1.5 * 1.5)); s += g[i]; }
-    for (int i = 0; i < WIN; ++i) w.w[i] = (float)(g[i] / s);
-    return w;
-}
-
 }  // namespace
 }  // namespace r2
 
@@ -230,7 +217,7 @@ extern "C" int r2_loss_l1_ssim(int width, int height, const float *img, const fl
     const int nb = (int)(grid.x * grid.y);
     float *D = scratch;
     float2 *partial = reinterpret_cast<float2 *>(scratch + 3 * (size_t)width * height);
-    const Window win = make_window();
+    const Window win = make_ssim_window();
     hipStream_t s = (hipStream_t)stream;
     ssim_forward_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, img, gt, win, D, partial);
     ssim_backward_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, img, gt, win, D, partial, nb, w_l1, w_ssim, dL_dimg, scalars);

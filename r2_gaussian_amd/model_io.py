@@ -115,9 +115,12 @@ def metric_vol(vol_gt, vol_pred, metric="psnr", pixel_max=1.0):
 
 
 @torch.no_grad()
-def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None):
+def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="host"):
     """query() of render_query.py:27-77 at the scanner's full resolution on the HIP voxelizer, + test.py's 3D metrics.
-    model: dict from load_point_cloud (raw parameters).  -> dict(vol, psnr_3d, ssim_3d, ...)."""
+    model: dict from load_point_cloud (raw parameters).  -> dict(vol, psnr_3d, ssim_3d, ...).
+    metrics="device": the metrics on the HIP kernels (r2_gaussian_amd.metrics, one host sync, the reference's NaN when no
+    slice of an axis counts); "host": the torch restatement above on a CPU copy."""
+    assert metrics in ("host", "device")
     from .voxelization import GaussianVoxelizationSettings, GaussianVoxelizer
     xyz, dens, scal, rot = activate(model)
     n, s, c = scanner_cfg["nVoxel"], scanner_cfg["sVoxel"], scanner_cfg["offOrigin"]
@@ -129,8 +132,12 @@ def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None):
     out = {"vol": vol, "radii": radii}
     if vol_gt is not None:
         gt = torch.as_tensor(vol_gt).to(vol.device)
-        out["psnr_3d"] = metric_vol(gt, vol, "psnr")[0]
-        out["ssim_3d"], (out["ssim_3d_x"], out["ssim_3d_y"], out["ssim_3d_z"]) = metric_vol(gt.cpu(), vol.cpu(), "ssim")
+        if metrics == "device":
+            from .metrics import metric_vol_both
+            out["psnr_3d"], out["ssim_3d"], (out["ssim_3d_x"], out["ssim_3d_y"], out["ssim_3d_z"]) = metric_vol_both(gt, vol)
+        else:
+            out["psnr_3d"] = metric_vol(gt, vol, "psnr")[0]
+            out["ssim_3d"], (out["ssim_3d_x"], out["ssim_3d_y"], out["ssim_3d_z"]) = metric_vol(gt.cpu(), vol.cpu(), "ssim")
         if save_dir:
             save_volumes(save_dir, gt, vol)
     return out
