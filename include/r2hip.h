@@ -169,7 +169,8 @@ R2_API int r2_raster_backward_batch(
  * r2_loss_l1_ssim: loss = w_l1 * mean|img - gt| + w_ssim * (1 - SSIM(img, gt)) (11x11 Gaussian window, sigma 1.5, zero
  * padding) of one [height,width] projection AND its gradient dL/dimg, in two launches; scalars = {l1 mean, ssim mean, loss}.
  * r2_loss_tv3d: tv = tv_3d_loss(vol, "mean") of a [nx,ny,nz] volume and dL/dvol = weight * d tv / d vol; scalars = {tv,
- * weight * tv}.  scratch: device floats, at least r2_loss_*_scratch_floats(...).  Sums are formed in a fixed order. */
+ * weight * tv}; a volume without neighbour pairs (1 x 1 x 1) gives tv = NaN (0 / 0, as the reference) and a zero gradient.
+ * scratch: device floats, at least r2_loss_*_scratch_floats(...).  Per-block sums are folded in a fixed order in double. */
 R2_API size_t r2_loss_l1_ssim_scratch_floats(int width, int height);
 R2_API int r2_loss_l1_ssim(int width, int height, const float *img, const float *gt, float w_l1, float w_ssim,
                            float *dL_dimg, float *scratch, float *scalars /* [3] */, void *stream);

@@ -132,19 +132,19 @@ __global__ void __launch_bounds__(LT * LT) ssim_backward_kernel(int W, int H, co
         const float invN = 1.0f / (float)N;
         dL_dx[o] = -w_ssim * invN * (b1 + 2.f * xv * b2 + yv * b3) + w_l1 * invN * sgn;
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0) {   // fixed-order reduction of the per-block sums: deterministic scalars
-        __shared__ float2 red[LT * LT / 64];
-        float2 acc = make_float2(0.f, 0.f);
-        for (int i = tid; i < nblocks; i += LT * LT) { acc.x += partial[i].x; acc.y += partial[i].y; }
+    if (blockIdx.x == 0 && blockIdx.y == 0) {   // fixed-order reduction of the per-block sums in double: deterministic scalars
+        __shared__ double red[LT * LT / 64][2];
+        double sS = 0.0, sA = 0.0;
+        for (int i = tid; i < nblocks; i += LT * LT) { const float2 q = partial[i]; sS += q.x; sA += q.y; }
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { acc.x += __shfl_xor(acc.x, d); acc.y += __shfl_xor(acc.y, d); }
-        if ((tid & 63) == 0) red[tid >> 6] = acc;
+        for (int d = 32; d >= 1; d >>= 1) { sS += __shfl_xor(sS, d); sA += __shfl_xor(sA, d); }
+        if ((tid & 63) == 0) { red[tid >> 6][0] = sS; red[tid >> 6][1] = sA; }
         __syncthreads();
         if (tid == 0) {
-            float2 t = red[0];
-            for (int w = 1; w < LT * LT / 64; ++w) { t.x += red[w].x; t.y += red[w].y; }
-            const float l1 = t.y / (float)N, ssim = t.x / (float)N;
-            scalars[0] = l1; scalars[1] = ssim; scalars[2] = w_l1 * l1 + w_ssim * (1.0f - ssim);
+            for (int w = 1; w < LT * LT / 64; ++w) { red[0][0] += red[w][0]; red[0][1] += red[w][1]; }
+            const double l1 = red[0][1] / (double)N, ssim = red[0][0] / (double)N;
+            scalars[0] = (float)l1; scalars[1] = (float)ssim;
+            scalars[2] = (float)((double)w_l1 * l1 + (double)w_ssim * (1.0 - ssim));
         }
     }
 }
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256) tv3d_kernel(int nx, int ny, int nz, const
         if (yy + 1 < ny) { const float d = v[i + sys] - c; g -= sgn(d); sum += fabsf(d); }
         if (z > 0) { const float d = c - v[i - 1]; g += sgn(d); }
         if (z + 1 < nz) { const float d = v[i + 1] - c; g -= sgn(d); sum += fabsf(d); }
-        dL_dv[i] = weight * g / cnt;
+        dL_dv[i] = cnt > 0.f ? weight * g / cnt : 0.f;   // no neighbour pairs: the reference's 0/0 value has a zero gradient
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
@@ -179,30 +179,36 @@ __global__ void __launch_bounds__(256) tv3d_kernel(int nx, int ny, int nz, const
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
 }
 
-__global__ void __launch_bounds__(256) tv3d_finish_kernel(const float *__restrict__ partial, int nblocks, float inv_cnt, float weight,
+// fixed-order fold of the per-block sums in double; cnt == 0 (no neighbour pairs) gives 0 / 0 = NaN like the reference
+__global__ void __launch_bounds__(256) tv3d_finish_kernel(const float *__restrict__ partial, int nblocks, double cnt, float weight,
                                                           float *__restrict__ scalars)
 {
-    __shared__ float red[4];
-    float s = 0.f;
+    __shared__ double red[4];
+    double s = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) s += partial[i];
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const float tv = (red[0] + red[1] + red[2] + red[3]) * inv_cnt;
-        scalars[0] = tv;
-        scalars[1] = weight * tv;
+        const double tv = (red[0] + red[1] + red[2] + red[3]) / cnt;
+        scalars[0] = (float)tv;
+        scalars[1] = (float)((double)weight * tv);
     }
 }
 
 }  // namespace
 }  // namespace r2
 
+namespace {
+// the float2 partials follow the three derivative maps, rounded up to an even float offset (8-byte aligned for odd W * H)
+size_t ssim_partial_offset(int width, int height) { return (3 * (size_t)width * height + 1) & ~(size_t)1; }
+}  // namespace
+
 extern "C" size_t r2_loss_l1_ssim_scratch_floats(int width, int height)
 {
     const size_t nb = (size_t)((width + r2::LT - 1) / r2::LT) * ((height + r2::LT - 1) / r2::LT);
-    return 3 * (size_t)width * height + 2 * nb;
+    return ssim_partial_offset(width, height) + 2 * nb;
 }
 
 extern "C" int r2_loss_l1_ssim(int width, int height, const float *img, const float *gt, float w_l1, float w_ssim,
@@ -216,7 +222,7 @@ extern "C" int r2_loss_l1_ssim(int width, int height, const float *img, const fl
     const dim3 grid((width + LT - 1) / LT, (height + LT - 1) / LT);
     const int nb = (int)(grid.x * grid.y);
     float *D = scratch;
-    float2 *partial = reinterpret_cast<float2 *>(scratch + 3 * (size_t)width * height);
+    float2 *partial = reinterpret_cast<float2 *>(scratch + ssim_partial_offset(width, height));
     const Window win = make_ssim_window();
     hipStream_t s = (hipStream_t)stream;
     ssim_forward_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, img, gt, win, D, partial);
@@ -243,7 +249,7 @@ extern "C" int r2_loss_tv3d(int nx, int ny, int nz, const float *vol, float weig
     const double cnt = (double)(nx - 1) * ny * nz + (double)nx * (ny - 1) * nz + (double)nx * ny * (nz - 1);
     hipStream_t s = (hipStream_t)stream;
     tv3d_kernel<<<dim3(nb), dim3(256), 0, s>>>(nx, ny, nz, vol, weight, dL_dvol, scratch);
-    tv3d_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(scratch, nb, (float)(1.0 / cnt), weight, scalars);
+    tv3d_finish_kernel<<<dim3(1), dim3(256), 0, s>>>(scratch, nb, cnt, weight, scalars);
     R2_STAGE_CHECK(0, s, "tv3d loss");
     return 0;
 }

@@ -12,9 +12,20 @@ from ._C import _on_device, _require_gpu, _stream
 _F32 = torch.float32
 
 
+def _check_image_shapes(image, gt):
+    """One [H, W] or [1, H, W] projection and a ground truth of the same size (the kernel reads gt with the image's W and H:
+    a mismatch would be a silently wrong value or a read past gt's end).  The reference raises a shape error here too."""
+    for name, t in (("image", image), ("gt", gt)):
+        if t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1):
+            raise ValueError("%s must be [H, W] or [1, H, W], got %s" % (name, tuple(t.shape)))
+    if tuple(gt.shape[-2:]) != tuple(image.shape[-2:]):
+        raise ValueError("gt is %s but the image is %s" % (tuple(gt.shape[-2:]), tuple(image.shape[-2:])))
+
+
 class _ImageLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt, w_l1, w_ssim):
+        _check_image_shapes(image, gt)
         _require_gpu(image, "image")
         img = image.reshape(image.shape[-2], image.shape[-1]).to(_F32).contiguous()
         ref = gt.reshape(gt.shape[-2], gt.shape[-1]).to(device=img.device, dtype=_F32).contiguous()
@@ -28,14 +39,14 @@ class _ImageLoss(torch.autograd.Function):
                                    scratch.data_ptr(), scalars.data_ptr(), _stream(img.device))
         _lib.check(rc, "r2_loss_l1_ssim")
         ctx.save_for_backward(grad)
-        ctx.shape = image.shape
+        ctx.shape, ctx.dtype = image.shape, image.dtype
         ctx.mark_non_differentiable(scalars)
         return scalars[2], scalars
 
     @staticmethod
     def backward(ctx, g, _):
         (grad,) = ctx.saved_tensors
-        return (grad * g).reshape(ctx.shape), None, None, None
+        return (grad * g).reshape(ctx.shape).to(ctx.dtype), None, None, None
 
 
 def image_loss(image, gt, lambda_dssim=0.25):
@@ -59,14 +70,16 @@ class _TV3D(torch.autograd.Function):
                                 _stream(v.device))
         _lib.check(rc, "r2_loss_tv3d")
         ctx.save_for_backward(grad)
+        ctx.dtype = vol.dtype
         return scalars[0]
 
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return grad * g
+        return (grad * g).to(ctx.dtype)
 
 
 def tv_3d_loss(vol):
-    """tv_3d_loss(vol, reduction="mean") of loss_utils.py:19-34 as one autograd node."""
+    """tv_3d_loss(vol, reduction="mean") of loss_utils.py:19-34 as one autograd node.  A volume without neighbour pairs
+    (1 x 1 x 1) gives NaN and a zero gradient, as the reference's 0 / 0 does."""
     return _TV3D.apply(vol)
