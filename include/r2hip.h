@@ -343,6 +343,23 @@ R2_API int r2_fdk_backproject(int V, int H, int W, const float *filtered_t, cons
                               int nx, int ny, int nz, float sVoxel_x, float sVoxel_y, float sVoxel_z, float center_x,
                               float center_y, float center_z, float *vol /* [nx,ny,nz] */, void *stream);
 
+/* ---- forward projection of a volume (tigre.Ax as generate_data.py:47-69 calls it to make a dataset) ----------------------
+ * r2_project_volume: out[V][H][W] = the line integral of the volume along the ray of every detector pixel, ray-driven.
+ * Coordinates are voxel-index coordinates q = (x - (center - sVoxel/2)) / dVoxel - 1/2 (voxel (i,j,k) at integer q, the
+ * voxelizer's and r2_fdk_backproject's convention).  rays[V][12] per view, in those coordinates: {a[3], p00[3], pu[3], pv[3]};
+ * the point of pixel (r, c) is P = p00 + c pu + r pv (the host puts it at the preimage of the pixel centre's detector NDC
+ * ((2c+1)/W - 1, (2r+1)/H - 1) under the rasterizer's camera).  cone != 0: the ray runs from the source a through P, t >= 0;
+ * cone == 0: the ray passes through P along the direction a, all t.
+ * The integrand f is the trilinear interpolant of vol[nx][ny][nz] with zero for neighbours outside [0, n_a - 1] (support
+ * [-1, n_a] on each axis).  The ray is clipped to that support ([t0, t1]; a ray that misses writes exactly 0), L = chord
+ * length in index units, n = max(1, ceil(L / accuracy)), and out = (t1 - t0)/n * |d_world| * sum over k = 0..n-1 in order of
+ * f(q(t0 + (k + 1/2)(t1 - t0)/n)), with d_world the ray direction times dVoxel: world length units.  t0, t1 and n come from
+ * separately rounded float32 operations.  No atomics, no allocation, no host synchronisation; bit-reproducible, and a view's
+ * output does not depend on the other views of the call.  V <= 65535, ny * nz < 2^32. */
+R2_API int r2_project_volume(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                             float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy, const float *vol /* [nx,ny,nz] */,
+                             float *out /* [V,H,W] */, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

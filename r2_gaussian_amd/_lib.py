@@ -67,6 +67,7 @@ _SIGNATURES = {
     "r2_metric_slices": (C.c_int, [_i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _p]),
     "r2_fdk_filter": (C.c_int, [_i, _i, _i, _fp, _fp, _f, _i, _f, _f, _f, _fp, _p]),
     "r2_fdk_backproject": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _fp, _p]),
+    "r2_project_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),
     "r2_profile_stage_count": (C.c_int, []),
     "r2_profile_stage_name": (C.c_char_p, [_i]),

@@ -44,6 +44,7 @@ SOURCES = {
     "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,
     "fdk.hip": FAST,
+    "projector.hip": EXACT,
     "dispatch.hip": FAST,
 }
 

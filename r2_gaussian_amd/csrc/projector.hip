@@ -1,0 +1,152 @@
+// projector.hip -- ray-driven forward projection of a voxel volume: the counterpart of tigre.Ax, which the reference's data
+// generator calls to turn a CT volume into its training and test projections
+// (data_generator/synthetic_dataset/generate_data.py:47-69).  fdk.hip is the back-projection half of the pair.
+//
+// One thread per detector pixel.  The ray of pixel (r, c) is P(r, c) = p00 + c pu + r pv, in voxel-index coordinates
+// (voxel (i,j,k) at integer q): a cone ray runs from the source s through P for t >= 0, a parallel ray through P along the
+// direction a for all t.  The host derives those 12 floats per view from the rasterizer's camera (projector.py), so the
+// projections are registered to rendered images by construction.
+//
+// The integrand is the trilinear interpolant of the volume with zero outside [0, n_a - 1], whose support is [-1, n_a].  The
+// ray is clipped to that box analytically ([t0, t1]; a ray that misses writes 0 and costs nothing), and the chord is cut into
+// n = max(1, ceil(L / accuracy)) equal pieces (L: chord length in index units) sampled at their midpoints:
+//     out = (t1 - t0)/n * |d|_world * sum_k f(q(t0 + (k + 1/2)(t1 - t0)/n)).
+// The sum runs over k in order in one thread: no atomics, and each pixel's bits depend only on its own ray.
+//
+// Work order: blockIdx.z is the view, so the grid walks the views one after the other and the volume stays in the Infinity
+// Cache while a view's rays traverse it; each wave covers an 8 x 8 pixel tile, so its 64 rays walk neighbouring voxels.
+// Hardware-filtered texture sampling is not used: its interpolation weights are fixed-point with 8 fractional bits
+// (an error of up to 2^-9 of the local voxel difference per sample), far beyond the float32 explicit gathers' error.
+//
+// This TU is compiled with -ffp-contract=off (build.py: EXACT): the clip points and n are separately rounded float32
+// operations, so the float64 restatement (tests/projector_ref.py) can tell which pixels sit on a decision boundary.  The
+// sampling loop contracts by hand (fmaf), where the restatement's bound covers it.
+#include "r2_common.hpp"
+#include <math.h>
+
+namespace r2 {
+
+namespace {
+
+constexpr int PT = 8;          // wave tile: PT x PT pixels
+constexpr int PB = 256;        // threads per block: 2 x 2 wave tiles
+constexpr int BW = 2 * PT, BH = 2 * PT;
+
+// Clip the line s + t d to the slab -1 <= q <= n of one axis.  Returns false when the line misses it.
+__device__ __forceinline__ bool clip_axis(float s, float d, int n, float &t0, float &t1)
+{
+    const float lo = -1.0f, hi = (float)n;
+    if (d == 0.0f) return s > lo && s < hi;
+    const float ta = (lo - s) / d, tb = (hi - s) / d;
+    t0 = fmaxf(t0, fminf(ta, tb));
+    t1 = fminf(t1, fmaxf(ta, tb));
+    return true;
+}
+
+// One axis of the trilinear footprint: the two neighbour indices clamped into the volume, and their weights, zero for a
+// neighbour outside it.
+struct Axis {
+    int i0, i1;
+    float w0, w1;
+};
+
+__device__ __forceinline__ Axis axis_of(float q, int n)
+{
+    // q lies in [-1, n] up to rounding; clamp before the int conversion so that no rounding can overflow it
+    const float f = floorf(fminf(fmaxf(q, -2.0f), (float)n + 1.0f));
+    const int i = (int)f;
+    const float w = q - f;
+    Axis a;
+    a.w0 = (unsigned)i < (unsigned)n ? 1.0f - w : 0.0f;
+    a.w1 = (unsigned)(i + 1) < (unsigned)n ? w : 0.0f;
+    a.i0 = min(max(i, 0), n - 1);
+    a.i1 = min(max(i + 1, 0), n - 1);
+    return a;
+}
+
+template <typename OFF>
+__global__ void __launch_bounds__(PB) project_kernel(int H, int W, const float *__restrict__ rays, int cone, int nx, int ny,
+                                                     int nz, float3 dv, float accuracy, const float *__restrict__ vol,
+                                                     float *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.x * BW + (wave & 1) * PT + (lane & (PT - 1));
+    const int r = blockIdx.y * BH + (wave >> 1) * PT + (lane / PT);
+    const int view = blockIdx.z;
+    if (c >= W || r >= H) return;
+    const float *R = rays + 12 * view;
+    const float fc = (float)c, fr = (float)r;
+    const float px = R[3] + fc * R[6] + fr * R[9];
+    const float py = R[4] + fc * R[7] + fr * R[10];
+    const float pz = R[5] + fc * R[8] + fr * R[11];
+    float sx, sy, sz, dx, dy, dz;
+    if (cone) {
+        sx = R[0]; sy = R[1]; sz = R[2];
+        dx = px - sx; dy = py - sy; dz = pz - sz;
+    } else {
+        sx = px; sy = py; sz = pz;
+        dx = R[0]; dy = R[1]; dz = R[2];
+    }
+    float t0 = cone ? 0.0f : -INFINITY, t1 = INFINITY;
+    const bool inside = clip_axis(sx, dx, nx, t0, t1) & clip_axis(sy, dy, ny, t0, t1) & clip_axis(sz, dz, nz, t0, t1);
+    float *o = out + ((size_t)view * H + r) * W + c;
+    if (!inside || !(t1 > t0)) {
+        *o = 0.0f;
+        return;
+    }
+    const float span = t1 - t0;
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    const float nf = ceilf(span * len / accuracy);
+    const int ns = max(1, (int)fminf(nf, 1073741824.0f));
+    const float dt = span / (float)ns;
+    // world length per unit t: the direction scaled back from index units by the voxel size
+    const float wx = dx * dv.x, wy = dy * dv.y, wz = dz * dv.z;
+    const float wlen = sqrtf(wx * wx + wy * wy + wz * wz);
+    // voxel offsets: unsigned 32-bit when the volume has fewer than 2^32 voxels (OFF = unsigned), 64-bit otherwise
+    const OFF sxy = (OFF)ny * (OFF)nz;
+    float acc = 0.0f;
+    for (int k = 0; k < ns; ++k) {
+        const float t = fmaf((float)k + 0.5f, dt, t0);
+        const Axis X = axis_of(fmaf(t, dx, sx), nx), Y = axis_of(fmaf(t, dy, sy), ny), Z = axis_of(fmaf(t, dz, sz), nz);
+        const OFF x0 = (OFF)X.i0 * sxy, x1 = X.i1 != X.i0 ? x0 + sxy : x0;
+        const unsigned y0 = (unsigned)Y.i0 * (unsigned)nz, y1 = Y.i1 != Y.i0 ? y0 + (unsigned)nz : y0;
+        const unsigned z0 = (unsigned)Z.i0, z1 = (unsigned)Z.i1;
+        // the clamped neighbours are always inside the volume: load all eight unconditionally (no branches around the
+        // gathers); a neighbour outside it has weight 0
+        const float v000 = vol[x0 + (y0 + z0)], v001 = vol[x0 + (y0 + z1)], v010 = vol[x0 + (y1 + z0)], v011 = vol[x0 + (y1 + z1)];
+        const float v100 = vol[x1 + (y0 + z0)], v101 = vol[x1 + (y0 + z1)], v110 = vol[x1 + (y1 + z0)], v111 = vol[x1 + (y1 + z1)];
+        const float c00 = fmaf(Z.w1, v001, Z.w0 * v000), c01 = fmaf(Z.w1, v011, Z.w0 * v010);
+        const float c10 = fmaf(Z.w1, v101, Z.w0 * v100), c11 = fmaf(Z.w1, v111, Z.w0 * v110);
+        const float c0 = fmaf(Y.w1, c01, Y.w0 * c00), c1 = fmaf(Y.w1, c11, Y.w0 * c10);
+        acc += fmaf(X.w1, c1, X.w0 * c0);
+    }
+    *o = acc * (dt * wlen);
+}
+
+}  // namespace
+
+}  // namespace r2
+
+extern "C" int r2_project_volume(int V, int H, int W, const float *rays, int cone, int nx, int ny, int nz, float dVoxel_x,
+                                 float dVoxel_y, float dVoxel_z, float accuracy, const float *vol, float *out, void *stream)
+{
+    using namespace r2;
+    if (V <= 0 || H <= 0 || W <= 0 || nx <= 0 || ny <= 0 || nz <= 0 || !rays || !vol || !out || !(accuracy > 0.f) ||
+        !(dVoxel_x > 0.f) || !(dVoxel_y > 0.f) || !(dVoxel_z > 0.f)) {
+        set_error("r2_project_volume: invalid argument");
+        return R2_ERR_INVALID;
+    }
+    if ((long long)ny * nz >= (1LL << 32) || V > 65535 || (H + BH - 1) / BH > 65535) {
+        set_error("r2_project_volume: shape out of range (V %d, H %d, ny*nz %lld)", V, H, (long long)ny * nz);
+        return R2_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((W + BW - 1) / BW, (H + BH - 1) / BH, V);
+    const float3 d = make_float3(dVoxel_x, dVoxel_y, dVoxel_z);
+    if ((unsigned long long)nx * ny * nz < (1ULL << 32))
+        project_kernel<unsigned><<<grid, dim3(PB), 0, s>>>(H, W, rays, cone, nx, ny, nz, d, accuracy, vol, out);
+    else
+        project_kernel<size_t><<<grid, dim3(PB), 0, s>>>(H, W, rays, cone, nx, ny, nz, d, accuracy, vol, out);
+    R2_STAGE_CHECK(0, s, "project volume");
+    return 0;
+}

@@ -1,0 +1,116 @@
+"""Synthetic CT dataset generation without TIGRE: ``main`` of data_generator/synthetic_dataset/generate_data.py on the
+projector of projector.py.
+
+    python -m r2_gaussian_amd.datagen --vol vol.npy --scanner cone_beam.yml --output data/case_dir [--n_train 50]
+                                      [--n_test 100] [--seed 0]
+
+writes ``{output}/{vol_name}_{mode}/`` with ``vol_gt.npy``, ``proj_train/proj_train_%04d.npy``,
+``proj_test/proj_test_%04d.npy`` (float32 [H, W], the rasterizer's row order) and ``meta_data.json`` (keys scanner, vol,
+bbox, proj_train, proj_test; each projection entry {file_path, angle}) -- the layout dataset_readers.py reads.
+
+Training angles are linspace(0, totalAngle, n_train + 1)[:-1] + startAngle, test angles sort(rand(n_test) 2 pi) + startAngle
+(radians; the config's angles are degrees).  With ``noise: true`` the training stack gets ``add_noise`` (TIGRE's
+``CTnoise.add``) and its negatives are clipped to 0; test projections stay noise-free.  Every draw comes from one explicit
+``numpy.random.RandomState`` (``--seed``), so a seed reproduces a dataset bit for bit -- the reference draws from numpy's
+global generator.
+"""
+import argparse
+import json
+import os
+import os.path as osp
+
+import numpy as np
+
+from . import projector as P
+
+
+def add_noise(projs, i0, gaussian, rng):
+    """Restatement of TIGRE's ``CTnoise.add(projs, Poisson=i0, Gaussian=[mu, sigma])`` applied to the whole stack,
+    followed by the clip of negatives of generate_data.py:59: with m = max(projs),
+    I = Poisson(i0 exp(-projs / m)) + Normal(mu, sigma), I <= 0 -> 1e-6, projs = -log(I / i0) m, then max(projs, 0).
+    Unpinned: TIGRE is not available to compare against, this follows its published source.  Draws: first the Poisson
+    field, then the normal field, both from ``rng`` (a numpy RandomState) in C order.  float32 result."""
+    p = np.asarray(projs, dtype=np.float64)
+    mu, sigma = (float(x) for x in gaussian)
+    m = float(p.max())
+    if not m > 0:
+        return np.asarray(projs, dtype=np.float32).copy()   # an all-zero stack: exp(-0/0) is undefined, nothing attenuates
+    intensity = rng.poisson(i0 * np.exp(-p / m)).astype(np.float64)
+    intensity = intensity + rng.normal(mu, sigma, size=p.shape)
+    intensity[intensity <= 0] = 1e-6
+    out = (-np.log(intensity / i0) * m).astype(np.float32)
+    out[out < 0.0] = 0.0
+    return out
+
+
+def noisy_train(projs, cfg, rng):
+    """The training stack as generate_data.py:51-60 saves it: ``add_noise`` when the config says ``noise: true``, else
+    ``projs`` itself."""
+    if not cfg.get("noise", False):
+        return projs
+    return add_noise(projs, cfg["possion_noise"], cfg["gaussian_noise"], rng)
+
+
+def angles_for(cfg, n_train, n_test, rng):
+    """-> (train angles, test angles) in radians (generate_data.py:47-50, 63-66)."""
+    start = cfg.get("startAngle", 0.0) / 180.0 * np.pi
+    train = np.linspace(0.0, cfg.get("totalAngle", 360.0) / 180.0 * np.pi, n_train + 1)[:-1] + start
+    test = np.sort(rng.rand(n_test) * 360.0 / 180.0 * np.pi) + start
+    return train, test
+
+
+def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles_test):
+    """The on-disk layout of generate_data.py:70-100 for given projections [V, H, W]; -> the meta dictionary written."""
+    os.makedirs(case_dir, exist_ok=True)
+    np.save(osp.join(case_dir, "vol_gt.npy"), np.asarray(vol, dtype=np.float32))
+    entries = {}
+    for split, projs, angles in (("proj_train", projs_train, angles_train), ("proj_test", projs_test, angles_test)):
+        os.makedirs(osp.join(case_dir, split), exist_ok=True)
+        entries[split] = []
+        for i in range(len(angles)):
+            name = osp.join(split, "%s_%04d.npy" % (split, i))
+            np.save(osp.join(case_dir, name), np.ascontiguousarray(projs[i], dtype=np.float32))
+            entries[split].append({"file_path": name, "angle": float(angles[i])})
+    meta = {"scanner": cfg, "vol": "vol_gt.npy", "bbox": [[-1, -1, -1], [1, 1, 1]],
+            "proj_train": entries["proj_train"], "proj_test": entries["proj_test"]}
+    with open(osp.join(case_dir, "meta_data.json"), "w", encoding="utf-8") as f:
+        json.dump(meta, f, indent=4)
+    return meta
+
+
+def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda"):
+    """Project ``vol`` [nx,ny,nz] with the raw scanner config ``cfg`` and write the case ``{output}/{vol_name}_{mode}``;
+    -> the case directory."""
+    rng = np.random.RandomState(seed)
+    vol = np.asarray(vol, dtype=np.float32)
+    train_angles, test_angles = angles_for(cfg, n_train, n_test, rng)
+    train = P.project(vol, train_angles, cfg, device=device).cpu().numpy()
+    train = noisy_train(train, cfg, rng)
+    test = P.project(vol, test_angles, cfg, device=device).cpu().numpy()
+    case_dir = osp.join(output, "%s_%s" % (vol_name, cfg["mode"]))
+    write_case(case_dir, cfg, vol, train, train_angles, test, test_angles)
+    return case_dir
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Data generator parameters")
+    ap.add_argument("--vol", default="data_generator/volume_gt/0_chest.npy", type=str, help="Path to volume.")
+    ap.add_argument("--scanner", default="data_generator/scanner/cone_beam.yml", type=str,
+                    help="Path to scanner configuration.")
+    ap.add_argument("--output", default="data/cone_ntrain_50_angle_360", type=str, help="Path to output.")
+    ap.add_argument("--n_train", default=50, type=int, help="Number of projections for training.")
+    ap.add_argument("--n_test", default=100, type=int, help="Number of projections for evaluation.")
+    ap.add_argument("--seed", default=0, type=int, help="Seed of every random draw (test angles, noise).")
+    args = ap.parse_args(argv)
+    import yaml
+    with open(args.scanner, "r") as f:
+        cfg = yaml.safe_load(f)
+    vol_name = osp.basename(args.vol)[:-4]
+    print("Generate data for case %s_%s" % (vol_name, cfg["mode"]))
+    case_dir = generate(np.load(args.vol), cfg, args.output, vol_name, args.n_train, args.n_test, args.seed)
+    print("Generate data for case %s complete!" % osp.basename(case_dir))
+    return case_dir
+
+
+if __name__ == "__main__":
+    main()
