@@ -227,6 +227,18 @@ TF_MARK = 0x71FE   # host word DW_PMAX of a rasterizer forward that took the til
 VOX_STICKS_MARK = 0x571C
 
 
+def sticks_mode():
+    """Fixture body (tests/test_voxel_sticks_gpu.py, tests/test_voxel_tiers_gpu.py): -> a setter of the stick-first chain's mode
+    (0 off, 1 on); the default, the parts switch and the thread's notes are restored afterwards."""
+    from r2_gaussian_amd import _lib
+    L = _lib.lib()
+    L.r2_voxel_sticks_control(3)
+    yield L.r2_voxel_sticks_control
+    L.r2_voxel_sticks_control(1)
+    L.r2_voxel_sticks_control(5)
+    L.r2_voxel_sticks_control(3)
+
+
 def took_sticks(h):
     return int(h["host_words"][2]) == VOX_STICKS_MARK
 

@@ -12,11 +12,7 @@ GPU; this pins the two claims their comments make, over Gaussians far more extre
 import numpy as np
 import pytest
 
-LOG2E = 1.4426950408889634
-LN2 = 0.6931471805599453
-LOG2_ALPHA_MIN = -19.931568569324174
-ALPHA_MIN = 1e-6
-f32 = np.float32
+from tests.voxel_ref import ALPHA_MIN, LOG2_ALPHA_MIN, f32, needs_exact, record, slab_live
 
 
 def random_gaussians(n, seed, smin, smax):
@@ -36,32 +32,6 @@ def random_gaussians(n, seed, smin, smax):
     return mean, conic, op
 
 
-def record(mean, conic, op):
-    """What voxel_preprocess_one stores: float32 record + culling extents (computed in double from the float32 conic)."""
-    A, B, C, D, E, F = (conic[:, 0, 0].astype(f32).astype(np.float64), conic[:, 0, 1].astype(f32).astype(np.float64),
-                        conic[:, 0, 2].astype(f32).astype(np.float64), conic[:, 1, 1].astype(f32).astype(np.float64),
-                        conic[:, 1, 2].astype(f32).astype(np.float64), conic[:, 2, 2].astype(f32).astype(np.float64))
-    L = np.log2(op.astype(f32)).astype(f32)
-    qmax = 2.0 * LN2 * (L.astype(np.float64) - LOG2_ALPHA_MIN) + 1e-3
-    m00, m11, m22 = D * F - E * E, A * F - C * C, A * D - B * B
-    det3 = A * m00 - B * (B * F - C * E) + C * (B * E - C * D)
-    ok = (qmax > 0) & (A > 0) & (m22 > 0) & (det3 > 0) & (m00 > 0) & (m11 > 0) & (D > 0) & (F > 0) & \
-         ((A + D + F) * (m00 + m11 + m22) <= 1.0e4 * det3)
-    with np.errstate(all="ignore"):
-        hx = np.where(ok, np.sqrt(qmax * m00 / det3) * 1.004 + 0.05, np.inf)
-        hyc = np.where(ok, np.sqrt(qmax * F / m00) * 1.004 + 0.05, np.inf)
-        hzc = np.where(ok, np.sqrt(qmax * D / m00) * 1.004 + 0.05, np.inf)
-        ky = np.where(ok, -(F * B - E * C) / m00, 0.0)
-        kz = np.where(ok, -(D * C - E * B) / m00, 0.0)
-    dead = ~(qmax > 0)
-    hx, hyc, hzc = (np.where(dead, -np.inf, h) for h in (hx, hyc, hzc))
-    rec = dict(p=mean.astype(f32),
-               a2=(f32(-0.5 * LOG2E) * A.astype(f32)), b2=(f32(-LOG2E) * B.astype(f32)), c2=(f32(-LOG2E) * C.astype(f32)),
-               d2=(f32(-0.5 * LOG2E) * D.astype(f32)), e2=(f32(-LOG2E) * E.astype(f32)), f2=(f32(-0.5 * LOG2E) * F.astype(f32)),
-               L=L, hx=hx.astype(f32), hyc=hyc.astype(f32), hzc=hzc.astype(f32), ky=ky.astype(f32), kz=kz.astype(f32), safe=ok)
-    return rec
-
-
 def exponent_double(rec, xc):
     """log2(alpha) of the 8 x 8 voxels of the slab x = xc of tile [0,8)^3, in double from the float32 record: [n, y, z]."""
     p = rec["p"].astype(np.float64)
@@ -70,18 +40,6 @@ def exponent_double(rec, xc):
     dz = p[:, 2][:, None, None] - (np.arange(8) + 0.5)[None, None, :]
     g = {k: rec[k].astype(np.float64)[:, None, None] for k in ("a2", "b2", "c2", "d2", "e2", "f2", "L")}
     return g["a2"] * dx * dx + g["b2"] * dx * dy + g["c2"] * dx * dz + g["d2"] * dy * dy + g["e2"] * dy * dz + g["f2"] * dz * dz + g["L"]
-
-
-def slab_live(rec, xc):
-    """csrc/voxel_render.hip: slab_live, in float32."""
-    p = rec["p"]
-    with np.errstate(all="ignore"):
-        dx = p[:, 0] - f32(xc)
-        u = dx * (f32(1.0) / rec["hx"])
-        t = np.sqrt(np.maximum(f32(1.0) - u * u, f32(0.0))).astype(f32)
-        cy, cz = p[:, 1] - rec["ky"] * dx, p[:, 2] - rec["kz"] * dx
-        ey, ez = rec["hyc"] * t, rec["hzc"] * t
-        return (np.abs(dx) <= rec["hx"]) & (cy - ey <= f32(7.5)) & (cy + ey >= f32(0.5)) & (cz - ez <= f32(7.5)) & (cz + ez >= f32(0.5))
 
 
 @pytest.mark.parametrize("smin,smax,seed", [(0.8, 3.0, 1), (0.25, 6.0, 2), (0.05, 12.0, 3)], ids=["ordinary", "anisotropic", "extreme"])
@@ -102,15 +60,6 @@ def test_cross_section_slab_test_never_drops_a_live_slab(smin, smax, seed):
     assert box_total < 8 * len(op), "the test never culled anything"
     if smax <= 3.0:   # compact Gaussians: the cross-section test is tight (exact set / kept set)
         assert live_total >= 0.6 * box_total, (live_total, box_total)
-
-
-def needs_exact(rec):
-    """voxel_state.hpp: needs_exact_slab3 (VOX_RECUR_YSTEPS = 3, VOX_RECUR_STEPS - 1 = 3)."""
-    L = rec["L"]
-    with np.errstate(all="ignore"):
-        smax = np.sqrt(np.maximum(f32(125.5) + np.minimum(L, f32(0)), f32(0))) - np.sqrt(np.maximum(L - f32(LOG2_ALPHA_MIN), f32(0)) + f32(1))
-        need = f32(3) * np.sqrt(np.abs(rec["d2"])) + f32(3) * np.sqrt(np.abs(rec["f2"]))
-    return ~((smax > 0) & (need <= smax)) | ~(rec["hx"] < f32(3.0e38))
 
 
 def step_float32(rec, xc):

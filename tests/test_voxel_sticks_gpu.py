@@ -24,15 +24,7 @@ def _stats(reset=True):
     return list(st)   # taken, fallback, declined
 
 
-@pytest.fixture
-def sticks_mode():
-    """-> a setter of the chain's mode (0 off, 1 on); the default and the thread's notes are restored afterwards"""
-    L = _lib()
-    L.r2_voxel_sticks_control(3)
-    yield L.r2_voxel_sticks_control
-    L.r2_voxel_sticks_control(1)
-    L.r2_voxel_sticks_control(5)
-    L.r2_voxel_sticks_control(3)
+sticks_mode = pytest.fixture(Hh.sticks_mode)
 
 
 # (P, nVoxel, sVoxel, center, scale_mult, mode)
