@@ -360,6 +360,32 @@ R2_API int r2_project_volume(int V, int H, int W, const float *rays /* [V,12] */
                              float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy, const float *vol /* [nx,ny,nz] */,
                              float *out /* [V,H,W] */, void *stream);
 
+/* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
+ * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
+ * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel
+ * (view, r, c) with the forward's float32 t0, n, dt and |d_world|, and its sample points q_k = fma(fma(k + 1/2, dt, t0), d, s):
+ *     A[rho, v] = dt |d_world| sum_k X_k(v_x) Y_k(v_y) Z_k(v_z),
+ * X_k(i) = the forward's trilinear weight w0 where i is the floor index of q_k,x, w1 where it is floor + 1, 0 otherwise
+ * (likewise Y, Z); vol[v] = sum over the views in order of sum_rho A[rho, v] projs[rho].  The clip, hit or miss, n, the
+ * sample positions and the weights are bit-identical to the forward's (csrc/ray_sampling.hpp is shared); only the rounding
+ * of the products and sums differs.  Voxel-driven: no atomics, no allocation, no host synchronisation; bit-reproducible,
+ * and `vol` is overwritten (its prior contents never matter).  A cone source anywhere, inside the volume included, is
+ * handled (the voxels whose support reaches the source plane gather from the whole detector).  The forward's limits plus
+ * nx, ny <= 4 * 65535. */
+R2_API int r2_backproject_volume(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                                 float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy,
+                                 const float *projs /* [V,H,W] */, float *vol /* [nx,ny,nz] */, void *stream);
+/* r2_tv_descent: n_iter steps of normalised steepest descent on TV_eps(x) = sum_v sqrt(Dx(v)^2 + Dy(v)^2 + Dz(v)^2 + eps),
+ * eps = 1e-8, for vol[nx][ny][nz] (z fastest), with forward differences Dx(i,j,k) = x(i+1,j,k) - x(i,j,k) and Dx = 0 at
+ * i = nx - 1 (Neumann; likewise y, z).  Its gradient is
+ *     g(v) = - (Dx(v) + Dy(v) + Dz(v)) / s(v) + sum_a [v_a > 0] Da(v - e_a) / s(v - e_a),   s = sqrt(Dx^2 + Dy^2 + Dz^2 + eps),
+ * and each step is  x <- x - (*step / |g|_2) g,  skipped when |g|_2 = 0 (no division by zero).  |g|_2 is a fixed-order
+ * on-device reduction (double partial sums); `step` is a device scalar, read by the kernels: no host synchronisation.
+ * scratch: a device buffer of at least r2_tv_descent_scratch_bytes(nx, ny, nz) bytes, 8-byte aligned. */
+R2_API size_t r2_tv_descent_scratch_bytes(int nx, int ny, int nz);
+R2_API int r2_tv_descent(int nx, int ny, int nz, float *vol, const float *step /* device scalar */, int n_iter, void *scratch,
+                         size_t scratch_bytes, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

@@ -45,6 +45,8 @@ SOURCES = {
     "densify_ops.hip": EXACT,
     "fdk.hip": FAST,
     "projector.hip": EXACT,
+    "backprojector.hip": EXACT,
+    "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }
 

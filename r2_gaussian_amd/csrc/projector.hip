@@ -22,6 +22,7 @@
 // operations, so the float64 restatement (tests/projector_ref.py) can tell which pixels sit on a decision boundary.  The
 // sampling loop contracts by hand (fmaf), where the restatement's bound covers it.
 #include "r2_common.hpp"
+#include "ray_sampling.hpp"
 #include <math.h>
 
 namespace r2 {
@@ -31,38 +32,6 @@ namespace {
 constexpr int PT = 8;          // wave tile: PT x PT pixels
 constexpr int PB = 256;        // threads per block: 2 x 2 wave tiles
 constexpr int BW = 2 * PT, BH = 2 * PT;
-
-// Clip the line s + t d to the slab -1 <= q <= n of one axis.  Returns false when the line misses it.
-__device__ __forceinline__ bool clip_axis(float s, float d, int n, float &t0, float &t1)
-{
-    const float lo = -1.0f, hi = (float)n;
-    if (d == 0.0f) return s > lo && s < hi;
-    const float ta = (lo - s) / d, tb = (hi - s) / d;
-    t0 = fmaxf(t0, fminf(ta, tb));
-    t1 = fminf(t1, fmaxf(ta, tb));
-    return true;
-}
-
-// One axis of the trilinear footprint: the two neighbour indices clamped into the volume, and their weights, zero for a
-// neighbour outside it.
-struct Axis {
-    int i0, i1;
-    float w0, w1;
-};
-
-__device__ __forceinline__ Axis axis_of(float q, int n)
-{
-    // q lies in [-1, n] up to rounding; clamp before the int conversion so that no rounding can overflow it
-    const float f = floorf(fminf(fmaxf(q, -2.0f), (float)n + 1.0f));
-    const int i = (int)f;
-    const float w = q - f;
-    Axis a;
-    a.w0 = (unsigned)i < (unsigned)n ? 1.0f - w : 0.0f;
-    a.w1 = (unsigned)(i + 1) < (unsigned)n ? w : 0.0f;
-    a.i0 = min(max(i, 0), n - 1);
-    a.i1 = min(max(i + 1, 0), n - 1);
-    return a;
-}
 
 template <typename OFF>
 __global__ void __launch_bounds__(PB) project_kernel(int H, int W, const float *__restrict__ rays, int cone, int nx, int ny,
@@ -74,39 +43,23 @@ __global__ void __launch_bounds__(PB) project_kernel(int H, int W, const float *
     const int r = blockIdx.y * BH + (wave >> 1) * PT + (lane / PT);
     const int view = blockIdx.z;
     if (c >= W || r >= H) return;
-    const float *R = rays + 12 * view;
-    const float fc = (float)c, fr = (float)r;
-    const float px = R[3] + fc * R[6] + fr * R[9];
-    const float py = R[4] + fc * R[7] + fr * R[10];
-    const float pz = R[5] + fc * R[8] + fr * R[11];
-    float sx, sy, sz, dx, dy, dz;
-    if (cone) {
-        sx = R[0]; sy = R[1]; sz = R[2];
-        dx = px - sx; dy = py - sy; dz = pz - sz;
-    } else {
-        sx = px; sy = py; sz = pz;
-        dx = R[0]; dy = R[1]; dz = R[2];
-    }
-    float t0 = cone ? 0.0f : -INFINITY, t1 = INFINITY;
-    const bool inside = clip_axis(sx, dx, nx, t0, t1) & clip_axis(sy, dy, ny, t0, t1) & clip_axis(sz, dz, nz, t0, t1);
+    const Ray y = pixel_ray(rays + 12 * view, cone, r, c);
+    float t0, t1;
+    const bool hit = clip_ray(y, cone, nx, ny, nz, t0, t1);
     float *o = out + ((size_t)view * H + r) * W + c;
-    if (!inside || !(t1 > t0)) {
+    if (!hit) {
         *o = 0.0f;
         return;
     }
-    const float span = t1 - t0;
-    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    const float nf = ceilf(span * len / accuracy);
-    const int ns = max(1, (int)fminf(nf, 1073741824.0f));
-    const float dt = span / (float)ns;
-    // world length per unit t: the direction scaled back from index units by the voxel size
-    const float wx = dx * dv.x, wy = dy * dv.y, wz = dz * dv.z;
-    const float wlen = sqrtf(wx * wx + wy * wy + wz * wz);
+    const Sampling m = ray_sampling(y, t0, t1, dv, accuracy);
+    const float sx = y.sx, sy = y.sy, sz = y.sz, dx = y.dx, dy = y.dy, dz = y.dz;
+    const int ns = m.n;
+    const float dt = m.dt, wlen = m.wlen;
     // voxel offsets: unsigned 32-bit when the volume has fewer than 2^32 voxels (OFF = unsigned), 64-bit otherwise
     const OFF sxy = (OFF)ny * (OFF)nz;
     float acc = 0.0f;
     for (int k = 0; k < ns; ++k) {
-        const float t = fmaf((float)k + 0.5f, dt, t0);
+        const float t = sample_t(k, dt, t0);
         const Axis X = axis_of(fmaf(t, dx, sx), nx), Y = axis_of(fmaf(t, dy, sy), ny), Z = axis_of(fmaf(t, dz, sz), nz);
         const OFF x0 = (OFF)X.i0 * sxy, x1 = X.i1 != X.i0 ? x0 + sxy : x0;
         const unsigned y0 = (unsigned)Y.i0 * (unsigned)nz, y1 = Y.i1 != Y.i0 ? y0 + (unsigned)nz : y0;

@@ -118,7 +118,10 @@ def fdk(projs, angles, scanner_cfg, filter_name=None, device="cuda"):
 
 
 def recon_volume(projs, angles, scanner_cfg, recon_method="fdk"):
-    """ct_utils.py:17-27 for ``recon_method="fdk"``: numpy volume [nx,ny,nz]."""
+    """ct_utils.py:17-27: numpy volume [nx,ny,nz]; ``"cgls"`` is recon.py's (60 iterations)."""
+    if recon_method == "cgls":
+        from . import recon
+        return recon.recon_volume(projs, angles, scanner_cfg, "cgls")
     if recon_method != "fdk":
         raise ValueError("Unsupported reconstruction method")
     return fdk(projs, angles, scanner_cfg).cpu().numpy()

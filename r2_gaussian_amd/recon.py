@@ -1,0 +1,490 @@
+"""Classical iterative CT reconstructions without TIGRE: CGLS, SART, OS-SART, ASD-POCS and OS-ASD-POCS, the baselines of
+the reference's ``run_ct_recon_algs`` (r2_gaussian/utils/ct_utils.py:60-215) and ``scripts/run_traditional_methods.py``.
+
+They stand on two MI355X kernels behind the C ABI: the forward projector ``r2_project_volume`` (``A``, projector.py) and its
+exact transpose ``r2_backproject_volume`` (``A^T``, csrc/backprojector.hip), plus ``r2_tv_descent`` (csrc/tv_descent.hip) for
+the TV steps of ASD-POCS.  The vector updates between them are elementwise tensor operations; every data-dependent scalar
+stays a 0-d device tensor, so an iteration makes no host synchronisation unless ``computel2`` or ``verbose`` asks for one.
+
+Conventions are those of ``projector.project`` and ``fdk.fdk``: the raw scanner config and its length units, projections
+[V, H, W] as datagen writes them (rasterizer row order), volumes [nx, ny, nz] in ``query()`` layout.  In those units the
+operator is ``A = project(., angles, cfg)``, i.e. ``A_scene / scale`` with ``scale = 2 / max(sVoxel)``, and
+``backproject`` is its transpose ``A_scene^T / scale``.
+
+The algorithms are restated from their published definitions (INTEGRATION.md lists where they knowingly differ from TIGRE):
+
+* CGLS (Hestenes-Stiefel / Bjorck): x0 = 0, r = b, p = s = A^T r, gamma = |s|^2; per iteration q = A p,
+  alpha = gamma / |q|^2, x += alpha p, r -= alpha q, s = A^T r, gamma' = |s|^2, p = s + (gamma' / gamma) p.
+* OS-SART (Jiang & Wang; SART is blocksize 1): W = 1 / (A 1) per ray (0 where a ray misses), V_B = A_B^T 1 per block of
+  consecutive views in input order (V^-1 = 0 where V_B = 0); for each block x <- max(0, x + lambda V_B^-1 (A_B^T (W (b_B -
+  A_B x)))), and lambda <- lambda lambda_red after each sweep over all blocks.
+* ASD-POCS (Sidky & Pan 2008), see ``os_asd_pocs``.
+"""
+import argparse
+import json
+import os
+import os.path as osp
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import fdk as F
+from . import projector as P
+from . import scene as S
+from ._C import _on_device, _require_gpu, _stream
+
+_F32 = torch.float32
+_F64 = torch.float64
+METHODS = ("fdk", "sart", "ossart", "asd_pocs", "os_asd_pocs", "cgls")
+
+
+# ---- the adjoint ----------------------------------------------------------------------------------------------------------
+
+def _backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy, out):
+    V, H, W = projs.shape
+    nx, ny, nz = nVoxel
+    L = _lib.lib()
+    with _on_device(projs.device):
+        rc = L.r2_backproject_volume(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]), float(dVoxel[1]),
+                                     float(dVoxel[2]), float(accuracy), projs.data_ptr(), out.data_ptr(),
+                                     _stream(projs.device))
+    _lib.check(rc, "r2_backproject_volume")
+    return out
+
+
+def _project_rays(vol, rays, cone, H, W, dVoxel, accuracy, out):
+    nx, ny, nz = vol.shape
+    L = _lib.lib()
+    with _on_device(vol.device):
+        rc = L.r2_project_volume(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
+                                 float(dVoxel[1]), float(dVoxel[2]), float(accuracy), vol.data_ptr(), out.data_ptr(),
+                                 _stream(vol.device))
+    _lib.check(rc, "r2_project_volume")
+    return out
+
+
+def _check_views(views):
+    views = list(views)
+    if not views:
+        raise ValueError("no views to back-project")
+    H, W = views[0].image_height, views[0].image_width
+    if any((v.image_height, v.image_width) != (H, W) for v in views):
+        raise ValueError("all views must share one detector size")
+    if any(v.mode != views[0].mode for v in views):
+        raise ValueError("all views must share one beam mode")
+    return views, H, W
+
+
+def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVoxel=None):
+    """The exact transpose of ``projector.project_views``: vol [nx,ny,nz] (GPU) = A^T projs for projections [V,H,W] (GPU,
+    float32) of ``views`` (scene units).  The volume's shape comes from ``out`` (a contiguous float32 GPU tensor, overwritten)
+    or ``nVoxel``.  No host synchronisation."""
+    _require_gpu(projs, "projs")
+    if projs.dim() != 3:
+        raise ValueError("projs must be [V,H,W], got shape %s" % (tuple(projs.shape),))
+    if not accuracy > 0:
+        raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
+    views, H, W = _check_views(views)
+    if tuple(projs.shape) != (len(views), H, W):
+        raise ValueError("projs shape %s differs from the views' [%d,%d,%d]" % (tuple(projs.shape), len(views), H, W))
+    if len(sVoxel) != 3 or len(center) != 3 or not all(s > 0 for s in sVoxel):
+        raise ValueError("sVoxel must be three positive sizes and center three coordinates")
+    if out is None:
+        if nVoxel is None or len(nVoxel) != 3 or not all(int(n) > 0 for n in nVoxel):
+            raise ValueError("give the volume's shape: nVoxel (three positive sizes) or out")
+        out = torch.empty(tuple(int(n) for n in nVoxel), dtype=_F32, device=projs.device)
+    elif (out.dtype != _F32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 3 or out.device != projs.device
+          or (nVoxel is not None and tuple(out.shape) != tuple(int(n) for n in nVoxel))):
+        raise ValueError("out must be a contiguous float32 tensor [nx,ny,nz] on %s" % (projs.device,))
+    p32 = projs if projs.dtype == _F32 and projs.is_contiguous() else projs.to(_F32).contiguous()
+    nv = tuple(out.shape)
+    rays = torch.from_numpy(P.ray_params(views, sVoxel, center, nv)).pin_memory().to(p32.device, non_blocking=True)
+    d = [float(s) / n for s, n in zip(sVoxel, nv)]
+    return _backproject_rays(p32, rays, views[0].mode == 1, nv, d, accuracy, out)
+
+
+# ---- the operator pair in config units --------------------------------------------------------------------------------------
+
+class Operator:
+    """A = ``project(., angles, cfg)`` and its transpose on one device, with the rays computed once: ``A(x, v0, v1)`` projects
+    views v0..v1-1, ``At(p, v0, v1)`` back-projects them."""
+
+    def __init__(self, angles, cfg, accuracy=None, device="cuda"):
+        self.cfg = cfg
+        acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
+        if not acc > 0:
+            raise ValueError("accuracy must be > 0, got %r" % (acc,))
+        self.accuracy = float(acc)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.R2HipError("the reconstructions run on the MI355X kernels: device must be a GPU, got %s" % device)
+        self.nVoxel = tuple(int(n) for n in cfg["nVoxel"])
+        self.H, self.W = (int(n) for n in cfg["nDetector"])
+        scale = 2.0 / max(cfg["sVoxel"])   # make_view works in the normalised scene (dataset_readers.py:62-76)
+        self.inv_scale = 1.0 / scale
+        ang = np.asarray(angles, dtype=np.float64).reshape(-1)
+        if ang.size == 0:
+            raise ValueError("no angles")
+        self.V = int(ang.size)
+        views = [S.make_view(float(a), (self.H, self.W), cfg) for a in ang]
+        self.cone = views[0].mode == 1
+        sV = [s * scale for s in cfg["sVoxel"]]
+        self.dVoxel = [s / n for s, n in zip(sV, self.nVoxel)]
+        rays = P.ray_params(views, sV, [o * scale for o in cfg["offOrigin"]], self.nVoxel)
+        self.rays = torch.from_numpy(rays).pin_memory().to(self.device, non_blocking=True)
+
+    def A(self, x, v0=0, v1=None, out=None):
+        v1 = self.V if v1 is None else v1
+        if tuple(x.shape) != self.nVoxel:
+            raise ValueError("volume shape %s differs from the config's nVoxel %s" % (tuple(x.shape), self.nVoxel))
+        if out is None:
+            out = torch.empty((v1 - v0, self.H, self.W), dtype=_F32, device=self.device)
+        _project_rays(x, self.rays[v0:v1], self.cone, self.H, self.W, self.dVoxel, self.accuracy, out)
+        return out.mul_(self.inv_scale)
+
+    def At(self, p, v0=0, v1=None, out=None):
+        v1 = self.V if v1 is None else v1
+        if tuple(p.shape) != (v1 - v0, self.H, self.W):
+            raise ValueError("projections %s are not views %d..%d of [%d,%d]" % (tuple(p.shape), v0, v1 - 1, self.H, self.W))
+        if out is None:
+            out = torch.empty(self.nVoxel, dtype=_F32, device=self.device)
+        _backproject_rays(p, self.rays[v0:v1], self.cone, self.nVoxel, self.dVoxel, self.accuracy, out)
+        return out.mul_(self.inv_scale)
+
+
+def _projections(projs, op):
+    p = projs if isinstance(projs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(projs))
+    if p.dim() != 3 or tuple(p.shape) != (op.V, op.H, op.W):
+        raise ValueError("projections must be [%d,%d,%d] (one per angle, the config's nDetector), got %s"
+                         % (op.V, op.H, op.W, tuple(p.shape)))
+    if p.is_floating_point() is False:
+        raise ValueError("projections must be floating point, got %s" % (p.dtype,))
+    if not p.is_cuda:
+        p = p.to(_F32).contiguous().pin_memory()
+    return p.to(device=op.device, dtype=_F32, non_blocking=True).contiguous()
+
+
+def backproject(projs, angles, scanner_cfg, accuracy=None, device="cuda"):
+    """The transpose of ``projector.project``: vol [nx,ny,nz] (GPU tensor) = A^T projs for projections [V,H,W] at ``angles``
+    with the raw scanner config, including ``project``'s 1 / scale."""
+    op = Operator(angles, scanner_cfg, accuracy, device)
+    return op.At(_projections(projs, op))
+
+
+def _sq(t):
+    return t.pow(2).sum(dtype=_F64)
+
+
+# ---- CGLS -----------------------------------------------------------------------------------------------------------------
+
+def cgls(projs, angles, cfg, niter=60, computel2=False, accuracy=None, device="cuda"):
+    """CGLS from x0 = 0: ``niter`` iterations on |A x - b|_2.  -> x [nx,ny,nz] (GPU), or (x, l2) with computel2, l2 the
+    residual norms |b - A x_k| after each iteration (a host list: one synchronisation per iteration)."""
+    op = Operator(angles, cfg, accuracy, device)
+    b = _projections(projs, op)
+    if int(niter) < 0:
+        raise ValueError("niter must be >= 0")
+    x = torch.zeros(op.nVoxel, dtype=_F32, device=op.device)
+    r = b.clone()
+    p = op.At(r)
+    s = torch.empty_like(p)
+    q = torch.empty_like(b)
+    gamma = _sq(p)
+    zero = torch.zeros((), dtype=_F64, device=op.device)
+    l2 = []
+    for _ in range(int(niter)):
+        op.A(p, out=q)
+        qq = _sq(q)
+        alpha = torch.where(qq > 0, gamma / torch.where(qq > 0, qq, 1.0), zero).to(_F32)
+        x.add_(p * alpha)
+        r.sub_(q * alpha)
+        if computel2:
+            l2.append(float(torch.linalg.vector_norm(r, dtype=_F64)))
+        op.At(r, out=s)
+        gamma_new = _sq(s)
+        beta = torch.where(gamma > 0, gamma_new / torch.where(gamma > 0, gamma, 1.0), zero).to(_F32)
+        p = s + beta * p
+        gamma = gamma_new
+    return (x, l2) if computel2 else x
+
+
+# ---- SART / OS-SART ---------------------------------------------------------------------------------------------------------
+
+class _Sart:
+    """The weights of OS-SART for one operator and block size, computed once: W = 1/(A 1) per ray, V_B^-1 per block."""
+
+    def __init__(self, op, blocksize):
+        if int(blocksize) < 1:
+            raise ValueError("blocksize must be >= 1, got %r" % (blocksize,))
+        self.op = op
+        bs = int(blocksize)
+        self.blocks = [(v0, min(v0 + bs, op.V)) for v0 in range(0, op.V, bs)]
+        ones = torch.ones(op.nVoxel, dtype=_F32, device=op.device)
+        a1 = op.A(ones)
+        self.W = torch.where(a1 > 0, 1.0 / torch.where(a1 > 0, a1, 1.0), torch.zeros_like(a1))
+        one_p = torch.ones((op.V, op.H, op.W), dtype=_F32, device=op.device)
+        self.Vinv = []
+        for v0, v1 in self.blocks:
+            v = op.At(one_p[v0:v1], v0, v1)
+            self.Vinv.append(torch.where(v > 0, 1.0 / torch.where(v > 0, v, 1.0), torch.zeros_like(v)))
+
+    def sweep(self, x, b, lmbda, nonneg=True):
+        """One pass over all blocks, in place."""
+        op = self.op
+        for (v0, v1), vinv in zip(self.blocks, self.Vinv):
+            res = op.A(x, v0, v1)
+            res = (b[v0:v1] - res).mul_(self.W[v0:v1])
+            upd = op.At(res, v0, v1)
+            x.addcmul_(upd, vinv, value=float(lmbda))
+            if nonneg:
+                x.clamp_(min=0.0)
+        return x
+
+
+def ossart(projs, angles, cfg, niter=20, blocksize=10, lmbda=1.0, lmbda_red=0.999, init=None, nonneg=True, computel2=False,
+           accuracy=None, device="cuda"):
+    """OS-SART: ``niter`` sweeps over blocks of ``blocksize`` consecutive views (input order).  -> x (GPU), or (x, l2) with
+    computel2 (|A x - b|_2 after each sweep; one synchronisation per sweep)."""
+    op = Operator(angles, cfg, accuracy, device)
+    b = _projections(projs, op)
+    st = _Sart(op, blocksize)
+    x = _init(init, op)
+    lam = float(lmbda)
+    l2 = []
+    for _ in range(int(niter)):
+        st.sweep(x, b, lam, nonneg)
+        lam *= lmbda_red
+        if computel2:
+            l2.append(float(torch.linalg.vector_norm(op.A(x) - b, dtype=_F64)))
+    return (x, l2) if computel2 else x
+
+
+def sart(projs, angles, cfg, niter=20, lmbda=1.0, lmbda_red=0.999, init=None, nonneg=True, computel2=False, accuracy=None,
+         device="cuda"):
+    """SART: OS-SART with one view per block."""
+    return ossart(projs, angles, cfg, niter, 1, lmbda, lmbda_red, init, nonneg, computel2, accuracy, device)
+
+
+def _init(init, op):
+    if init is None:
+        return torch.zeros(op.nVoxel, dtype=_F32, device=op.device)
+    x = torch.as_tensor(init).to(device=op.device, dtype=_F32).clone().contiguous()
+    if tuple(x.shape) != op.nVoxel:
+        raise ValueError("init must be [%d,%d,%d]" % op.nVoxel)
+    return x
+
+
+# ---- TV descent and ASD-POCS ------------------------------------------------------------------------------------------------
+
+def tv_descent(vol, step, n_iter, scratch=None):
+    """``n_iter`` steps x <- x - step g / |g|_2, g = grad TV_eps(x) (include/r2hip.h, r2_tv_descent), in place on ``vol``
+    [nx,ny,nz] (contiguous float32, GPU).  ``step``: a float or a 0-d device tensor (read on the device).  -> vol."""
+    _require_gpu(vol, "vol")
+    if vol.dim() != 3 or vol.dtype != _F32 or not vol.is_contiguous():
+        raise ValueError("vol must be a contiguous float32 [nx,ny,nz] tensor")
+    if int(n_iter) < 0:
+        raise ValueError("n_iter must be >= 0")
+    if isinstance(step, torch.Tensor):
+        st = step.to(device=vol.device, dtype=_F32).reshape(())
+    else:
+        st = torch.full((), float(step), dtype=_F32, device=vol.device)
+    nx, ny, nz = vol.shape
+    L = _lib.lib()
+    nbytes = int(L.r2_tv_descent_scratch_bytes(nx, ny, nz))
+    if scratch is None or scratch.numel() * scratch.element_size() < nbytes or scratch.device != vol.device:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
+    with _on_device(vol.device):
+        rc = L.r2_tv_descent(nx, ny, nz, vol.data_ptr(), st.data_ptr(), int(n_iter), scratch.data_ptr(),
+                             scratch.numel() * scratch.element_size(), _stream(vol.device))
+    _lib.check(rc, "r2_tv_descent")
+    return vol
+
+
+def maxl2err_default(projs, angles, cfg, device="cuda"):
+    """The reference's ASD-POCS tolerance: 0.15 |A fdk(b) - b|_2 (a 0-d device tensor)."""
+    op = Operator(angles, cfg, None, device)
+    b = _projections(projs, op)
+    return 0.15 * torch.linalg.vector_norm(op.A(F.fdk(b, angles, cfg, device=device)) - b, dtype=_F64)
+
+
+def os_asd_pocs(projs, angles, cfg, niter=10, blocksize=10, tviter=20, maxl2err=None, alpha=0.002, lmbda=1.0,
+                lmbda_red=0.9999, alpha_red=0.95, rmax=0.94, init=None, verbose=False, accuracy=None, device="cuda",
+                return_trace=False):
+    """OS-ASD-POCS (Sidky & Pan 2008, with OS-SART as the data step; ASD-POCS is blocksize 1).  Each iteration:
+
+    1. x_prev = x; one (OS-)SART sweep with the current lambda, clipped to x >= 0; x_sart = x.
+    2. dd = |A x_sart - b|_2, dp = |x_sart - x_prev|_2; on the first iteration dtvg = alpha dp.
+    3. ``tviter`` TV descent steps of length dtvg (``tv_descent``).
+    4. dg = |x - x_sart|_2; if dg > rmax dp and dd > maxl2err: dtvg <- dtvg alpha_red.
+    5. lambda <- lambda lambda_red.
+    6. c = <x - x_sart, x_sart - x_prev> / max(dg dp, 1e-6); stop when c < -0.99 and dd <= maxl2err, or after ``niter``.
+
+    ``maxl2err`` None: 0.15 |A fdk(b) - b|_2.  The stop test is kept on the device: once it holds, later iterations leave x
+    as it is, so no iteration waits for the host unless ``verbose``.  -> x (GPU); with return_trace also a dict of per-
+    iteration device tensors (dd, dp, dg, dtvg, reduced, c, active, sart_min = min x_sart)."""
+    op = Operator(angles, cfg, accuracy, device)
+    b = _projections(projs, op)
+    st = _Sart(op, blocksize)
+    if maxl2err is None:
+        maxl2err = maxl2err_default(b, angles, cfg, device)
+    eps = (maxl2err.to(device=op.device, dtype=_F64) if isinstance(maxl2err, torch.Tensor)
+           else torch.full((), float(maxl2err), dtype=_F64, device=op.device))
+    x = _init(init, op)
+    lam = float(lmbda)
+    active = torch.ones((), dtype=torch.bool, device=op.device)
+    dtvg = torch.zeros((), dtype=_F32, device=op.device)
+    scratch = torch.empty(int(_lib.lib().r2_tv_descent_scratch_bytes(*op.nVoxel)), dtype=torch.uint8, device=op.device)
+    trace = {k: [] for k in ("dd", "dp", "dg", "dtvg", "reduced", "c", "active", "sart_min")}
+    for it in range(int(niter)):
+        x_prev = x.clone()
+        st.sweep(x, b, lam, True)
+        x_sart = x.clone()
+        dd = torch.linalg.vector_norm(op.A(x_sart) - b, dtype=_F64)
+        dp = torch.linalg.vector_norm(x_sart - x_prev, dtype=_F64)
+        if it == 0:
+            dtvg = (alpha * dp).to(_F32)
+        tv_descent(x, dtvg, tviter, scratch)
+        dg = torch.linalg.vector_norm(x - x_sart, dtype=_F64)
+        reduced = (dg > rmax * dp) & (dd > eps)
+        dtvg = torch.where(reduced, dtvg * alpha_red, dtvg)
+        lam *= lmbda_red
+        c = ((x - x_sart).double() * (x_sart - x_prev).double()).sum() / torch.clamp(dg * dp, min=1e-6)
+        # a stopped run keeps the x it stopped with
+        x.copy_(torch.where(active, x, x_prev))
+        for k, v in (("dd", dd), ("dp", dp), ("dg", dg), ("dtvg", dtvg), ("reduced", reduced), ("c", c), ("active", active),
+                     ("sart_min", x_sart.min())):
+            trace[k].append(v)
+        active = active & ~((c < -0.99) & (dd <= eps))
+        if verbose:
+            print("asd_pocs it %d: dd %.4g dp %.4g dg %.4g dtvg %.4g c %.4f" % (it, float(dd), float(dp), float(dg),
+                                                                               float(dtvg), float(c)))
+    return (x, trace) if return_trace else x
+
+
+def asd_pocs(projs, angles, cfg, niter=10, tviter=20, maxl2err=None, alpha=0.002, lmbda=1.0, lmbda_red=0.9999,
+             alpha_red=0.95, rmax=0.94, init=None, verbose=False, accuracy=None, device="cuda", return_trace=False):
+    """ASD-POCS: ``os_asd_pocs`` with one view per block (SART as the data step)."""
+    return os_asd_pocs(projs, angles, cfg, niter, 1, tviter, maxl2err, alpha, lmbda, lmbda_red, alpha_red, rmax, init,
+                       verbose, accuracy, device, return_trace)
+
+
+# ---- the reference's entry points -------------------------------------------------------------------------------------------
+
+def reconstruct(projs, angles, cfg, method, device="cuda"):
+    """One of METHODS with the parameters ct_utils.py:60-175 passes -> x [nx,ny,nz] (GPU)."""
+    if method == "fdk":
+        return F.fdk(projs, angles, cfg, device=device)
+    if method == "sart":
+        return sart(projs, angles, cfg, 20, 1.0, 0.999, device=device)
+    if method == "ossart":
+        return ossart(projs, angles, cfg, 20, 10, 1.0, 0.999, device=device)
+    if method == "asd_pocs":
+        return asd_pocs(projs, angles, cfg, 10, device=device)
+    if method == "os_asd_pocs":
+        return os_asd_pocs(projs, angles, cfg, 10, 10, device=device)
+    if method == "cgls":
+        return cgls(projs, angles, cfg, 60, device=device)
+    raise NotImplementedError("Unsupported reconstruction method!")
+
+
+def recon_volume(projs, angles, scanner_cfg, recon_method="fdk"):
+    """ct_utils.py:17-27: ``"fdk"`` or ``"cgls"`` (60 iterations) -> numpy volume [nx,ny,nz]."""
+    if recon_method not in ("fdk", "cgls"):
+        raise ValueError("Unsupported reconstruction method")
+    return reconstruct(projs, angles, scanner_cfg, recon_method).cpu().numpy()
+
+
+def run_ct_recon_algs(projs, angles, cfg, ct_gt, save_path, method):
+    """ct_utils.py:60-215: reconstruct with ``method``, evaluate against ``ct_gt`` [nx,ny,nz] with ``metrics.metric_vol``, and
+    write ``{save_path}/{method}/``: ct_gt.npy, ct_pred.npy, eval_3d.yml and slice_{method}/{i:05d}_gt.png / _pred.png
+    (z slices).  -> (report, ct_pred, ct_gt), numpy volumes."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    import yaml
+    from .metrics import metric_vol
+    print("Run {}...".format(method))
+    if method not in METHODS:
+        raise NotImplementedError("Unsupported reconstruction method!")
+    save_path = osp.join(save_path, method)
+    slice_save_path = osp.join(save_path, "slice_{}".format(method))
+    os.makedirs(slice_save_path, exist_ok=True)
+    start = time.time()
+    ct_pred = reconstruct(projs, angles, cfg, method).cpu().numpy()
+    duration = time.time() - start
+    ct_gt = np.asarray(ct_gt, dtype=np.float32)
+    psnr_3d, _ = metric_vol(ct_gt, ct_pred, "psnr")
+    ssim_3d, ssim_3d_axis = metric_vol(ct_gt, ct_pred, "ssim")
+    np.save(osp.join(save_path, "ct_gt.npy"), ct_gt)
+    np.save(osp.join(save_path, "ct_pred.npy"), ct_pred)
+    for i in range(ct_gt.shape[2]):
+        plt.imsave(osp.join(slice_save_path, "{0:05d}_gt.png".format(i)), ct_gt[:, :, i], cmap="gray", vmin=0.0, vmax=1.0)
+        plt.imsave(osp.join(slice_save_path, "{0:05d}_pred.png".format(i)), ct_pred[:, :, i], cmap="gray", vmin=0.0,
+                   vmax=1.0)
+    report = {"method": method, "psnr_3d": float(psnr_3d), "ssim_3d": float(ssim_3d), "ssim_3d_x": float(ssim_3d_axis[0]),
+              "ssim_3d_y": float(ssim_3d_axis[1]), "ssim_3d_z": float(ssim_3d_axis[2]), "duration (sec)": duration,
+              "duration (min)": duration / 60}
+    with open(osp.join(save_path, "eval_3d.yml"), "w") as f:
+        yaml.dump(report, f, default_flow_style=False, sort_keys=False)
+    print("[{}] psnr_3d: {}, ssim_3d: {}".format(method, psnr_3d, ssim_3d))
+    return report, ct_pred, ct_gt
+
+
+def _read_case(case_dir):
+    """The case written by ``datagen.write_case``: raw config, projections and angles per split, the ground truth, and the
+    reference reader's scene_scale (dataset_readers.py:62-76)."""
+    with open(osp.join(case_dir, "meta_data.json"), "r", encoding="utf-8") as f:
+        meta = json.load(f)
+    cfg = meta["scanner"]
+    out = {"cfg": cfg, "vol": np.load(osp.join(case_dir, meta["vol"])), "scale": 2.0 / max(cfg["sVoxel"])}
+    for split in ("train", "test"):
+        e = meta["proj_" + split]
+        out[split] = (np.stack([np.load(osp.join(case_dir, x["file_path"])) for x in e]).astype(np.float32),
+                      np.array([x["angle"] for x in e], dtype=np.float64))
+    return out
+
+
+def run_traditional_methods(source_path, model_path, methods=("fdk", "sart", "asd_pocs")):
+    """scripts/run_traditional_methods.py for a case in datagen's layout: every method's reconstruction and report, and its
+    test-view projections ``{model_path}/{method}/projs/{i:05d}_render.npy/.png`` next to ``_gt.npy/.png``.  Like the
+    reference (which reads them through Scene), the saved projections are in the normalised scene's units (times
+    scene_scale).  -> the dict written to ``{model_path}/eval_3d.yml``."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+    import yaml
+    case = _read_case(source_path)
+    cfg, scale = case["cfg"], case["scale"]
+    projs, angles = case["train"]
+    test_projs, test_angles = case["test"]
+    print("Run traditional algorithms on {}".format(osp.basename(osp.normpath(source_path))))
+    out = {}
+    for method in methods:
+        out[method], ct_pred, _ = run_ct_recon_algs(projs, angles, cfg, case["vol"], model_path, method)
+        render = (P.project(ct_pred, test_angles, cfg) * scale).cpu().numpy()
+        gt = test_projs * np.float32(scale)
+        proj_save_path = osp.join(model_path, method, "projs")
+        os.makedirs(proj_save_path, exist_ok=True)
+        for i in range(render.shape[0]):
+            np.save(osp.join(proj_save_path, "{0:05d}_render.npy".format(i)), render[i])
+            np.save(osp.join(proj_save_path, "{0:05d}_gt.npy".format(i)), gt[i])
+            plt.imsave(osp.join(proj_save_path, "{0:05d}_render.png".format(i)), render[i], cmap="gray")
+            plt.imsave(osp.join(proj_save_path, "{0:05d}_gt.png".format(i)), gt[i], cmap="gray")
+    with open(osp.join(model_path, "eval_3d.yml"), "w") as f:
+        yaml.dump(out, f, default_flow_style=False, sort_keys=False)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Classical CT reconstructions of a case (run_traditional_methods.py)")
+    ap.add_argument("-s", "--source_path", required=True, help="case directory as datagen writes it")
+    ap.add_argument("-m", "--model_path", required=True, help="output directory")
+    ap.add_argument("--methods", nargs="+", default=["fdk", "sart", "asd_pocs"], choices=METHODS)
+    a = ap.parse_args(argv)
+    run_traditional_methods(a.source_path, a.model_path, a.methods)
+
+
+if __name__ == "__main__":
+    main()
