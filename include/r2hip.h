@@ -222,6 +222,33 @@ R2_API int r2_densify_emit(int P, const float *const *params, const float *const
                            float *const *exp_avg_sq_out, float *max_radii2D_out, float *grad_accum_out, float *denom_out,
                            void *stream);
 
+/* ---- model step of a training iteration (r2_gaussian/gaussian/gaussian_model.py:38-64, 112-126, 188-254; train.py:174-176) ----
+ * r2_gaussian_activate replaces the activation properties get_density / get_scaling / get_rotation (gaussian_model.py:112-126):
+ *   density_act = softplus(density) with torch's beta 1, threshold 20 (x > 20: x); scaling_act = sigmoid(x) * (hi - lo) + lo with
+ *   a scale bound, exp(x) without one; rotation_act = q / max(|q|, 1e-12).  xyz's activation is the identity (no output).
+ * r2_gaussian_adam_step replaces torch.optim.Adam.step() over the model's four parameter groups (gaussian_model.py:188-215:
+ *   betas (0.9, 0.999) and eps 1e-15, FIXED; no weight decay, no amsgrad) together with the backward of the activations, and
+ *   writes the NEXT iteration's activated parameters in the same pass.  grads[k] is dL/d(activated parameter k) -- what autograd
+ *   leaves in the .grad of the activated leaves -- and is chained through the activation's derivative as torch's backward
+ *   formulas compute it (softplus_backward's threshold, the sigmoid derivative (1 - y) y, exp, the normalize Jacobian
+ *   (g - q^(q^.g)) / |q|); then, in torch's non-fused order:  m = m + (1 - b1)(g - m);  v = v b2 + (1 - b2) g g;
+ *   denom = sqrt(v) / sqrt(bias_correction2[k]) + eps;  p = p - (lr[k] / bias_correction1[k]) m / denom.  The host computes
+ *   lr and both bias corrections in double from the group's step count (1 - beta^step); the call reads nothing back from the
+ *   device and does not synchronise.  grads[k] == NULL: group k is left untouched (no parameter, moment or step change),
+ *   as torch skips a parameter without .grad; its activated output is still written.
+ * params / grads / exp_avg / exp_avg_sq: 4 device pointers each in the order xyz [P,3], density [P,1], scaling [P,3],
+ *   rotation [P,4]; parameters and moments are updated in place.  Validation (R2_ERR_INVALID): P < 0; a NULL pointer array
+ *   or activation output; a NULL parameter; NULL moments of a group with a gradient; lr < 0 or a bias correction <= 0 in such
+ *   a group; a scale bound other than scale_lo < scale_hi (bounded sigmoid) or scale_lo == scale_hi == 0 (exp, no bound);
+ *   rotation arrays not 16-byte aligned.  P == 0 enqueues nothing. */
+R2_API int r2_gaussian_activate(int P, const float *density, const float *scaling, const float *rotation, double scale_lo,
+                                double scale_hi, float *density_act /* [P,1] */, float *scaling_act /* [P,3] */,
+                                float *rotation_act /* [P,4] */, void *stream);
+R2_API int r2_gaussian_adam_step(int P, float *const *params, const float *const *grads, float *const *exp_avg,
+                                 float *const *exp_avg_sq, const double *lr /* [4] */, const double *bias_correction1 /* [4] */,
+                                 const double *bias_correction2 /* [4] */, double scale_lo, double scale_hi,
+                                 float *density_act, float *scaling_act, float *rotation_act, void *stream);
+
 /* ---- voxelizer ------------------------------------------------------------------------------- */
 R2_API int r2_voxel_forward(
     r2_alloc_fn geometryBuffer, void *geometry_user,

@@ -71,6 +71,8 @@ _SIGNATURES = {
     "r2_backproject_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
     "r2_tv_descent_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
+    "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
+    "r2_gaussian_adam_step": (C.c_int, [_i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),
     "r2_profile_stage_count": (C.c_int, []),
     "r2_profile_stage_name": (C.c_char_p, [_i]),

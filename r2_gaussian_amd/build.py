@@ -43,6 +43,7 @@ SOURCES = {
     "loss_ops.hip": FAST,
     "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,
+    "gaussian_step.hip": EXACT,
     "fdk.hip": FAST,
     "projector.hip": EXACT,
     "backprojector.hip": EXACT,

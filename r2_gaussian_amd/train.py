@@ -1,0 +1,308 @@
+"""R2-Gaussian training on the MI355X kernels: train.py:34-330 of the reference for a case in datagen's layout, on
+``gaussians.GaussianModel`` (one fused HIP launch for the activations' backward, Adam and the next activations) and the
+package's rasterizer, voxelizer, fused losses and fused density control.
+
+    python -m r2_gaussian_amd.train -s <case> -m <output> [--iterations N] [--test_iterations ...] [...]
+
+Flag names and defaults are the reference's (ModelParams, OptimizationParams, PipelineParams and train.py's own); an unknown
+flag is an error.  ``training()`` is the loop itself: it takes views, projections, the ground truth, the geometry and the
+initial points, so it runs as well on an in-memory case.  Outputs, in the reference's layout under the model path:
+``point_cloud/iteration_N/{point_cloud.pickle, vol_gt.npy, vol_pred.npy}``, ``eval/iter_NNNNNN/{eval3d.yml,
+eval2d_render_train.yml, eval2d_render_test.yml}``, ``ckpt/chkpnt{N}.pth``.
+"""
+import argparse
+import os
+import os.path as osp
+import random
+import sys
+import time
+import uuid
+
+import numpy as np
+import torch
+
+from . import losses as FL
+from . import metrics as M
+from . import model_io
+from . import scene as S
+from .gaussians import GaussianModel
+from .rasterization import GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerBatch
+from .voxelization import GaussianVoxelizationSettings, GaussianVoxelizer
+
+
+class OptimizationParams:
+    """arguments/__init__.py:44-72."""
+    iterations = 30_000
+    position_lr_init, position_lr_final, position_lr_max_steps = 0.0002, 0.00002, 30_000
+    density_lr_init, density_lr_final, density_lr_max_steps = 0.01, 0.001, 30_000
+    scaling_lr_init, scaling_lr_final, scaling_lr_max_steps = 0.005, 0.0005, 30_000
+    rotation_lr_init, rotation_lr_final, rotation_lr_max_steps = 0.001, 0.0001, 30_000
+    lambda_dssim, lambda_tv, tv_vol_size = 0.25, 0.05, 32
+    density_min_threshold = 0.00001
+    densification_interval, densify_from_iter, densify_until_iter = 100, 500, 15000
+    densify_grad_threshold, densify_scale_threshold = 5.0e-5, 0.1
+    max_screen_size, max_scale = None, None
+    max_num_gaussians = 500_000
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            if not hasattr(OptimizationParams, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+
+def _bbox(geometry):
+    off, s = torch.tensor(geometry["offOrigin"], dtype=torch.float32), torch.tensor(geometry["sVoxel"], dtype=torch.float32)
+    return torch.stack([off - s / 2, off + s / 2], 0)
+
+
+def _query(xyz, dens, scal, rot, center, nVoxel, sVoxel):
+    """query() of render_query.py:120-160."""
+    vs = GaussianVoxelizationSettings(scale_modifier=1.0, nVoxel_x=int(nVoxel[0]), nVoxel_y=int(nVoxel[1]), nVoxel_z=int(nVoxel[2]),
+                                      sVoxel_x=float(sVoxel[0]), sVoxel_y=float(sVoxel[1]), sVoxel_z=float(sVoxel[2]),
+                                      center_x=float(center[0]), center_y=float(center[1]), center_z=float(center[2]),
+                                      prefiltered=False, debug=False)
+    vol, _radii = GaussianVoxelizer(voxel_settings=vs)(means3D=xyz, opacities=dens, scales=scal, rotations=rot, cov3D_precomp=None)
+    return vol
+
+
+def _settings(v, dev, views=None):
+    """Rasterizer settings of one view, or of a list of views for GaussianRasterizerBatch ([V,4,4] matrices)."""
+    vm = v.world_view_transform if views is None else torch.stack([u.world_view_transform for u in views])
+    pm = v.full_proj_transform if views is None else torch.stack([u.full_proj_transform for u in views])
+    return GaussianRasterizationSettings(image_height=v.image_height, image_width=v.image_width, tanfovx=v.tanfovx,
+                                         tanfovy=v.tanfovy, scale_modifier=1.0, viewmatrix=vm.to(dev), projmatrix=pm.to(dev),
+                                         campos=v.camera_center.to(dev), prefiltered=False, mode=v.mode, debug=False)
+
+
+@torch.no_grad()
+def render_views(gaussians, views, dev, batch=8):
+    """[V, H, W] projections of the views through GaussianRasterizerBatch, `batch` views per call."""
+    xyz, d, s, r = (t.detach() for t in gaussians.activated())
+    out = []
+    for i in range(0, len(views), batch):
+        vb = views[i:i + batch]
+        m2d = torch.zeros((len(vb),) + tuple(xyz.shape), dtype=torch.float32, device=dev)
+        img, _radii = GaussianRasterizerBatch(_settings(vb[0], dev, vb))(xyz, m2d, d, scales=s, rotations=r)
+        out.append(img)
+    return torch.cat(out, 0)
+
+
+@torch.no_grad()
+def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals):
+    """training_report of train.py:262-330 without tensorboard: eval2d_<name>.yml per view set, eval3d.yml.  -> eval3d dict."""
+    import yaml
+    dev = gaussians.device
+    path = osp.join(model_path, "eval", "iter_%06d" % iteration)
+    os.makedirs(path, exist_ok=True)
+    for name, views, gts in evals:
+        if not views:
+            continue
+        images = render_views(gaussians, views, dev).permute(1, 2, 0)
+        psnr_2d, psnr_projs = M.metric_proj(gts, images, "psnr")
+        ssim_2d, ssim_projs = M.metric_proj(gts, images, "ssim")
+        with open(osp.join(path, "eval2d_%s.yml" % name), "w") as f:
+            yaml.dump({"psnr_2d": float(psnr_2d), "ssim_2d": float(ssim_2d), "psnr_2d_projs": [float(x) for x in psnr_projs],
+                       "ssim_2d_projs": [float(x) for x in ssim_projs]}, f, default_flow_style=False, sort_keys=False)
+    xyz, d, s, r = (t.detach() for t in gaussians.activated())
+    vol = _query(xyz, d, s, r, geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"])
+    psnr_3d, ssim_3d, axes = M.metric_vol_both(vol_gt, vol)
+    out = {"psnr_3d": float(psnr_3d), "ssim_3d": float(ssim_3d), "ssim_3d_x": float(axes[0]), "ssim_3d_y": float(axes[1]),
+           "ssim_3d_z": float(axes[2])}
+    with open(osp.join(path, "eval3d.yml"), "w") as f:
+        yaml.dump(out, f, default_flow_style=False, sort_keys=False)
+    return out
+
+
+def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry, init_points, opt, model_path,
+             scale_bound=None, test_iterations=(), save_iterations=(), checkpoint_iterations=(), start_checkpoint=None,
+             seed=0, log=print, device="cuda"):
+    """The training loop of train.py:34-216.  views: scene.View lists; projections: [V, H, W] in scene units (times
+    scene_scale); vol_gt [nx, ny, nz]; geometry: the NORMALISED scanner config (nVoxel, sVoxel, offOrigin, dVoxel);
+    init_points [N, 4] = xyz | density; scale_bound: (lo, hi) in scene units or None.  Randomness (view order, TV patch centres,
+    split samples) comes from generators seeded with `seed`: random.Random for the view order, a CPU torch.Generator for the
+    rest, in the order tests/mini_trainer.py draws them.  -> dict(model, evals {iteration: eval3d}, it_per_s, P)."""
+    dev = torch.device(device)
+    gaussians = GaussianModel(scale_bound, device=dev)
+    gaussians.create_from_pcd(init_points[:, :3], init_points[:, 3:4], 1.0)
+    gaussians.training_setup(opt)
+    first_iter = 0
+    if start_checkpoint:
+        model_params, first_iter = torch.load(start_checkpoint, map_location=dev, weights_only=False)
+        gaussians.restore(model_params, opt)
+        log("Load checkpoint %s." % osp.basename(start_checkpoint))
+    bbox = _bbox(geometry)
+    volume_to_world = max(geometry["sVoxel"])
+    max_scale = opt.max_scale * volume_to_world if opt.max_scale else None
+    densify_scale_threshold = opt.densify_scale_threshold * volume_to_world if opt.densify_scale_threshold else None
+    gts = [torch.as_tensor(np.asarray(p), dtype=torch.float32).to(dev) for p in train_projs]
+    vol_gt = torch.as_tensor(np.asarray(vol_gt), dtype=torch.float32).to(dev)
+    evals = [("render_train", train_views, torch.stack(gts, -1)),
+             ("render_test", test_views,
+              torch.as_tensor(np.asarray(test_projs), dtype=torch.float32).to(dev).permute(1, 2, 0) if len(test_views) else None)]
+    use_tv = opt.lambda_tv > 0
+    tvN = torch.tensor([opt.tv_vol_size] * 3)
+    tvS = torch.tensor(geometry["dVoxel"], dtype=torch.float32) * tvN
+    settings = [_settings(v, dev) for v in train_views]
+    gen = torch.Generator().manual_seed(seed)
+    pyrng = random.Random(seed)
+    ckpt_path = osp.join(model_path, "ckpt")
+    os.makedirs(ckpt_path, exist_ok=True)
+    out = {"evals": {}}
+    if first_iter == 0 and 0 in test_iterations:
+        out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals)
+    stack = []
+    t_train, n_timed = 0.0, 0
+    for iteration in range(first_iter + 1, opt.iterations + 1):
+        t0 = time.perf_counter()
+        gaussians.update_learning_rate(iteration)
+        if not stack:
+            stack = list(range(len(train_views)))
+        vi = stack.pop(pyrng.randint(0, len(stack) - 1))
+        xyz, dens, scal, rot = gaussians.activated()
+        screen = torch.zeros_like(xyz, requires_grad=True)
+        img, radii = GaussianRasterizer(raster_settings=settings[vi])(means3D=xyz, means2D=screen, opacities=dens, scales=scal,
+                                                                      rotations=rot, cov3D_precomp=None)
+        loss, _parts = FL.image_loss(img, gts[vi], opt.lambda_dssim)
+        if use_tv:
+            c = (bbox[0] + tvS / 2) + (bbox[1] - tvS - bbox[0]) * torch.rand(3, generator=gen)
+            loss = loss + opt.lambda_tv * FL.tv_3d_loss(_query(xyz, dens, scal, rot, c, tvN, tvS))
+        loss.backward()
+        with torch.no_grad():
+            gaussians.add_densification_stats(radii, screen.grad)
+            if opt.densify_from_iter < iteration < opt.densify_until_iter and iteration % opt.densification_interval == 0:
+                gaussians.densify_and_prune(opt.densify_grad_threshold, opt.density_min_threshold, opt.max_screen_size,
+                                            max_scale, opt.max_num_gaussians, densify_scale_threshold, bbox,
+                                            normals=torch.randn((2, gaussians.P, 3), generator=gen))
+            if iteration < opt.iterations:
+                gaussians.step()
+            else:
+                for t in gaussians.activated():
+                    t.grad = None
+        torch.cuda.synchronize(dev)
+        t_train += time.perf_counter() - t0
+        n_timed += 1
+        if iteration in save_iterations or iteration == opt.iterations:
+            pc = osp.join(model_path, "point_cloud", "iteration_%d" % iteration)
+            gaussians.save_ply(osp.join(pc, "point_cloud.pickle"))
+            with torch.no_grad():
+                x, d, s, r = (t.detach() for t in gaussians.activated())
+                vol = _query(x, d, s, r, geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"])
+            model_io.save_volumes(pc, vol_gt, vol)
+        if iteration in checkpoint_iterations:
+            model_io.save_checkpoint(osp.join(ckpt_path, "chkpnt%d.pth" % iteration), gaussians.capture(), iteration)
+        if iteration in test_iterations:
+            out["evals"][iteration] = e = evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals)
+            log("[ITER %d] Evaluating: psnr3d %.3f, ssim3d %.3f, P %d" % (iteration, e["psnr_3d"], e["ssim_3d"], gaussians.P))
+    out["it_per_s"] = n_timed / t_train if t_train > 0 else float("nan")
+    out["model"] = gaussians
+    out["P"] = gaussians.P
+    log("Training complete: %d iterations, %.1f it/s, %d Gaussians" % (n_timed, out["it_per_s"], gaussians.P))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the case on disk
+def load_case(source_path, ply_path="", seed=0):
+    """Scene + initialize_gaussian for a case in datagen's layout: the views (scene.make_view on the raw config), the
+    projections times scene_scale, the normalised geometry (dataset_readers.py:62-76), and the initial points from
+    ``init_<case>.npy``, else `ply_path` (.npy), else fdk.init_pcd on the normalised scene."""
+    from . import fdk
+    from .recon import _read_case
+    case = _read_case(source_path)
+    cfg, scale = case["cfg"], case["scale"]
+    geo = dict(cfg)
+    geo.setdefault("dVoxel", list(np.array(cfg["sVoxel"]) / np.array(cfg["nVoxel"])))
+    geo.setdefault("dDetector", list(np.array(cfg["sDetector"]) / np.array(cfg["nDetector"])))
+    for k in ("dVoxel", "sVoxel", "sDetector", "dDetector", "offOrigin", "offDetector", "DSD", "DSO"):
+        if k in geo:
+            geo[k] = (np.array(geo[k]) * scale).tolist()
+    det = tuple(int(x) for x in cfg["nDetector"])
+    out = {"geometry": geo, "vol_gt": case["vol"], "scale": scale}
+    for split in ("train", "test"):
+        projs, angles = case[split]
+        out[split + "_views"] = [S.make_view(a, det, cfg) for a in angles]
+        out[split + "_projs"] = projs * np.float32(scale)
+    init = osp.join(source_path, "init_" + osp.basename(osp.normpath(source_path)) + ".npy")
+    if not ply_path and osp.exists(init):
+        out["init_points"] = np.load(init)
+    elif ply_path:
+        if not ply_path.endswith(".npy"):
+            raise ValueError("--ply_path: only .npy point clouds (xyz | density) are read")
+        out["init_points"] = np.load(ply_path)
+    else:
+        projs, angles = case["train"]
+        projs = projs * np.float32(scale)
+        # initialize_pcd.py's 50000 points, or every voxel above its threshold in a smaller reconstruction
+        n_points = min(50000, int((fdk.recon_volume(projs, angles, geo) > 0.05).sum()))
+        out["init_points"] = fdk.init_pcd(projs, angles, geo, n_points=n_points, rng=np.random.RandomState(seed))
+    return out
+
+
+def build_parser():
+    """The reference's flags (arguments/__init__.py, train.py:376-389)."""
+    ap = argparse.ArgumentParser(description="Training script parameters")
+    g = ap.add_argument_group("Loading Parameters")
+    g.add_argument("--source_path", "-s", default="", type=str)
+    g.add_argument("--model_path", "-m", default="", type=str)
+    g.add_argument("--data_device", default="cuda", type=str)
+    g.add_argument("--ply_path", default="", type=str)
+    g.add_argument("--scale_min", default=0.0005, type=float)
+    g.add_argument("--scale_max", default=0.5, type=float)
+    g.add_argument("--eval", default=True, action="store_true")
+    g = ap.add_argument_group("Optimization Parameters")
+    for k, v in vars(OptimizationParams).items():
+        if k.startswith("_") or callable(v):
+            continue
+        g.add_argument("--" + k, default=v, type=float if v is None else type(v))
+    g = ap.add_argument_group("Pipeline Parameters")
+    g.add_argument("--compute_cov3D_python", default=False, action="store_true")
+    g.add_argument("--debug", default=False, action="store_true")
+    ap.add_argument("--detect_anomaly", action="store_true", default=False)
+    ap.add_argument("--test_iterations", nargs="+", type=int, default=[5_000, 10_000, 20_000])
+    ap.add_argument("--save_iterations", nargs="+", type=int, default=[])
+    ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
+    ap.add_argument("--start_checkpoint", type=str, default=None)
+    ap.add_argument("--config", type=str, default=None)
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.config is not None:
+        import yaml
+        with open(args.config) as f:
+            cfg = yaml.safe_load(f)
+        for k, v in cfg.items():
+            if not hasattr(args, k):
+                ap.error("unknown key %r in %s" % (k, args.config))
+            setattr(args, k, v)
+    if args.compute_cov3D_python:
+        ap.error("--compute_cov3D_python is not supported: the kernels build the covariance from scales and rotations")
+    args.save_iterations.append(args.iterations)
+    args.test_iterations += [args.iterations, 1]
+    if not args.source_path:
+        ap.error("--source_path is required")
+    if not args.model_path:
+        args.model_path = osp.join("./output/", str(uuid.uuid4())[0:10])
+    os.makedirs(args.model_path, exist_ok=True)
+    print("Optimizing " + args.model_path)
+    torch.autograd.set_detect_anomaly(args.detect_anomaly)
+    case = load_case(args.source_path, args.ply_path)
+    volume_to_world = max(case["geometry"]["sVoxel"])
+    scale_bound = None
+    if args.scale_min > 0 and args.scale_max > 0:
+        scale_bound = np.array([args.scale_min, args.scale_max]) * volume_to_world
+    opt = OptimizationParams(**{k: getattr(args, k) for k in vars(OptimizationParams) if not k.startswith("_") and
+                                not callable(getattr(OptimizationParams, k))})
+    log = (lambda *a: None) if args.quiet else print
+    out = training(case["train_views"], case["train_projs"], case["test_views"], case["test_projs"], case["vol_gt"],
+                   case["geometry"], case["init_points"], opt, args.model_path, scale_bound, set(args.test_iterations),
+                   set(args.save_iterations), set(args.checkpoint_iterations), args.start_checkpoint, log=log)
+    print("Training complete. %.1f it/s" % out["it_per_s"])
+    return out
+
+
+if __name__ == "__main__":
+    main()
