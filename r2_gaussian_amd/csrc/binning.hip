@@ -537,35 +537,8 @@ __global__ void __launch_bounds__(1024) build_work_kernel(const uint2 *__restric
 
 // (Measured and left out, round 4: ONE workgroup for 32768 tiles as well, every thread owning 32 consecutive tiles, two passes over
 // the L2-resident ranges with eight loads in flight -- one launch instead of four, but 45 us slower: 43 k stores through one CU.)
-// many tiles (256^3 volume: 32768): the same in three parallel steps -- per-tile work item counts, their prefix sum
-// (own scan above), then every tile writes its base and its work items
-__global__ void __launch_bounds__(256) work_count_kernel(const uint2 *__restrict__ ranges, uint32_t T, uint32_t chunk,
-                                                         uint32_t *__restrict__ nw, uint32_t min_len)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= T) return;
-    const uint2 r = ranges[t];
-    const uint32_t ch = work_tile_chunk(chunk, r.y - r.x);
-    nw[t] = (r.y - r.x) < min_len ? 0u : (r.y - r.x + ch - 1) / ch;
-}
-__global__ void __launch_bounds__(256) work_fill_kernel(const uint2 *__restrict__ ranges, uint32_t chunk,
-                                                        const uint32_t *__restrict__ nw, const uint32_t *__restrict__ incl,
-                                                        uint32_t T, uint32_t *__restrict__ chunk_base,
-                                                        uint4 *__restrict__ work_tile)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= T) return;
-    const uint32_t n = nw[t], start = incl[t] - n;
-    chunk_base[t] = start;
-    const uint2 r = ranges[t];
-    const uint32_t ch = work_tile_chunk(chunk, r.y - r.x);
-    for (uint32_t j = 0; j < n; ++j)
-        work_tile[start + j] = make_uint4(t, r.x + j * ch, min(r.y, r.x + (j + 1) * ch), n);
-    if (t == T - 1) chunk_base[T] = incl[t];
-}
-
-// Round 4: the same in TWO launches -- the scan's two kernels compute the per-tile counts from the ranges themselves, and the second
-// one writes bases and work items on the way (count + scan-reduce, scan-apply + fill): two ~5 us launches less per 256^3 query.
+// many tiles (256^3 volume: 32768): the same in TWO launches -- a scan whose two kernels compute the per-tile work item counts from
+// the ranges themselves, and whose second one writes bases and work items on the way (count + scan-reduce, scan-apply + fill)
 __device__ __forceinline__ uint32_t work_items_of(const uint2 r, uint32_t chunk, uint32_t min_len)
 {
     const uint32_t len = r.y - r.x, ch = work_tile_chunk(chunk, len);
@@ -636,7 +609,7 @@ void launch_build_work_from_partials(const uint2 *ranges, uint32_t T, uint32_t c
     work_apply_fill_kernel<<<dim3(tiles), dim3(SC_THREADS), 0, s>>>(ranges, T, chunk, min_len, partial, chunk_base, work_tile);
 }
 
-size_t build_work_temp_bytes(size_t T) { return T > 4096 ? sizeof(uint32_t) * 2 * T + scan_temp_bytes((int)T) + 256 : 0; }
+size_t build_work_temp_bytes(size_t T) { return T > 4096 ? sizeof(uint32_t) * ((T + SC_TILE - 1) / SC_TILE) + 256 : 0; }
 
 void launch_build_work(const uint2 *ranges, uint32_t T, uint32_t chunk, uint32_t *chunk_base, uint4 *work_tile,
                        void *temp, hipStream_t s, uint32_t min_len)
@@ -645,19 +618,10 @@ void launch_build_work(const uint2 *ranges, uint32_t T, uint32_t chunk, uint32_t
         build_work_kernel<<<dim3(1), dim3(1024), 0, s>>>(ranges, T, chunk, chunk_base, work_tile, min_len);
         return;
     }
-    static const bool two = [] { const char *e = getenv("R2_WORK_TWO"); return !(e && e[0] == '0'); }();
-    if (two) {
-        uint32_t *partial = reinterpret_cast<uint32_t *>(temp);   // (T + SC_TILE - 1) / SC_TILE words of the 2 T + ... reserved
-        const uint32_t tiles = (T + SC_TILE - 1) / SC_TILE;
-        work_reduce_kernel<<<dim3(tiles), dim3(SC_THREADS), 0, s>>>(ranges, T, chunk, min_len, partial);
-        work_apply_fill_kernel<<<dim3(tiles), dim3(SC_THREADS), 0, s>>>(ranges, T, chunk, min_len, partial, chunk_base, work_tile);
-        return;
-    }
-    uint32_t *nw = reinterpret_cast<uint32_t *>(temp), *incl = nw + T;
-    void *scan_tmp = incl + T;
-    work_count_kernel<<<dim3((T + 255) / 256), dim3(256), 0, s>>>(ranges, T, chunk, nw, min_len);
-    (void)inclusive_scan_u32(scan_tmp, scan_temp_bytes((int)T), nw, incl, (int)T, s);
-    work_fill_kernel<<<dim3((T + 255) / 256), dim3(256), 0, s>>>(ranges, chunk, nw, incl, T, chunk_base, work_tile);
+    uint32_t *partial = reinterpret_cast<uint32_t *>(temp);   // one word per block of SC_TILE tiles
+    const uint32_t tiles = (T + SC_TILE - 1) / SC_TILE;
+    work_reduce_kernel<<<dim3(tiles), dim3(SC_THREADS), 0, s>>>(ranges, T, chunk, min_len, partial);
+    work_apply_fill_kernel<<<dim3(tiles), dim3(SC_THREADS), 0, s>>>(ranges, T, chunk, min_len, partial, chunk_base, work_tile);
 }
 
 // Single-pass tile sort: the sort's digit totals are the per-tile instance counts, so the tile ranges

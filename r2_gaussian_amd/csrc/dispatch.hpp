@@ -12,7 +12,7 @@
 //   voxelizer fwd      small-grid   <= 64 tiles, <= 8 per axis (the 32^3 TV patch)    voxel_forward_choice()               more than 8192 survivors / state beyond the temp's capacity
 //                      stick-first  65 .. 32768 tiles (64^3 .. the 256^3 query)       voxel_forward_choice()               a list beyond the long-list rule (r2_voxel_sticks_limits), remembered per (P, grid)
 //                      general      everything (debug, x-slabs of <= 64 tiles, larger grids)
-//   render kernels     one-wave forward / four-wave forward (ids >= 2^28, R2_FWD_WAVE=0) / debug (n_contrib)
+//   render kernels     one-wave forward / four-wave forward (ids >= 2^28) / debug (n_contrib)
 // Results never depend on the chain: point_list, ranges, images / volumes and gradients are identical (tests/test_*_gpu.py compare them).
 #pragma once
 #include "r2_common.hpp"

@@ -169,7 +169,7 @@ static int raster_forward_impl(
         if (sort_is_single_pass(bit)) {
             const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, FWD_CHUNK,
                                  debug ? nullptr : img.tile_done, 0u, 0u,
-                                 (raster_forward_wave_kernel_on() && raster_ids_leave_room_for_masks((size_t)PV)) ? 1u : 0u};
+                                 raster_ids_leave_room_for_masks((size_t)PV) ? 1u : 0u};
             rc = sort_by_tile_single_pass(bin.sort_temp, bin.sort_bytes, bin.tiles_unsorted, bin.vals_unsorted, bin.point_list,
                                           debug ? bin.inv : nullptr, R, bit, &tile_counts, s, &wo, hist_ready);   // inv: introspection only
             work_built = true;

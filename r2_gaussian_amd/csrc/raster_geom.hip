@@ -837,20 +837,18 @@ int launch_raster_preprocess_tf(const RasterGeom &g, int P, int V, const TFGrid 
     const float focal_y = H / (2.0f * tan_fovy);
     const float focal_x = W / (2.0f * tan_fovx);
     const int gx = (W + TILE2D - 1) / TILE2D, gy = (H + TILE2D - 1) / TILE2D;
-    bool share = (int)grid.wgs > device_cu_count() && grid.threads > TF_THREADS_MAX / 2;
-    {   // stacked views: the view arithmetic does not fit the 64-register instantiation (35 spilled registers); one workgroup per CU
-        // at a time measured 1.5 % (V = 2) and 0.7 % (V = 4) faster per call than two spilling ones (R2_TF_MV_SHARE=1: the other way)
-        static const int mv_share = [] { const char *e = getenv("R2_TF_MV_SHARE"); return e ? atoi(e) : 0; }();
-        if (V > 1 && !mv_share) share = false;
-    }
+    // stacked views never share: the view arithmetic does not fit the 64-register instantiation (35 spilled registers); one workgroup
+    // per CU at a time measured 1.5 % (V = 2) and 0.7 % (V = 4) faster per call than two spilling ones
+    const bool share = V == 1 && (int)grid.wgs > device_cu_count() && grid.threads > TF_THREADS_MAX / 2;
 #define R2_TF_PRE(SLB, SHR, MVW)                                                                                                       \
     raster_preprocess_tf_kernel<SLB, SHR, MVW><<<dim3(grid.wgs), dim3(grid.threads), (size_t)gx * gy * V * slabs.n * sizeof(uint32_t), s>>>( \
         P, V, grid.per_wg, slabs, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, view, proj, W, H, tan_fovx, tan_fovy, \
         focal_x, focal_y, mode, gx, gy, radii, g.rec, g.depth_key, g.cov3D, g.tiles_touched, g.op_mu, g.first, g.tf_rect, g.tf_wgoff,      \
         g.tf_wgmm, ctr)
 #define R2_TF_PRE2(SLB)                                                                                                                \
-    if (share) { if (V > 1) R2_TF_PRE(SLB, true, true); else R2_TF_PRE(SLB, true, false); }                                             \
-    else { if (V > 1) R2_TF_PRE(SLB, false, true); else R2_TF_PRE(SLB, false, false); }
+    if (share) R2_TF_PRE(SLB, true, false);                                                                                            \
+    else if (V > 1) R2_TF_PRE(SLB, false, true);                                                                                       \
+    else R2_TF_PRE(SLB, false, false);
     if (slabs.n > 1u) { R2_TF_PRE2(true) }
     else { R2_TF_PRE2(false) }
 #undef R2_TF_PRE2

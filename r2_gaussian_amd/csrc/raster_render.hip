@@ -61,14 +61,9 @@ template <bool EXACT>
 __device__ __forceinline__ void fwd_item(const float4 a, float C2, float L, float x0, float y0, float (&acc)[64])
 {
     const float dx0 = a.x - x0;
-    const float k1 = a.z * (1.0f - 2.0f * dx0);                       // log2 of alpha(1)/alpha(0), minus B2*dy
-    const float rr = EXACT ? 0.f : __builtin_amdgcn_exp2f(2.0f * a.z);   // second ratio, constant along the row
-#if defined(R2_EXP_FWD_CMPX) && !defined(R2_EXP_NO_CMPX)
-    const unsigned long long full_exec = __builtin_amdgcn_read_exec();
-    (void)full_exec;
-#endif
-#ifndef R2_EXP_NO_YRECUR
     if (!EXACT) {
+        const float k1 = a.z * (1.0f - 2.0f * dx0);            // log2 of alpha(1)/alpha(0), minus B2*dy
+        const float rr = __builtin_amdgcn_exp2f(2.0f * a.z);   // second ratio, constant along the row
         // Round 6: a second recurrence ACROSS the rows (the voxelizer's, voxel_render.hip vfwd_item, round 4).  Until now every row
         // paid two v_exp_f32 (start value, first ratio) and the arithmetic of their arguments: 14 of a row's 54 issue slots.  The
         // row starts E(r) = log2 alpha(column 0, row r) are a parabola in r as well:
@@ -87,6 +82,9 @@ __device__ __forceinline__ void fwd_item(const float4 a, float C2, float L, floa
         const float chi = __builtin_amdgcn_exp2f(a.w), chii = __builtin_amdgcn_exp2f(-a.w);
         float rtu = __builtin_amdgcn_exp2f(fminf(k1 - a.w * dy4, 120.0f));
         float rtd = rtu * chii;
+        // power <= 0 holds: positive definite conic.  (The EXEC-mask form of the accumulation -- v_cmpx + add + s_mov exec, 2 VALU
+        // instead of 3 -- gains 2.7 us in the backward, which is issue-bound; here it was measured twice, rounds 1 and 2: 1 us
+        // SLOWER.  This kernel waits on latency, not on the VALU.)
 #define R2_FWD_ROW(ROW, G0, RT0)                                                                \
         {                                                                                       \
             float g = (G0), rt = (RT0);                                                         \
@@ -111,43 +109,19 @@ __device__ __forceinline__ void fwd_item(const float4 a, float C2, float L, floa
 #undef R2_FWD_ROW
         return;
     }
-#endif
 #pragma unroll
     for (int r = 0; r < SUB2D; ++r) {
         const float dy = a.y - (y0 + (float)r);
         const float bdy = a.w * dy;
         const float cdl = (C2 * dy) * dy + L;
-        if (EXACT) {
 #pragma unroll
-            for (int c = 0; c < SUB2D; ++c) {
-                const float dx = dx0 - (float)c;
-                const float pl = dx * (a.z * dx + bdy) + cdl;     // log2(alpha)
-                const float al = __builtin_amdgcn_exp2f(pl);
-                // power <= 0 (RAS/forward.cu:369) <=> pl <= L ; alpha >= 1e-5 (RAS/forward.cu:374)
-                const bool ok = (pl <= L) && (al >= ALPHA_MIN_2D);
-                acc[r * SUB2D + c] += ok ? al : 0.f;
-            }
-        } else {
-            float g = __builtin_amdgcn_exp2f(dx0 * (a.z * dx0 + bdy) + cdl);
-            float rt = __builtin_amdgcn_exp2f(fminf(k1 - bdy, 120.0f));
-#pragma unroll
-            for (int c = 0; c < SUB2D; ++c) {
-                // power <= 0 holds: positive definite conic.  (The EXEC-mask form of this -- v_cmpx + add + s_mov exec, 2 VALU
-                // instead of 3 -- gains 2.7 us in the backward, which is issue-bound; here it was measured twice, rounds 1
-                // and 2: 1 us SLOWER.  This kernel waits on latency, not on the VALU.)
-#if defined(R2_EXP_FWD_CMPX) && !defined(R2_EXP_NO_CMPX)
-                asm volatile("v_cmpx_le_f32_e32 %[thr], %[g]\n\t"
-                             "v_add_f32_e32 %[a], %[a], %[g]\n\t"
-                             "s_mov_b64 exec, %[ex]"
-                             : [a] "+v"(acc[r * SUB2D + c])
-                             : [thr] "v"(ALPHA_MIN_2D), [g] "v"(g), [ex] "s"(full_exec)
-                             : "vcc");
-#else
-                acc[r * SUB2D + c] += (g >= ALPHA_MIN_2D) ? g : 0.f;
-#endif
-                g *= rt;
-                rt *= rr;
-            }
+        for (int c = 0; c < SUB2D; ++c) {
+            const float dx = dx0 - (float)c;
+            const float pl = dx * (a.z * dx + bdy) + cdl;     // log2(alpha)
+            const float al = __builtin_amdgcn_exp2f(pl);
+            // power <= 0 (RAS/forward.cu:369) <=> pl <= L ; alpha >= 1e-5 (RAS/forward.cu:374)
+            const bool ok = (pl <= L) && (al >= ALPHA_MIN_2D);
+            acc[r * SUB2D + c] += ok ? al : 0.f;
         }
         __builtin_amdgcn_sched_barrier(0);   // one row at a time: keeps the 64 accumulators + one row of temporaries live
     }
@@ -336,11 +310,9 @@ __global__ void __launch_bounds__(256, 4) raster_render_forward_kernel(
 // whole chunk instead of per 256-entry batch), so the two kernels' images agree to float association, not bit for bit.
 // blockIdx -> (work item, block): the four blocks of an item run on ONE XCD (block b of the grid runs on XCD b % 8), so its
 // records are pulled into one L2.
-#ifndef R2_EXP_FWD_OCC
-#define R2_EXP_FWD_OCC 4
-#endif
+constexpr int FWD_WAVE_OCC = 4;   // waves per SIMD the kernel is compiled for
 template <bool MV>
-__global__ void __launch_bounds__(64, R2_EXP_FWD_OCC) raster_render_forward_wave_kernel(
+__global__ void __launch_bounds__(64, FWD_WAVE_OCC) raster_render_forward_wave_kernel(
     const uint2 *__restrict__ ranges, const uint32_t *__restrict__ chunk_base, const uint4 *__restrict__ work_tile, uint32_t T, uint32_t NW,
     const uint32_t *__restrict__ masked, const float4 *__restrict__ rec, int gx, int gy, float *__restrict__ partial,
     uint32_t *__restrict__ tile_done, float *__restrict__ out_color, int W, int H, uint32_t *__restrict__ tiles, char *tf_bin_base,
@@ -410,22 +382,12 @@ __global__ void __launch_bounds__(64, R2_EXP_FWD_OCC) raster_render_forward_wave
         nb = rec[2 * id + 1];
     }
     for (int head = 0; head < cnt; head += 64) {
-#ifdef R2_EXP_FWD_NOPF   // experiment: no record prefetch (8 registers less: 5 waves per SIMD), the gather's round trip exposed per step
-        float4 ea, eb;
-        {
-            const uint32_t id = sQ[min(head + lane, cnt - 1)];
-            ea = rec[2 * id];
-            eb = rec[2 * id + 1];
-        }
-        (void)na; (void)nb;
-#else
         float4 ea = na, eb = nb;
         {
             const uint32_t id = sQ[min(head + 64 + lane, cnt - 1)];
             na = rec[2 * id];
             nb = rec[2 * id + 1];
         }
-#endif
         const bool live = head + lane < cnt;
         if (!live) { ea = make_float4(0.f, 0.f, 0.f, 0.f); eb = make_float4(0.f, -INFINITY, 0.f, 0.f); }   // idle lane: alpha = 0
         const int tier = live ? item_tier(ea.z, ea.w, eb.x, eb.y, eb.z, eb.w) : 0;
@@ -620,10 +582,7 @@ constexpr int MAX_WAVE_TILES = 3;
 // frees its slot and its 8 KB of LDS at once instead of waiting for its three siblings (-3 % kernel time).  Walking the
 // chunks with a grid-stride loop from a few resident workgroups per CU was measured too: no gain.
 constexpr int BWD_WAVES = 1, BWD_THREADS = 64 * BWD_WAVES;
-#ifndef R2_EXP_BWD_OCC
-#define R2_EXP_BWD_OCC 4
-#endif
-constexpr int BWD_OCC = R2_EXP_BWD_OCC;   // waves per SIMD the kernel is compiled for (121 VGPRs with the pipeline registers)
+constexpr int BWD_OCC = 4;   // waves per SIMD the kernel is compiled for (121 VGPRs with the pipeline registers)
 
 __device__ __forceinline__ void pixel_moments(float A2, float lthr, float dx, float bdy, float cdy2, float g, float &r0,
                                               float &r1, float &r3)
@@ -719,7 +678,6 @@ __device__ __forceinline__ void block_moments_lds(const float4 a, const float4 b
         U[3] = fmaf(dy, t0, U[3]); U[4] = fmaf(dy, t1, U[4]); U[5] = fmaf(dy * dy, t0, U[5]);
     };
     if (!EXACT) {
-#ifndef R2_EXP_NO_YRECUR
         // Round 6: the row starts by a recurrence across the rows, as in the forward (fwd_item has the derivation; G carries
         // no amplitude here, the cut-off is gthr): nine exponentials per item instead of eighteen, three multiplications per row
         // instead of two exponentials and their arguments.  item_tier keeps out the entries the walks are not safe for.
@@ -744,15 +702,6 @@ __device__ __forceinline__ void block_moments_lds(const float4 a, const float4 b
             recur_row(N / 2 - 1 - j, gd, rtd);
             gd *= rd; rd *= kap; rtd *= chii;
         }
-#else
-#pragma unroll 2
-        for (int r = 0; r < N; ++r) {
-            const float dy = a.y - (by0 + (float)r);
-            const float bdy = a.w * dy;           // B2*dy
-            const float cdy2 = (b.x * dy) * dy;   // C2*dy^2
-            recur_row(r, __builtin_amdgcn_exp2f(dx0 * (a.z * dx0 + bdy) + cdy2), __builtin_amdgcn_exp2f(fminf(k1 - bdy, 120.0f)));
-        }
-#endif
         S[0] += U[0]; S[1] += dm * U[0] - U[1]; S[3] += dm * (dm * U[0] - 2.0f * U[1]) + U[2];
         S[2] += U[3]; S[4] += dm * U[3] - U[4]; S[5] += U[5];
         return;
@@ -853,11 +802,7 @@ __global__ void __launch_bounds__(BWD_THREADS, BWD_OCC) raster_render_backward_k
     uint32_t first_row;
     R2_TS_AT(render, 2);
     load1(blockIdx.x, tile, id, live);
-#ifndef R2_EXP_BWD_NOPIPE
     load1(blockIdx.x + G, tile1, id1, live1);
-#else
-    tile1 = 0; id1 = 0; live1 = false;
-#endif
     load2(id, a, b, rad, first_row);
 
     for (uint32_t v = blockIdx.x; v < nslots; v += G) {
@@ -887,12 +832,8 @@ __global__ void __launch_bounds__(BWD_THREADS, BWD_OCC) raster_render_backward_k
     float4 a1, b1;
     int rad1;
     uint32_t first_row1;
-#ifndef R2_EXP_BWD_NOPIPE
     load1(v + 2u * G, tile2, id2, live2);
     load2(id1, a1, b1, rad1, first_row1);
-#else   // experiment: no software pipeline (one chunk per wave), occupancy instead
-    tile2 = 0; id2 = 0; live2 = false; a1 = a; b1 = b; rad1 = 0; first_row1 = 0;
-#endif
 
     float S[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
     // The chunk's tiles are handled MAX_WAVE_TILES at a time (nearly always one pass: 97 % of the waves sit inside a
@@ -1009,9 +950,6 @@ __global__ void __launch_bounds__(BWD_THREADS, BWD_OCC) raster_render_backward_k
         part[2 * u] = make_float4(S[0], S[1], S[2], S[3]);
         part[2 * u + 1] = make_float4(S[4], S[5], 0.f, 0.f);
     }
-#ifdef R2_EXP_BWD_NOPIPE
-    break;
-#endif
     // rotate the pipeline registers
     tile = tile1; id = id1; live = live1;
     tile1 = tile2; id1 = id2; live1 = live2;
@@ -1029,25 +967,19 @@ __global__ void __launch_bounds__(BWD_THREADS, BWD_OCC) raster_render_backward_k
 // queue over all blocks of 64 instances fills its rounds to ~92 %: 57 k steps instead of 36 k rounds, at ~800 issue slots each, on
 // SIMDs that the seven resident waves keep 63 % busy -- the kernel was compute-bound on work it created itself.)
 // ------------------------------------------------------------------------------------------------ launchers
-bool raster_forward_wave_kernel_on()
-{
-    static const bool on = [] { const char *e = getenv("R2_FWD_WAVE"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 template <bool MV>
 static void launch_fwd(const RasterGeom &g, const RasterBinning &b, const RasterImage &im, int W, int H, int gx, int gy, uint32_t T,
                        float *out_color, bool write_ncontrib, uint32_t *fill_tiles, bool fused_combine, hipStream_t s,
                        char *tf_bin_base, const uint32_t *tf_words, bool ids_below_2_28)
 {
-    // round 6: the one-wave kernel (R2_FWD_WAVE=0: the four-wave kernel of rounds 1-5, kept as the A/B reference); ids carry
-    // MASK_BITS of block mask, i.e. view instances below 2^28
+    // the one-wave kernel wherever its list exists: ids carry MASK_BITS of block mask, i.e. view instances below 2^28; beyond that
+    // the four-wave kernel of rounds 1-5
     // the masked list for chains whose sort did not carry the masks: the forward's wave kernel and the backward read it, so every
     // forward leaves it behind (the backward cannot ask which path ran; it chooses by the same ids_below_2_28 rule)
     if (tf_bin_base == nullptr && im.NW > 0 && ids_below_2_28)
         raster_mask_fill_kernel<MV><<<dim3((unsigned)im.NW), dim3(256), 0, s>>>(im.chunk_base, im.work_tile, T, b.point_list, g.rec,
                                                                                 gx, gy, b.masked);
-    if (fused_combine && !write_ncontrib && im.NW > 0 && raster_forward_wave_kernel_on() && ids_below_2_28) {
+    if (fused_combine && !write_ncontrib && im.NW > 0 && ids_below_2_28) {
         const uint32_t *masked = b.masked;
         const unsigned grid = (unsigned)((im.NW + 7) / 8) * 32u;   // 8 work items x 4 blocks per group of 32 workgroups
         raster_render_forward_wave_kernel<MV><<<dim3(grid), dim3(64), 0, s>>>(
@@ -1095,8 +1027,7 @@ int launch_raster_render_backward(const RasterGeom &g, const RasterBinning &b, c
 {
     if (R == 0) return 0;
     // every forward leaves the masked list behind when the ids leave room for the mask bits (launch_raster_render_forward)
-    static const bool masks_on = [] { const char *e = getenv("R2_BWD_MASKS"); return !(e && e[0] == '0'); }();
-    const uint32_t *masked = (masks_on && view_instances < ((size_t)1 << (32 - MASK_BITS))) ? b.masked : nullptr;
+    const uint32_t *masked = view_instances < ((size_t)1 << (32 - MASK_BITS)) ? b.masked : nullptr;
     const int gx = (W + TILE2D - 1) / TILE2D;
     const uint32_t nchunks = (uint32_t)((R + BWD_THREADS - 1) / BWD_THREADS);
     // Grid = a whole number of "rounds" of resident waves (CUs x 4 SIMDs x BWD_OCC); the chunks beyond it are second chunks
@@ -1106,12 +1037,7 @@ int launch_raster_render_backward(const RasterGeom &g, const RasterBinning &b, c
     const int cus = device_cu_count();
     const uint32_t slots = (uint32_t)cus * 4u * (uint32_t)BWD_OCC;   // a multiple of 8 (XCD-aware chunk order)
     const uint32_t nslots = ((nchunks + 7u) >> 3) << 3;
-#ifdef R2_EXP_BWD_NOPIPE
-    const uint32_t grid = nslots;
-    (void)slots;
-#else
     const uint32_t grid = (nslots <= slots || (slots & 7u)) ? nslots : (nslots / slots) * slots;
-#endif
     const int gy = (H + TILE2D - 1) / TILE2D;
     if (V > 1)   // the view of an instance follows from its tile id
         raster_render_backward_kernel<true><<<dim3(grid), dim3(BWD_THREADS), 0, s>>>(

@@ -7,10 +7,7 @@
 
 namespace r2 {
 
-#ifndef R2_EXP_FWD_CHUNK
-#define R2_EXP_FWD_CHUNK 1024
-#endif
-constexpr uint32_t FWD_CHUNK = R2_EXP_FWD_CHUNK;   // instances of one tile list rendered by one workgroup (load balance)
+constexpr uint32_t FWD_CHUNK = 1024;   // instances of one tile list rendered by one workgroup (load balance)
 constexpr int PART_STRIDE = 8;        // floats per instance in the backward moment scratch (6 used)
 constexpr float ALPHA_MIN_2D = 0.00001f;               // RAS/forward.cu:374
 constexpr float LOG2_ALPHA_MIN_2D = -16.609640474436812f;   // log2(1e-5)
@@ -70,18 +67,13 @@ __device__ __forceinline__ bool needs_exact_row(float A2, float L, float hx) { r
 // Gaussian: sigma >= 0.92 px, against 0.85 px for the seven row steps alone; the bound 7 sqrt|A2| + 3 sqrt|C2| that ignores how
 // the two displacements combine sent sigma < 1.2 px -- a third of the benchmark cloud's entries -- down the exact path).  A row
 // start the column walk underflowed is covered by the row criterion, which this implies.  0: both recurrences; 2: exact
-// per-pixel evaluation.  (Without the row recurrence -- R2_EXP_NO_YRECUR -- this is row_tier.)
+// per-pixel evaluation.
 __device__ __forceinline__ int item_tier(float A2, float B2, float C2, float L, float hx, float hy)
 {
-#ifdef R2_EXP_NO_YRECUR
-    (void)B2; (void)C2; (void)hy;
-    return row_tier(A2, L, hx);
-#else
     const float room = __builtin_amdgcn_sqrtf(fmaxf(125.5f + fminf(L, 0.f), 0.f)) - __builtin_amdgcn_sqrtf(fmaxf(L - LOG2_ALPHA_MIN_2D, 0.f) + 1.0f);
     if (!(hx < 3.0e38f) || !(hy < 3.0e38f) || !(room > 0.f)) return 2;
     const float reach2 = 49.0f * fabsf(A2) + 9.0f * fabsf(C2) + 21.0f * fabsf(B2);
     return reach2 <= room * room ? 0 : 2;
-#endif
 }
 
 // does the bounding box (px +- hx, py +- hy) of a Gaussian's alpha >= 1e-5 region touch the pixel block
@@ -352,9 +344,8 @@ int launch_raster_render_forward(const RasterGeom &g, const RasterBinning &b, co
                                  float *out_color, bool write_ncontrib, uint32_t *fill_tiles, bool fused_combine,
                                  hipStream_t s, char *tf_bin_base = nullptr, const uint32_t *tf_words = nullptr,
                                  size_t view_instances = 0 /* P x V: ids of the masked list */);
-// the one-wave forward kernel is in use (R2_FWD_WAVE=0: the four-wave kernel of rounds 1-5); it takes its work list longest first,
-// the four-wave kernel in tile order (WorkListOut::longest_first)
-bool raster_forward_wave_kernel_on();
+// ids that leave room for the block mask are rendered by the one-wave forward kernel (not in debug mode); it takes its work list
+// longest first, the four-wave kernel in tile order (WorkListOut::longest_first)
 inline bool raster_ids_leave_room_for_masks(size_t view_instances) { return view_instances < ((size_t)1 << (32 - MASK_BITS)); }
 // raster_tilefirst.hip
 int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void *geometry_user, r2_alloc_fn binningBuffer,

@@ -764,12 +764,6 @@ bool tf_lds_ok()
            allow_dynamic_lds(reinterpret_cast<const void *>(raster_tf_sort_kernel), (int)TFK_LDS, lds_state);
 }
 
-int tf_forced_slabs()
-{
-    static const int v = [] { const char *e = getenv("R2_TF_SLABS"); return e ? atoi(e) : 0; }();
-    return (v == 1 || v == 2 || v == 4) ? v : 0;
-}
-
 }  // namespace
 
 void raster_tilefirst_note(int P, int V, int W, int H, uint32_t num_rendered, bool thin, uint32_t kmax, uint32_t kmin)
@@ -862,8 +856,6 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
         uint32_t d = 1u;
         if (ml > (double)TF_SLAB_SPLIT_ABOVE)
             while (d < TF_MAX_SLABS && T * d * 2u <= TF_MAX_TILES) d *= 2u;
-        if (const int f = tf_forced_slabs())
-            if (T * (size_t)f <= TF_MAX_TILES) d = (uint32_t)f;
         if (kmax <= kmin) d = 1u;   // no key range to lay the slabs over
         slabs.n = d;
         slabs.scale = d > 1u ? (float)d / ((float)(kmax - kmin) + 1.0f) : 0.f;
@@ -911,7 +903,7 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
             uint2 *pairs = reinterpret_cast<uint2 *>(bin.part);   // backward scratch (32 bytes per instance), free until then
             { StageScope t(ST_RAS_DUPLICATE, s);
             const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, FWD_CHUNK, img.tile_done, 0u, (uint32_t)img.NW,
-                                 raster_forward_wave_kernel_on() ? 1u : 0u};
+                                 1u /* ids below 2^24, never debug (dispatch.hpp): always the one-wave forward kernel */};
 #define R2_TF_SCATTER(SLB)                                                                                                        \
             raster_tf_scatter_kernel<SLB><<<dim3((unsigned)wgs + TFS_SERVICE), dim3(TFS_THREADS), TL * sizeof(uint32_t), s>>>(         \
                 PV, P, gy, grid.per_wg, grid.threads, gx, (uint32_t)TL, slabs, geom.tf_rect, geom.rec, geom.depth_key, geom.tiles_touched, geom.tf_wgoff, \

@@ -59,11 +59,7 @@ __device__ __forceinline__ bool slab_live(float px, float py, float pz, float4 h
     const float u = dx * __builtin_amdgcn_rcpf(h.x);
     const float t = __builtin_amdgcn_sqrtf(fmaxf(1.0f - u * u, 0.0f));   // raw v_sqrt_f32 (1 ulp): sqrtf costs ~20 instructions here
     const float cy = py - h.w * dx, cz = pz - kz * dx;
-#ifdef R2_EXP_SLAB_HALF   // sensitivity experiment of profiles/r04f_voxel_steps.txt: halved cross-section (WRONG volumes)
-    const float ey = 0.5f * h.y * t, ez = 0.5f * h.z * t;
-#else
     const float ey = h.y * t, ez = h.z * t;
-#endif
     return (fabsf(dx) <= h.x) && (cy - ey <= y0 + 7.5f) && (cy + ey >= y0 + 0.5f) && (cz - ez <= z0 + 7.5f) &&
            (cz + ez >= z0 + 0.5f);
 }
@@ -481,13 +477,6 @@ __device__ __forceinline__ void vfwd_short_body(
     }
 }
 
-__global__ void __launch_bounds__(256) voxel_render_short_kernel(
-    const uint2 *__restrict__ ranges, uint32_t T, const uint32_t *__restrict__ point_list, const float4 *__restrict__ rec,
-    const float4 *__restrict__ ext, VoxelGrid v, float *__restrict__ out)
-{
-    vfwd_short_body(blockIdx.x, ranges, T, point_list, rec, ext, v, out);
-}
-
 // Both in ONE launch: the item workgroups first (the long ones), the short-list workgroups behind them start while the
 // item tail drains (0.668 -> 0.660 ms at 256^3).  (Measured and left out: short groups interleaved evenly among the item
 // groups, so that latency-bound and arithmetic waves mix for the whole kernel: 0.685 ms -- the item workgroups lose the
@@ -567,7 +556,7 @@ __global__ void __launch_bounds__(512) voxel_combine_kernel(
         if (i < pub.T + 1u) pub.dst_chunk_base[i] = pub.src_chunk_base[i];
         if (i < pub.NW) pub.dst_work[i] = pub.src_work[i];
     }
-    if (!NCONTRIB && short_min) {   // tiles with a short list were rendered by voxel_render_short_kernel
+    if (!NCONTRIB && short_min) {   // tiles with a short list were rendered by the short-list workgroups
         const uint2 rg = ranges[tile];
         if (rg.y != rg.x && rg.y - rg.x < short_min) return;
     }
@@ -875,24 +864,9 @@ int launch_voxel_render_forward(const VoxelGeom &g, const VoxelBinning &b, const
         // short lists: one wave per tile (the work list holds no item for them, see voxel_short_list_min())
         // grid rounded up to whole 1024-block XCD interleave groups (the in-kernel block -> work item map)
         // item workgroups: an estimate of the work list (two per ~512 instances; im.NW is the upper bound), see vfwd_items
-        unsigned item_blocks = (unsigned)(((std::min<size_t>(2 * im.NW, std::max<size_t>(1024, im.R / 256)) + 1023) / 1024) * 1024);
-#ifdef R2_EXP_EXACT_GRID   // experiment: what do the workgroups beyond the work list cost?  (host read-back: not a product path)
-        {
-            uint32_t nitems = 0;
-            (void)hipMemcpyAsync(&nitems, im.chunk_base + T, 4, hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            item_blocks = (unsigned)(((2 * (size_t)nitems + 1023) / 1024) * 1024);
-        }
-#endif
-        static const bool split = [] { const char *e = getenv("R2_VOXEL_SPLIT_SHORT"); return e && e[0] == '1'; }();
-        if (split) {
-            voxel_render_short_kernel<<<dim3((T + 3) / 4), dim3(256), 0, s>>>(im.ranges, T, b.point_list, g.rec, g.ext, v, out_volume);
-            voxel_render_forward_kernel<<<dim3(item_blocks), dim3(256), 0, s>>>(
-                im.ranges, im.chunk_base, im.work_tile, T, b.point_list, g.rec, g.ext, v, im.partial, out_volume);
-        } else {
-            voxel_render_forward_both_kernel<<<dim3(item_blocks + (T + 3) / 4), dim3(256), 0, s>>>(
-                item_blocks, im.ranges, im.chunk_base, im.work_tile, T, b.point_list, g.rec, g.ext, v, im.partial, out_volume);
-        }
+        const unsigned item_blocks = (unsigned)(((std::min<size_t>(2 * im.NW, std::max<size_t>(1024, im.R / 256)) + 1023) / 1024) * 1024);
+        voxel_render_forward_both_kernel<<<dim3(item_blocks + (T + 3) / 4), dim3(256), 0, s>>>(
+            item_blocks, im.ranges, im.chunk_base, im.work_tile, T, b.point_list, g.rec, g.ext, v, im.partial, out_volume);
     }
     voxel_combine_tiles_kernel<<<dim3((T + 7) / 8), dim3(512), 0, s>>>(im.chunk_base, im.partial, v, out_volume, im.ranges, T,
                                                                         im.NW > 0 ? (uint32_t)VFWD_MIN_STEP : 0u, pub);

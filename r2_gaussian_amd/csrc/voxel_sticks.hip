@@ -841,9 +841,6 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
     // (the 92k trained cloud, 65 tiles per Gaussian, 6 M instances, longest list 7245: 791 -> 755 us) -- since a Gaussian of
     // thousands of tiles is walked by its whole wave in the count and scatter kernels; before that, one lane walked a background
     // blob's tiles for 235 us and the same query took 964.
-    const uint32_t nvis = hw[DW_NVIS];
-    static const bool dbg = [] { const char *e = getenv("R2_VOXEL_STICKS_DEBUG"); return e && e[0] == '1'; }();
-    if (dbg) fprintf(stderr, "voxel sticks: P %d R %u visible %u longest list %u\n", P, num_rendered, nvis, longest);
     const bool large = (long long)longest > g_vs_long_list.load(std::memory_order_relaxed) &&
                        (long long)num_rendered > g_vs_long_scene.load(std::memory_order_relaxed);
     if (large || parts_bound > st.bigcap || (g_vs_no_parts.load(std::memory_order_relaxed) && longest > VSK_BIG_CAP)) {
