@@ -170,10 +170,30 @@ R2_API int r2_raster_backward_batch(
  * padding) of one [height,width] projection AND its gradient dL/dimg, in two launches; scalars = {l1 mean, ssim mean, loss}.
  * r2_loss_tv3d: tv = tv_3d_loss(vol, "mean") of a [nx,ny,nz] volume and dL/dvol = weight * d tv / d vol; scalars = {tv,
  * weight * tv}; a volume without neighbour pairs (1 x 1 x 1) gives tv = NaN (0 / 0, as the reference) and a zero gradient.
- * scratch: device floats, at least r2_loss_*_scratch_floats(...).  Per-block sums are folded in a fixed order in double. */
+ * scratch: device floats, at least r2_loss_*_scratch_floats(...).  Per-block sums are folded in a fixed order in double.
+ * r2_loss_l1_ssim_batch: V >= 1 projections imgs [V,height,width] against V ground truths, for the loss
+ *   mean over the views v of  w_l1 * mean|img_v - gt_v| + w_ssim * (1 - SSIM(img_v, gt_v)),
+ * forward and gradient, with the kernels of r2_loss_l1_ssim run on a grid whose third dimension is the view.  gts_host: a
+ * HOST array of V device pointers, each to a [height,width] image (a step's ground truths are picks from a training set and
+ * need not be contiguous with each other; they are read in place).  The table travels to the kernels by value,
+ * R2_LOSS_BATCH_CHUNK views per pair of launches: ceil(V / R2_LOSS_BATCH_CHUNK) * 2 launches, no host synchronisation, no
+ * allocation, no copy.  V is bounded only by the grid: V * ceil(width / 16) * ceil(height / 16) must fit 31 bits.
+ *   scalars [V + 1][3]: row v < V = {l1 mean, ssim mean, loss} of view v, bit-identical to what r2_loss_l1_ssim(img_v, gt_v,
+ *     w_l1, w_ssim) writes; row V = the means of those float rows over the views, summed in view order in double.
+ *   dL_dimg [V,height,width]: the gradient of the batch loss; dL_dimg[v] is bit-identical to what r2_loss_l1_ssim(img_v,
+ *     gt_v, w_l1 / V, w_ssim / V) writes, the two quotients formed in float.
+ *   scratch: at least r2_loss_l1_ssim_batch_scratch_floats(V, width, height) device floats, 8-byte aligned ([V][3][height]
+ *     [width] derivative maps, then every view's per-block partial sums); 0 for sizes the call rejects.
+ *   R2_ERR_INVALID: V < 1, width or height <= 0, a NULL imgs / gts_host / gts_host[v] / dL_dimg / scratch / scalars, a
+ *     grid beyond the bound above. */
 R2_API size_t r2_loss_l1_ssim_scratch_floats(int width, int height);
 R2_API int r2_loss_l1_ssim(int width, int height, const float *img, const float *gt, float w_l1, float w_ssim,
                            float *dL_dimg, float *scratch, float *scalars /* [3] */, void *stream);
+#define R2_LOSS_BATCH_CHUNK 16 /* ground-truth pointers per launch of r2_loss_l1_ssim_batch */
+R2_API size_t r2_loss_l1_ssim_batch_scratch_floats(int V, int width, int height);
+R2_API int r2_loss_l1_ssim_batch(int V, int width, int height, const float *imgs /* [V,H,W] */,
+                                 const float *const *gts_host /* V device pointers */, float w_l1, float w_ssim,
+                                 float *dL_dimg /* [V,H,W] */, float *scratch, float *scalars /* [V + 1][3] */, void *stream);
 R2_API size_t r2_loss_tv3d_scratch_floats(int nx, int ny, int nz);
 R2_API int r2_loss_tv3d(int nx, int ny, int nz, const float *vol, float weight, float *dL_dvol, float *scratch,
                         float *scalars /* [2] */, void *stream);
@@ -195,6 +215,13 @@ R2_API int r2_metric_slices(int n0, int n1, int n2, int axis, const float *gt, c
 
 /* ---- adaptive density control on the device (r2_gaussian/gaussian/gaussian_model.py:320-556, train.py:151-168) ----
  * r2_densify_stats: max_radii2D / xyz_gradient_accum / denom update of one rendered view (in place, one launch).
+ * r2_densify_stats_batch: the same for the V >= 1 views of a batched render (radii [V,P], dL_dmeans2D [V,P,3], the layouts of
+ *   r2_raster_forward_batch / r2_raster_backward_batch) in ONE launch: for every view in order and every Gaussian with
+ *   radii > 0: max_radii2D = max(., radii), grad_accum += grad_scale * ||dL_dmeans2D[:2]||, denom += 1.  A thread owns a
+ *   Gaussian and walks the views in order, so with grad_scale == 1 the result is bit-identical to V calls of r2_densify_stats
+ *   in view order.  grad_scale: a step whose loss is the MEAN over its V views leaves 1 / V of each view's own gradient in
+ *   dL_dmeans2D; grad_scale = V gives the statistics of the views' own losses (exact for V a power of two), which keeps the
+ *   densification threshold a per-view quantity.  P == 0 enqueues nothing; P < 0, V < 1 or a NULL array: R2_ERR_INVALID.
  * r2_densify_classify + r2_densify_emit: densify_and_prune -- clone (small Gaussians with a large view-space gradient; both
  * copies get half the density), split (large ones: two children sampled from N(0, scale) in the local frame, scale / 1.6,
  * half the density, parent removed), prune (density below density_min, outside the box) -- with the Adam moments carried
@@ -207,6 +234,8 @@ R2_API int r2_metric_slices(int n0, int n1, int n2, int axis, const float *gt, c
  * params / exp_avg / exp_avg_sq (+ _out): 4 device pointers each in the order xyz[.,3], density[.,1], scaling[.,3], rotation[.,4]. */
 R2_API int r2_densify_stats(int P, const int *radii, const float *dL_dmeans2D /* [P,3] */, float *max_radii2D, float *grad_accum,
                             float *denom, void *stream);
+R2_API int r2_densify_stats_batch(int P, int V, const int *radii /* [V,P] */, const float *dL_dmeans2D /* [V,P,3] */,
+                                  float grad_scale, float *max_radii2D, float *grad_accum, float *denom, void *stream);
 R2_API size_t r2_densify_scratch_bytes(int P);
 R2_API int r2_densify_classify(int P, const float *xyz, const float *density, const float *scaling, const float *rotation,
                                const float *max_radii2D, const float *grad_accum, const float *denom, const float *normals,

@@ -17,6 +17,7 @@ R2_ERR_INVALID = -10001
 R2_ERR_ALLOC = -10002
 R2_METRIC_SSIM = 1
 R2_METRIC_NORMALIZE = 2
+R2_LOSS_BATCH_CHUNK = 16
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -55,12 +56,15 @@ _SIGNATURES = {
     "r2_path_stat_name": (C.c_char_p, [_i]),
     "r2_path_stats": (C.c_int, [C.POINTER(C.c_longlong), _i, _i]),
     "r2_densify_stats": (C.c_int, [_i, _p, _fp, _fp, _fp, _fp, _p]),
+    "r2_densify_stats_batch": (C.c_int, [_i, _i, _p, _fp, _f, _fp, _fp, _fp, _p]),
     "r2_densify_scratch_bytes": (C.c_size_t, [_i]),
     "r2_densify_classify": (C.c_int, [_i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _f, _p, _f, _f, _i, _f, _f, _p, _p, _p]),
     "r2_densify_emit": (C.c_int, [_i, _p, _p, _p, _fp, _fp, _fp, _fp, _f, _f, _f, _p, _f, _f, _i, _f, _f, _p, _p, _p, _p, _fp,
                                   _fp, _fp, _p]),
     "r2_loss_l1_ssim_scratch_floats": (C.c_size_t, [_i, _i]),
     "r2_loss_l1_ssim": (C.c_int, [_i, _i, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
+    "r2_loss_l1_ssim_batch_scratch_floats": (C.c_size_t, [_i, _i, _i]),
+    "r2_loss_l1_ssim_batch": (C.c_int, [_i, _i, _i, _fp, _p, _f, _f, _fp, _fp, _fp, _p]),
     "r2_loss_tv3d_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "r2_loss_tv3d": (C.c_int, [_i, _i, _i, _fp, _f, _fp, _fp, _fp, _p]),
     "r2_metric_slices_scratch_floats": (C.c_size_t, [_i, _i, _i, _i]),

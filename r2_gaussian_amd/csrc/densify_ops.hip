@@ -160,7 +160,19 @@ __global__ void __launch_bounds__(256) densify_emit_kernel(int P, Rows r, const 
     if (d.keep_child[1]) write_new((size_t)n0 + n1 + n2 + pos[3 * (size_t)P + i] - 1u, d.child_xyz[1], d.child_density_raw, d.child_scaling_raw);
 }
 
-// train.py:151-154 + add_densification_stats (gaussian_model.py:552-556), one launch, no boolean-mask indexing
+// train.py:151-154 + add_densification_stats (gaussian_model.py:552-556) of ONE view for ONE Gaussian, on the three statistics
+// in registers.  The single-view and the batched kernel both are this function.
+__device__ __forceinline__ void densify_stats_view(int rad, const float *__restrict__ g /* dL_dmeans2D row */, float grad_scale,
+                                                   float &max_radius, float &accum, float &count)
+{
+    if (!(rad > 0)) return;
+    max_radius = fmaxf(max_radius, (float)rad);
+    const float gx = g[0], gy = g[1];
+    accum += grad_scale * sqrtf(gx * gx + gy * gy);
+    count += 1.0f;
+}
+
+// one launch, no boolean-mask indexing
 __global__ void __launch_bounds__(256) densify_stats_kernel(int P, const int *__restrict__ radii, const float *__restrict__ g2d,
                                                             float *__restrict__ max_radii, float *__restrict__ grad_accum,
                                                             float *__restrict__ denom)
@@ -169,10 +181,28 @@ __global__ void __launch_bounds__(256) densify_stats_kernel(int P, const int *__
     if (i >= P) return;
     const int rad = radii[i];
     if (!(rad > 0)) return;
-    max_radii[i] = fmaxf(max_radii[i], (float)rad);
-    const float gx = g2d[3 * i], gy = g2d[3 * i + 1];
-    grad_accum[i] += sqrtf(gx * gx + gy * gy);
-    denom[i] += 1.0f;
+    float mr = max_radii[i], ga = grad_accum[i], dn = denom[i];
+    densify_stats_view(rad, g2d + 3 * (size_t)i, 1.0f, mr, ga, dn);
+    max_radii[i] = mr; grad_accum[i] = ga; denom[i] = dn;
+}
+
+// V views of the same Gaussians (radii [V,P], g2d [V,P,3]): every thread owns a Gaussian and walks the views in order
+__global__ void __launch_bounds__(256) densify_stats_batch_kernel(int P, int V, const int *__restrict__ radii,
+                                                                  const float *__restrict__ g2d, float grad_scale,
+                                                                  float *__restrict__ max_radii, float *__restrict__ grad_accum,
+                                                                  float *__restrict__ denom)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    float mr = max_radii[i], ga = grad_accum[i], dn = denom[i];
+    bool seen = false;
+    for (int v = 0; v < V; ++v) {
+        const size_t o = (size_t)v * P + i;
+        const int rad = radii[o];
+        seen = seen || rad > 0;
+        densify_stats_view(rad, g2d + 3 * o, grad_scale, mr, ga, dn);
+    }
+    if (seen) { max_radii[i] = mr; grad_accum[i] = ga; denom[i] = dn; }
 }
 
 }  // namespace
@@ -189,6 +219,24 @@ extern "C" int r2_densify_stats(int P, const int *radii, const float *dL_dmeans2
     r2::densify_stats_kernel<<<dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(P, radii, dL_dmeans2D, max_radii2D,
                                                                                           grad_accum, denom);
     R2_STAGE_CHECK(0, (hipStream_t)stream, "densification statistics");
+    return 0;
+}
+
+extern "C" int r2_densify_stats_batch(int P, int V, const int *radii, const float *dL_dmeans2D, float grad_scale, float *max_radii2D,
+                                      float *grad_accum, float *denom, void *stream)
+{
+    if (P < 0 || V < 1) {
+        r2::set_error("r2_densify_stats_batch: invalid argument (P < 0 or V < 1)");
+        return R2_ERR_INVALID;
+    }
+    if (P == 0) return 0;
+    if (!radii || !dL_dmeans2D || !max_radii2D || !grad_accum || !denom) {
+        r2::set_error("r2_densify_stats_batch: invalid argument (NULL array)");
+        return R2_ERR_INVALID;
+    }
+    r2::densify_stats_batch_kernel<<<dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(P, V, radii, dL_dmeans2D, grad_scale,
+                                                                                                max_radii2D, grad_accum, denom);
+    R2_STAGE_CHECK(0, (hipStream_t)stream, "batched densification statistics");
     return 0;
 }
 

@@ -26,10 +26,11 @@ __device__ __forceinline__ float load_or_zero(const float *__restrict__ p, int x
     return (x >= 0 && x < W && y >= 0 && y < H) ? p[(size_t)y * W + x] : 0.f;
 }
 
-// pass 1: SSIM map value + its three partial derivatives per pixel; per-block sums of S and |x - y|
-__global__ void __launch_bounds__(LT * LT) ssim_forward_kernel(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
-                                                                Window win, float *__restrict__ D /* [3][H][W] */,
-                                                                float2 *__restrict__ partial /* per block {sum S, sum |x-y|} */)
+// pass 1 of ONE view, by the block (blockIdx.x, blockIdx.y) of its tile grid: SSIM map value + its three partial derivatives
+// per pixel; per-block sums of S and |x - y|.  The single-view and the batched kernel both are this function.
+__device__ __forceinline__ void ssim_forward_view(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
+                                                  const Window &win, float *__restrict__ D /* [3][H][W] */,
+                                                  float2 *__restrict__ partial /* per block {sum S, sum |x-y|} */)
 {
     __shared__ float sx[LR][LR + 1], sy[LR][LR + 1];
     __shared__ float hb[5][LR][LT + 1];   // horizontally blurred x, y, x^2, y^2, xy
@@ -89,12 +90,10 @@ __global__ void __launch_bounds__(LT * LT) ssim_forward_kernel(int W, int H, con
     }
 }
 
-// pass 2: blur the three derivative maps, combine with x, y -> dL/dx; block 0 also folds the partial sums into the scalars
-__global__ void __launch_bounds__(LT * LT) ssim_backward_kernel(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
-                                                                 Window win, const float *__restrict__ D,
-                                                                 const float2 *__restrict__ partial, int nblocks, float w_l1,
-                                                                 float w_ssim, float *__restrict__ dL_dx,
-                                                                 float *__restrict__ scalars /* {l1 mean, ssim mean, loss} */)
+// pass 2 of ONE view: blur the three derivative maps, combine with x, y -> dL/dx with the weights (w_l1, w_ssim)
+__device__ __forceinline__ void ssim_backward_view(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
+                                                   const Window &win, const float *__restrict__ D, float w_l1, float w_ssim,
+                                                   float *__restrict__ dL_dx)
 {
     __shared__ float sd[3][LR][LR + 1];
     __shared__ float hb[3][LR][LT + 1];
@@ -132,19 +131,87 @@ __global__ void __launch_bounds__(LT * LT) ssim_backward_kernel(int W, int H, co
         const float invN = 1.0f / (float)N;
         dL_dx[o] = -w_ssim * invN * (b1 + 2.f * xv * b2 + yv * b3) + w_l1 * invN * sgn;
     }
-    if (blockIdx.x == 0 && blockIdx.y == 0) {   // fixed-order reduction of the per-block sums in double: deterministic scalars
-        __shared__ double red[LT * LT / 64][2];
-        double sS = 0.0, sA = 0.0;
-        for (int i = tid; i < nblocks; i += LT * LT) { const float2 q = partial[i]; sS += q.x; sA += q.y; }
+}
+
+// fixed-order reduction of ONE view's per-block sums in double, by a whole block: deterministic scalars {l1 mean, ssim mean,
+// loss}, returned to thread 0 (the other threads' return value is not meaningful).  A block that calls this more than once
+// puts a __syncthreads() between the calls (`red` is reused).
+__device__ __forceinline__ float3 ssim_fold_view(const float2 *__restrict__ partial, int nblocks, size_t N, float w_l1, float w_ssim)
+{
+    __shared__ double red[LT * LT / 64][2];
+    const int tid = threadIdx.x;
+    float3 out = make_float3(0.f, 0.f, 0.f);
+    double sS = 0.0, sA = 0.0;
+    for (int i = tid; i < nblocks; i += LT * LT) { const float2 q = partial[i]; sS += q.x; sA += q.y; }
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { sS += __shfl_xor(sS, d); sA += __shfl_xor(sA, d); }
-        if ((tid & 63) == 0) { red[tid >> 6][0] = sS; red[tid >> 6][1] = sA; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < LT * LT / 64; ++w) { red[0][0] += red[w][0]; red[0][1] += red[w][1]; }
-            const double l1 = red[0][1] / (double)N, ssim = red[0][0] / (double)N;
-            scalars[0] = (float)l1; scalars[1] = (float)ssim;
-            scalars[2] = (float)((double)w_l1 * l1 + (double)w_ssim * (1.0 - ssim));
+    for (int d = 32; d >= 1; d >>= 1) { sS += __shfl_xor(sS, d); sA += __shfl_xor(sA, d); }
+    if ((tid & 63) == 0) { red[tid >> 6][0] = sS; red[tid >> 6][1] = sA; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < LT * LT / 64; ++w) { red[0][0] += red[w][0]; red[0][1] += red[w][1]; }
+        const double l1 = red[0][1] / (double)N, ssim = red[0][0] / (double)N;
+        out = make_float3((float)l1, (float)ssim, (float)((double)w_l1 * l1 + (double)w_ssim * (1.0 - ssim)));
+    }
+    return out;
+}
+
+__global__ void __launch_bounds__(LT * LT) ssim_forward_kernel(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
+                                                                Window win, float *__restrict__ D, float2 *__restrict__ partial)
+{
+    ssim_forward_view(W, H, x, y, win, D, partial);
+}
+
+// block 0 also folds the partial sums into the scalars
+__global__ void __launch_bounds__(LT * LT) ssim_backward_kernel(int W, int H, const float *__restrict__ x, const float *__restrict__ y,
+                                                                 Window win, const float *__restrict__ D,
+                                                                 const float2 *__restrict__ partial, int nblocks, float w_l1,
+                                                                 float w_ssim, float *__restrict__ dL_dx,
+                                                                 float *__restrict__ scalars /* {l1 mean, ssim mean, loss} */)
+{
+    ssim_backward_view(W, H, x, y, win, D, w_l1, w_ssim, dL_dx);
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        const float3 r = ssim_fold_view(partial, nblocks, (size_t)W * H, w_l1, w_ssim);
+        if (threadIdx.x == 0) { scalars[0] = r.x; scalars[1] = r.y; scalars[2] = r.z; }
+    }
+}
+
+// ---- V views per launch: the view is the third grid dimension, every block runs the single-view code on its view.  The
+// images, derivative maps, partial sums, gradients and scalar rows of a launch's views are contiguous; the ground truths are
+// not, so their pointers travel by value, R2_LOSS_BATCH_CHUNK views per launch.
+struct GtChunk { const float *gt[R2_LOSS_BATCH_CHUNK]; };
+
+__global__ void __launch_bounds__(LT * LT) ssim_forward_batch_kernel(int W, int H, const float *__restrict__ x, GtChunk gts, Window win,
+                                                                      float *__restrict__ D, float2 *__restrict__ partial)
+{
+    const size_t v = blockIdx.z, N = (size_t)W * H;
+    ssim_forward_view(W, H, x + v * N, gts.gt[v], win, D + 3 * v * N, partial + v * (gridDim.x * gridDim.y));
+}
+
+// (w_l1, w_ssim) weigh the scalars' loss, (gw_l1, gw_ssim) the gradient.  n_all > 0 (the LAST launch of a call, whose views
+// complete the batch): block (0, 0, 0) then folds every view of the batch again, in view order, and writes the batch row:
+// the means of the float rows, summed in double.
+__global__ void __launch_bounds__(LT * LT) ssim_backward_batch_kernel(int W, int H, const float *__restrict__ x, GtChunk gts, Window win,
+                                                                       const float *__restrict__ D, const float2 *__restrict__ partial,
+                                                                       float w_l1, float w_ssim, float gw_l1, float gw_ssim,
+                                                                       float *__restrict__ dL_dx, float *__restrict__ scalars,
+                                                                       int n_all, const float2 *partial_all /* view 0's */,
+                                                                       float *batch_row /* scalars row n_all */)
+{
+    const size_t v = blockIdx.z, N = (size_t)W * H;
+    const int nblocks = gridDim.x * gridDim.y;
+    ssim_backward_view(W, H, x + v * N, gts.gt[v], win, D + 3 * v * N, gw_l1, gw_ssim, dL_dx + v * N);
+    if (blockIdx.x != 0 || blockIdx.y != 0) return;
+    const float3 mine = ssim_fold_view(partial + v * nblocks, nblocks, N, w_l1, w_ssim);
+    if (threadIdx.x == 0) { scalars[3 * v] = mine.x; scalars[3 * v + 1] = mine.y; scalars[3 * v + 2] = mine.z; }
+    if (n_all > 0 && v == 0) {
+        double l1 = 0.0, ssim = 0.0, loss = 0.0;
+        for (int u = 0; u < n_all; ++u) {
+            __syncthreads();
+            const float3 r = ssim_fold_view(partial_all + (size_t)u * nblocks, nblocks, N, w_l1, w_ssim);
+            l1 += (double)r.x; ssim += (double)r.y; loss += (double)r.z;
+        }
+        if (threadIdx.x == 0) {
+            batch_row[0] = (float)(l1 / n_all); batch_row[1] = (float)(ssim / n_all); batch_row[2] = (float)(loss / n_all);
         }
     }
 }
@@ -228,6 +295,57 @@ extern "C" int r2_loss_l1_ssim(int width, int height, const float *img, const fl
     ssim_forward_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, img, gt, win, D, partial);
     ssim_backward_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, img, gt, win, D, partial, nb, w_l1, w_ssim, dL_dimg, scalars);
     R2_STAGE_CHECK(0, s, "l1 + ssim loss");
+    return 0;
+}
+
+namespace {
+size_t ssim_blocks(int width, int height) { return (size_t)((width + r2::LT - 1) / r2::LT) * ((height + r2::LT - 1) / r2::LT); }
+// batched scratch: [V][3][H][W] derivative maps, then (8-byte aligned) [V][blocks] float2 partial sums
+size_t ssim_batch_partial_offset(int V, int width, int height) { return (3 * (size_t)V * width * height + 1) & ~(size_t)1; }
+}  // namespace
+
+extern "C" size_t r2_loss_l1_ssim_batch_scratch_floats(int V, int width, int height)
+{
+    if (V < 1 || width <= 0 || height <= 0) return 0;
+    return ssim_batch_partial_offset(V, width, height) + 2 * (size_t)V * ssim_blocks(width, height);
+}
+
+extern "C" int r2_loss_l1_ssim_batch(int V, int width, int height, const float *imgs, const float *const *gts_host, float w_l1,
+                                     float w_ssim, float *dL_dimg, float *scratch, float *scalars, void *stream)
+{
+    using namespace r2;
+    if (V < 1 || width <= 0 || height <= 0 || !imgs || !gts_host || !dL_dimg || !scratch || !scalars) {
+        set_error("r2_loss_l1_ssim_batch: invalid argument");
+        return R2_ERR_INVALID;
+    }
+    for (int v = 0; v < V; ++v)
+        if (!gts_host[v]) {
+            set_error("r2_loss_l1_ssim_batch: ground truth %d is NULL", v);
+            return R2_ERR_INVALID;
+        }
+    const size_t N = (size_t)width * height, nb = ssim_blocks(width, height);
+    const dim3 tiles((width + LT - 1) / LT, (height + LT - 1) / LT);
+    if (tiles.y > 65535u || nb > 0x7fffffffu || (size_t)V * nb > 0x7fffffffu) {   // grid limits; block counts are ints on the device
+        set_error("r2_loss_l1_ssim_batch: %d views of %d x %d exceed the grid", V, width, height);
+        return R2_ERR_INVALID;
+    }
+    float2 *partial = reinterpret_cast<float2 *>(scratch + ssim_batch_partial_offset(V, width, height));
+    const Window win = make_ssim_window();
+    const float gw_l1 = w_l1 / (float)V, gw_ssim = w_ssim / (float)V;
+    hipStream_t s = (hipStream_t)stream;
+    for (int v0 = 0; v0 < V; v0 += R2_LOSS_BATCH_CHUNK) {
+        const int nv = V - v0 < R2_LOSS_BATCH_CHUNK ? V - v0 : R2_LOSS_BATCH_CHUNK;
+        GtChunk gts;
+        for (int k = 0; k < R2_LOSS_BATCH_CHUNK; ++k) gts.gt[k] = k < nv ? gts_host[v0 + k] : nullptr;
+        const dim3 grid(tiles.x, tiles.y, nv);
+        const float *x = imgs + (size_t)v0 * N;
+        float *D = scratch + 3 * (size_t)v0 * N;
+        ssim_forward_batch_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, x, gts, win, D, partial + (size_t)v0 * nb);
+        ssim_backward_batch_kernel<<<grid, dim3(LT * LT), 0, s>>>(width, height, x, gts, win, D, partial + (size_t)v0 * nb, w_l1, w_ssim,
+                                                                 gw_l1, gw_ssim, dL_dimg + (size_t)v0 * N, scalars + 3 * (size_t)v0,
+                                                                 v0 + nv == V ? V : 0, partial, scalars + 3 * (size_t)V);
+    }
+    R2_STAGE_CHECK(0, s, "batched l1 + ssim loss");
     return 0;
 }
 

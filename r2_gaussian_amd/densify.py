@@ -32,6 +32,26 @@ def densification_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom):
     _lib.check(rc, "r2_densify_stats")
 
 
+def densification_stats_batch(radii, viewspace_grad, max_radii2D, grad_accum, denom, grad_scale=1.0):
+    """`densification_stats` of the V views of a batched render in ONE launch: radii [V, P] int32 and viewspace_grad [V, P, 3] as
+    GaussianRasterizerBatch leaves them.  Every view in order: for radii > 0: max_radii2D = max(., radii), grad_accum +=
+    grad_scale * ||viewspace_grad[v, :, :2]||, denom += 1; with grad_scale 1 bit-identical to V single-view calls.
+    grad_scale = V undoes the 1 / V a mean-over-views loss leaves in the gradients (exact for V a power of two)."""
+    _require_gpu(viewspace_grad, "viewspace_grad")
+    if radii.dim() != 2 or radii.shape[0] < 1:
+        raise ValueError("radii must be [V, P] with V >= 1, got %s" % (tuple(radii.shape),))
+    V, P = radii.shape
+    assert viewspace_grad.shape == (V, P, 3) and viewspace_grad.is_contiguous() and viewspace_grad.dtype == _F32
+    assert radii.dtype == torch.int32
+    for t in (max_radii2D, grad_accum, denom):
+        assert t.numel() == P and t.is_contiguous() and t.dtype == _F32
+    dev = viewspace_grad.device
+    with _on_device(dev):
+        rc = _lib.lib().r2_densify_stats_batch(P, V, radii.contiguous().data_ptr(), viewspace_grad.data_ptr(), float(grad_scale),
+                                               max_radii2D.data_ptr(), grad_accum.data_ptr(), denom.data_ptr(), _stream(dev))
+    _lib.check(rc, "r2_densify_stats_batch")
+
+
 def _ptrs(ts):
     arr = (C.c_void_p * 4)()
     for i, t in enumerate(ts):

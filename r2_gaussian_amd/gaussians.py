@@ -229,9 +229,16 @@ class GaussianModel:
             t.grad = None
 
     # ------------------------------------------------------------------------------------------------ density control
-    def add_densification_stats(self, radii, viewspace_grad):
-        """train.py:151-154 in one launch: max_radii2D, xyz_gradient_accum, denom of the visible Gaussians."""
-        D.densification_stats(radii, viewspace_grad, self.max_radii2D, self.xyz_gradient_accum, self.denom)
+    def add_densification_stats(self, radii, viewspace_grad, grad_scale=1.0):
+        """train.py:151-154 in one launch: max_radii2D, xyz_gradient_accum, denom of the visible Gaussians.  radii [P] and
+        viewspace_grad [P, 3] of one view, or [V, P] and [V, P, 3] of a batched render (the views in order, the gradient norms
+        times grad_scale: densify.densification_stats_batch)."""
+        if radii.dim() == 1 and grad_scale == 1.0:
+            D.densification_stats(radii, viewspace_grad, self.max_radii2D, self.xyz_gradient_accum, self.denom)
+            return
+        if radii.dim() == 1:
+            radii, viewspace_grad = radii[None], viewspace_grad[None]
+        D.densification_stats_batch(radii, viewspace_grad, self.max_radii2D, self.xyz_gradient_accum, self.denom, grad_scale)
 
     @torch.no_grad()
     def densify_and_prune(self, max_grad, min_density, max_screen_size, max_scale, max_num_gaussians, densify_scale_threshold,

@@ -4,6 +4,8 @@ autograd node whose forward already computes the gradient (two / one kernel laun
 vendor convolution).  The results are device scalars: nothing here synchronises with the host (train.py:204-209 calls
 ``.item()`` on every loss every iteration; read the tensors only when something is logged).
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -53,6 +55,67 @@ def image_loss(image, gt, lambda_dssim=0.25):
     """-> (loss, parts): loss = L1 + lambda_dssim * (1 - SSIM) as a device scalar with a gradient; parts = tensor
     {l1, ssim, loss} for logging (train.py:118-126)."""
     return _ImageLoss.apply(image, gt, 1.0, float(lambda_dssim))
+
+
+def _check_batch_shapes(images, gts):
+    """[V, H, W] projections and V ground truths: a sequence of [H, W] / [1, H, W] tensors or one [V, H, W] tensor."""
+    if not torch.is_tensor(images) or images.dim() != 3 or images.shape[0] < 1:
+        raise ValueError("images must be [V, H, W] with V >= 1, got %s" % (tuple(images.shape) if torch.is_tensor(images) else
+                                                                           type(images).__name__,))
+    V, hw = images.shape[0], tuple(images.shape[1:])
+    if torch.is_tensor(gts):
+        if gts.dim() != 3 or tuple(gts.shape) != (V,) + hw:
+            raise ValueError("gts is %s but the images are %s" % (tuple(gts.shape), tuple(images.shape)))
+        return
+    gts = list(gts)
+    if len(gts) != V:
+        raise ValueError("%d ground truths for %d images" % (len(gts), V))
+    for k, t in enumerate(gts):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1):
+            raise ValueError("gts[%d] must be [H, W] or [1, H, W], got %s" % (k, tuple(t.shape) if torch.is_tensor(t) else
+                                                                              type(t).__name__))
+        if tuple(t.shape[-2:]) != hw:
+            raise ValueError("gts[%d] is %s but the images are %s" % (k, tuple(t.shape[-2:]), hw))
+
+
+class _ImageLossBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, images, gts, w_l1, w_ssim):
+        _check_batch_shapes(images, gts)
+        _require_gpu(images, "images")
+        img = images.to(_F32).contiguous()
+        V, H, W = img.shape
+        # the ground truths are read where they lie; only one on another device / of another type / strided is converted
+        refs = list(gts.to(device=img.device, dtype=_F32).contiguous()) if torch.is_tensor(gts) else [
+            t.reshape(H, W).to(device=img.device, dtype=_F32).contiguous() for t in gts]
+        table = (C.c_void_p * V)(*[t.data_ptr() for t in refs])
+        L = _lib.lib()
+        grad = torch.empty_like(img)
+        scratch = torch.empty(L.r2_loss_l1_ssim_batch_scratch_floats(V, W, H), dtype=_F32, device=img.device)
+        scalars = torch.empty((V + 1, 3), dtype=_F32, device=img.device)
+        with _on_device(img.device):
+            rc = L.r2_loss_l1_ssim_batch(V, W, H, img.data_ptr(), table, float(w_l1), float(w_ssim), grad.data_ptr(),
+                                         scratch.data_ptr(), scalars.data_ptr(), _stream(img.device))
+        _lib.check(rc, "r2_loss_l1_ssim_batch")
+        ctx.save_for_backward(grad)
+        ctx.dtype = images.dtype
+        ctx.mark_non_differentiable(scalars)
+        return scalars[V, 2], scalars
+
+    @staticmethod
+    def backward(ctx, g, _):
+        (grad,) = ctx.saved_tensors
+        return (grad * g).to(ctx.dtype), None, None, None
+
+
+def image_loss_batch(images, gts, lambda_dssim=0.25):
+    """`image_loss` of V views in two launches per 16 views and ONE autograd node.  images [V, H, W]; gts: a sequence of V
+    tensors [H, W] / [1, H, W] (read in place: they need not be contiguous with each other) or one [V, H, W] tensor.
+    -> (loss, parts): loss = the mean over the views of L1 + lambda_dssim * (1 - SSIM), a device scalar with a gradient;
+    parts [V + 1, 3]: row v = {l1, ssim, loss} of view v, bit-identical to image_loss's, row V their means.  Shape errors
+    raise ValueError before the library is touched."""
+    _check_batch_shapes(images, gts)
+    return _ImageLossBatch.apply(images, gts if torch.is_tensor(gts) else list(gts), 1.0, float(lambda_dssim))
 
 
 class _TV3D(torch.autograd.Function):
