@@ -416,6 +416,36 @@ R2_API int r2_project_volume(int V, int H, int W, const float *rays /* [V,12] */
                              float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy, const float *vol /* [nx,ny,nz] */,
                              float *out /* [V,H,W] */, void *stream);
 
+/* r2_project_volume_siddon: the same rays, coordinates and arguments (no `accuracy`) with the Siddon ray-voxel intersection
+ * model: voxel (i,j,k) is the index-space cube [i - 1/2, i + 1/2]^3 with the constant value vol[i][j][k], the volume is
+ * [-1/2, n_a - 1/2] on each axis and zero outside, and out = the exact integral of that piecewise-constant function along
+ * the ray, in world length units.  With s, d the ray's start and direction (csrc/ray_sampling.hpp: pixel_ray), per axis
+ * rd_a = 1 / d_a (one rounded division) and, for the integer m = 0..n_a,
+ *     plane_t_a(m) = (((float)m - 1/2) - s_a) * rd_a          (plane m lies at q_a = m - 1/2),
+ * a fixed sequence of separately rounded float32 operations, monotone in m, never accumulated along the ray.  The clip to the
+ * volume is [t0, t1] = the intersection over the axes of the intervals between plane_t_a(0) and plane_t_a(n_a), with
+ * t0 = max(t0, 0) for a cone ray.  An axis is flat when d_a = 0 (or 1 / d_a overflows): it clips nothing, and the ray
+ * misses unless -1/2 <= s_a < n_a - 1/2.  A ray that misses, has t1 <= t0, has no direction at all or non-finite
+ * parameters writes exactly 0.  For the ray rho of a pixel and voxel v = (i, j, k) the matrix entry is
+ *     A[rho, v] = wlen * max(0, min(t1, min_a hi_a) - max(t0, max_a lo_a)),        wlen = |d (.) dVoxel|,
+ * lo_a, hi_a the smaller and larger of plane_t_a(m_a) and plane_t_a(m_a + 1) (m_a = i, j, k); a flat axis contributes
+ * (-inf, +inf) when m_a - 1/2 <= s_a < m_a + 1/2 and makes the entry 0 otherwise.  The forward walks the cells from t0 to
+ * t1 (per-axis integer plane counters, the axis with the smallest next plane_t advances, ties in the order x, y, z, the
+ * cell index moves by integer steps) and adds (t_next - t_cur) * vol[cell] segment by segment in order in one thread, then
+ * scales the sum by wlen once; the interval it spends in v is the one above.  No atomics, no allocation, no host
+ * synchronisation; bit-reproducible, and a view's output does not depend on the other views of the call.  Limits as
+ * r2_project_volume.
+ * r2_backproject_volume_siddon: vol = A^T projs for that A: vol[v] = sum over the views in order, and over the pixels of
+ * a view in row-major order, of A[rho, v] projs[rho], with entries bit-identical to the forward's (csrc/siddon_ray.hpp is
+ * shared); only the products and sums round differently.  Voxel-driven: no atomics, no workspace; bit-reproducible, `vol`
+ * is overwritten, and a cone source anywhere, inside the volume included, is handled.  Limits as r2_backproject_volume. */
+R2_API int r2_project_volume_siddon(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                                    float dVoxel_x, float dVoxel_y, float dVoxel_z, const float *vol /* [nx,ny,nz] */,
+                                    float *out /* [V,H,W] */, void *stream);
+R2_API int r2_backproject_volume_siddon(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                                        float dVoxel_x, float dVoxel_y, float dVoxel_z, const float *projs /* [V,H,W] */,
+                                        float *vol /* [nx,ny,nz] */, void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -73,6 +73,8 @@ _SIGNATURES = {
     "r2_fdk_backproject": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _fp, _p]),
     "r2_project_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
     "r2_backproject_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
+    "r2_project_volume_siddon": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _p]),
+    "r2_backproject_volume_siddon": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _p]),
     "r2_tv_descent_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),

@@ -47,6 +47,8 @@ SOURCES = {
     "fdk.hip": FAST,
     "projector.hip": EXACT,
     "backprojector.hip": EXACT,
+    "projector_siddon.hip": EXACT,
+    "backprojector_siddon.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

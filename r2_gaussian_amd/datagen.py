@@ -2,7 +2,7 @@
 projector of projector.py.
 
     python -m r2_gaussian_amd.datagen --vol vol.npy --scanner cone_beam.yml --output data/case_dir [--n_train 50]
-                                      [--n_test 100] [--seed 0]
+                                      [--n_test 100] [--seed 0] [--projection_type interpolated|siddon]
 
 writes ``{output}/{vol_name}_{mode}/`` with ``vol_gt.npy``, ``proj_train/proj_train_%04d.npy``,
 ``proj_test/proj_test_%04d.npy`` (float32 [H, W], the rasterizer's row order) and ``meta_data.json`` (keys scanner, vol,
@@ -12,7 +12,8 @@ Training angles are linspace(0, totalAngle, n_train + 1)[:-1] + startAngle, test
 (radians; the config's angles are degrees).  With ``noise: true`` the training stack gets ``add_noise`` (TIGRE's
 ``CTnoise.add``) and its negatives are clipped to 0; test projections stay noise-free.  Every draw comes from one explicit
 ``numpy.random.RandomState`` (``--seed``), so a seed reproduces a dataset bit for bit -- the reference draws from numpy's
-global generator.
+global generator.  ``--projection_type siddon`` projects with the ray-voxel intersection model instead of the interpolated
+one; a case made with a model named explicitly records it as ``projection_type`` in its saved scanner config.
 """
 import argparse
 import json
@@ -78,15 +79,25 @@ def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles
     return meta
 
 
-def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda"):
+def recorded_projection_type(cfg):
+    """The projector model a saved scanner config records ("interpolated" for a case that records none)."""
+    return P.check_projection_type(cfg.get("projection_type", "interpolated"))
+
+
+def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda", projection_type=None):
     """Project ``vol`` [nx,ny,nz] with the raw scanner config ``cfg`` and write the case ``{output}/{vol_name}_{mode}``;
-    -> the case directory."""
+    -> the case directory.  ``projection_type``: "interpolated" or "siddon", written into the case's saved scanner config;
+    None takes the config's own ``projection_type`` ("interpolated" if absent) and saves the config as it is."""
+    if projection_type is None:
+        projection_type = recorded_projection_type(cfg)
+    else:
+        cfg = dict(cfg, projection_type=P.check_projection_type(projection_type))
     rng = np.random.RandomState(seed)
     vol = np.asarray(vol, dtype=np.float32)
     train_angles, test_angles = angles_for(cfg, n_train, n_test, rng)
-    train = P.project(vol, train_angles, cfg, device=device).cpu().numpy()
+    train = P.project(vol, train_angles, cfg, device=device, projection_type=projection_type).cpu().numpy()
     train = noisy_train(train, cfg, rng)
-    test = P.project(vol, test_angles, cfg, device=device).cpu().numpy()
+    test = P.project(vol, test_angles, cfg, device=device, projection_type=projection_type).cpu().numpy()
     case_dir = osp.join(output, "%s_%s" % (vol_name, cfg["mode"]))
     write_case(case_dir, cfg, vol, train, train_angles, test, test_angles)
     return case_dir
@@ -101,13 +112,16 @@ def main(argv=None):
     ap.add_argument("--n_train", default=50, type=int, help="Number of projections for training.")
     ap.add_argument("--n_test", default=100, type=int, help="Number of projections for evaluation.")
     ap.add_argument("--seed", default=0, type=int, help="Seed of every random draw (test angles, noise).")
+    ap.add_argument("--projection_type", default=None, choices=P.PROJECTION_TYPES,
+                    help="Projector model (default: the scanner configuration's, else interpolated).")
     args = ap.parse_args(argv)
     import yaml
     with open(args.scanner, "r") as f:
         cfg = yaml.safe_load(f)
     vol_name = osp.basename(args.vol)[:-4]
     print("Generate data for case %s_%s" % (vol_name, cfg["mode"]))
-    case_dir = generate(np.load(args.vol), cfg, args.output, vol_name, args.n_train, args.n_test, args.seed)
+    case_dir = generate(np.load(args.vol), cfg, args.output, vol_name, args.n_train, args.n_test, args.seed,
+                        projection_type=args.projection_type)
     print("Generate data for case %s complete!" % osp.basename(case_dir))
     return case_dir
 

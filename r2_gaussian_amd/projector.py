@@ -14,6 +14,9 @@ construction -- the forward half of what fdk.py does for the back-projection.  P
 
 The integrand is the trilinear interpolant of the volume (zero outside it), sampled at the midpoints of
 n = max(1, ceil(L / accuracy)) equal pieces of the clipped chord (include/r2hip.h, r2_project_volume, states the contract).
+That is ``projection_type="interpolated"``, the default.  ``projection_type="siddon"`` takes the ray-voxel intersection model
+instead (csrc/projector_siddon.hip, ``r2_project_volume_siddon``): the exact integral of the piecewise-constant volume, voxel
+(i,j,k) being a cube of constant value; it has no ``accuracy``.
 """
 import numpy as np
 import torch
@@ -23,6 +26,14 @@ from . import scene as S
 from ._C import _on_device, _require_gpu, _stream
 
 _F32 = torch.float32
+PROJECTION_TYPES = ("interpolated", "siddon")
+
+
+def check_projection_type(projection_type):
+    """-> ``projection_type``, or ValueError for anything but the two models."""
+    if projection_type not in PROJECTION_TYPES:
+        raise ValueError("projection_type must be one of %s, got %r" % (PROJECTION_TYPES, projection_type))
+    return projection_type
 
 
 def ray_params(views, sVoxel, center, nVoxel):
@@ -53,15 +64,16 @@ def ray_params(views, sVoxel, center, nVoxel):
     return out.astype(np.float32)
 
 
-def project_views(vol, views, sVoxel, center, accuracy=0.5, out=None):
+def project_views(vol, views, sVoxel, center, accuracy=0.5, out=None, projection_type="interpolated"):
     """Line integrals of ``vol`` [nx,ny,nz] (GPU, the query() / voxelizer layout) along the rays of every pixel of ``views``
     (``scene.View`` list, one detector size): a GPU tensor [V,H,W] in scene units.  ``sVoxel`` / ``center``: the volume's
     extent and centre in the views' (scene) units.  No host synchronisation; ``out`` may be a preallocated [V,H,W] float32
-    contiguous GPU tensor."""
+    contiguous GPU tensor.  ``projection_type``: "interpolated" or "siddon" (which ignores ``accuracy``)."""
+    check_projection_type(projection_type)
     _require_gpu(vol, "vol")
     if vol.dim() != 3:
         raise ValueError("vol must be a 3D array [nx,ny,nz], got shape %s" % (tuple(vol.shape),))
-    if not accuracy > 0:
+    if projection_type == "interpolated" and not accuracy > 0:
         raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
     views = list(views)
     if not views:
@@ -85,17 +97,23 @@ def project_views(vol, views, sVoxel, center, accuracy=0.5, out=None):
     d = [float(s) / n for s, n in zip(sVoxel, (nx, ny, nz))]
     L = _lib.lib()
     with _on_device(v32.device):
-        rc = L.r2_project_volume(V, H, W, rays.data_ptr(), int(views[0].mode == 1), nx, ny, nz, d[0], d[1], d[2],
-                                 float(accuracy), v32.data_ptr(), out.data_ptr(), _stream(v32.device))
-    _lib.check(rc, "r2_project_volume")
+        if projection_type == "siddon":
+            rc = L.r2_project_volume_siddon(V, H, W, rays.data_ptr(), int(views[0].mode == 1), nx, ny, nz, d[0], d[1], d[2],
+                                            v32.data_ptr(), out.data_ptr(), _stream(v32.device))
+        else:
+            rc = L.r2_project_volume(V, H, W, rays.data_ptr(), int(views[0].mode == 1), nx, ny, nz, d[0], d[1], d[2],
+                                     float(accuracy), v32.data_ptr(), out.data_ptr(), _stream(v32.device))
+    _lib.check(rc, "r2_project_volume_siddon" if projection_type == "siddon" else "r2_project_volume")
     return out
 
 
-def project(vol, angles, scanner_cfg, accuracy=None, device="cuda"):
+def project(vol, angles, scanner_cfg, accuracy=None, device="cuda", projection_type="interpolated"):
     """``tigre.Ax(vol, geo, angles)[:, ::-1, :]`` as generate_data.py saves it: projections [V,H,W] (GPU tensor) of ``vol``
     [nx,ny,nz] at ``angles`` (radians) with the raw, unscaled scanner config (mode, DSD, DSO, nDetector [v, u], sDetector,
     sVoxel, offOrigin, accuracy), in the config's length units -- what dataset_readers.py:129 later multiplies by
-    scene_scale.  Rows come in the rasterizer's order.  ``accuracy``: None takes the config's ``accuracy`` (0.5 if absent)."""
+    scene_scale.  Rows come in the rasterizer's order.  ``accuracy``: None takes the config's ``accuracy`` (0.5 if absent).
+    ``projection_type``: "interpolated" or "siddon" (which ignores ``accuracy``)."""
+    check_projection_type(projection_type)
     cfg = scanner_cfg
     v = torch.as_tensor(np.ascontiguousarray(vol) if isinstance(vol, np.ndarray) else vol)
     if v.dim() != 3:
@@ -103,12 +121,13 @@ def project(vol, angles, scanner_cfg, accuracy=None, device="cuda"):
     if tuple(int(n) for n in cfg["nVoxel"]) != tuple(v.shape):
         raise ValueError("vol shape %s differs from the config's nVoxel %s" % (tuple(v.shape), list(cfg["nVoxel"])))
     acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
-    if not acc > 0:
+    if projection_type == "interpolated" and not acc > 0:
         raise ValueError("accuracy must be > 0, got %r" % (acc,))
     if not v.is_cuda:
         v = v.to(device)
     scale = 2.0 / max(cfg["sVoxel"])   # make_view works in the normalised scene (dataset_readers.py:62-76)
     H, W = (int(n) for n in cfg["nDetector"])
     views = [S.make_view(float(a), (H, W), cfg) for a in np.asarray(angles, dtype=np.float64).reshape(-1)]
-    out = project_views(v, views, [s * scale for s in cfg["sVoxel"]], [o * scale for o in cfg["offOrigin"]], acc)
+    out = project_views(v, views, [s * scale for s in cfg["sVoxel"]], [o * scale for o in cfg["offOrigin"]], acc,
+                        projection_type=projection_type)
     return out.mul_(1.0 / scale)

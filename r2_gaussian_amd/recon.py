@@ -3,7 +3,9 @@ the reference's ``run_ct_recon_algs`` (r2_gaussian/utils/ct_utils.py:60-215) and
 
 They stand on two MI355X kernels behind the C ABI: the forward projector ``r2_project_volume`` (``A``, projector.py) and its
 exact transpose ``r2_backproject_volume`` (``A^T``, csrc/backprojector.hip), plus ``r2_tv_descent`` (csrc/tv_descent.hip) for
-the TV steps of ASD-POCS.  The vector updates between them are elementwise tensor operations; every data-dependent scalar
+the TV steps of ASD-POCS.  ``projection_type="siddon"`` swaps the pair for the ray-voxel intersection model,
+``r2_project_volume_siddon`` and its exact transpose ``r2_backproject_volume_siddon`` (csrc/backprojector_siddon.hip); the
+default everywhere is ``"interpolated"``.  The vector updates between them are elementwise tensor operations; every data-dependent scalar
 stays a 0-d device tensor, so an iteration makes no host synchronisation unless ``computel2`` or ``verbose`` asks for one.
 
 Conventions are those of ``projector.project`` and ``fdk.fdk``: the raw scanner config and its length units, projections
@@ -42,26 +44,36 @@ METHODS = ("fdk", "sart", "ossart", "asd_pocs", "os_asd_pocs", "cgls")
 
 # ---- the adjoint ----------------------------------------------------------------------------------------------------------
 
-def _backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy, out):
+def _backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy, out, projection_type="interpolated"):
     V, H, W = projs.shape
     nx, ny, nz = nVoxel
     L = _lib.lib()
     with _on_device(projs.device):
-        rc = L.r2_backproject_volume(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]), float(dVoxel[1]),
-                                     float(dVoxel[2]), float(accuracy), projs.data_ptr(), out.data_ptr(),
-                                     _stream(projs.device))
-    _lib.check(rc, "r2_backproject_volume")
+        if projection_type == "siddon":
+            rc = L.r2_backproject_volume_siddon(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
+                                                float(dVoxel[1]), float(dVoxel[2]), projs.data_ptr(), out.data_ptr(),
+                                                _stream(projs.device))
+        else:
+            rc = L.r2_backproject_volume(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]), float(dVoxel[1]),
+                                         float(dVoxel[2]), float(accuracy), projs.data_ptr(), out.data_ptr(),
+                                         _stream(projs.device))
+    _lib.check(rc, "r2_backproject_volume_siddon" if projection_type == "siddon" else "r2_backproject_volume")
     return out
 
 
-def _project_rays(vol, rays, cone, H, W, dVoxel, accuracy, out):
+def _project_rays(vol, rays, cone, H, W, dVoxel, accuracy, out, projection_type="interpolated"):
     nx, ny, nz = vol.shape
     L = _lib.lib()
     with _on_device(vol.device):
-        rc = L.r2_project_volume(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
-                                 float(dVoxel[1]), float(dVoxel[2]), float(accuracy), vol.data_ptr(), out.data_ptr(),
-                                 _stream(vol.device))
-    _lib.check(rc, "r2_project_volume")
+        if projection_type == "siddon":
+            rc = L.r2_project_volume_siddon(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
+                                            float(dVoxel[1]), float(dVoxel[2]), vol.data_ptr(), out.data_ptr(),
+                                            _stream(vol.device))
+        else:
+            rc = L.r2_project_volume(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
+                                     float(dVoxel[1]), float(dVoxel[2]), float(accuracy), vol.data_ptr(), out.data_ptr(),
+                                     _stream(vol.device))
+    _lib.check(rc, "r2_project_volume_siddon" if projection_type == "siddon" else "r2_project_volume")
     return out
 
 
@@ -77,14 +89,15 @@ def _check_views(views):
     return views, H, W
 
 
-def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVoxel=None):
+def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVoxel=None, projection_type="interpolated"):
     """The exact transpose of ``projector.project_views``: vol [nx,ny,nz] (GPU) = A^T projs for projections [V,H,W] (GPU,
     float32) of ``views`` (scene units).  The volume's shape comes from ``out`` (a contiguous float32 GPU tensor, overwritten)
-    or ``nVoxel``.  No host synchronisation."""
+    or ``nVoxel``.  No host synchronisation.  ``projection_type`` as in ``project_views``."""
+    P.check_projection_type(projection_type)
     _require_gpu(projs, "projs")
     if projs.dim() != 3:
         raise ValueError("projs must be [V,H,W], got shape %s" % (tuple(projs.shape),))
-    if not accuracy > 0:
+    if projection_type == "interpolated" and not accuracy > 0:
         raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
     views, H, W = _check_views(views)
     if tuple(projs.shape) != (len(views), H, W):
@@ -102,19 +115,21 @@ def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVox
     nv = tuple(out.shape)
     rays = torch.from_numpy(P.ray_params(views, sVoxel, center, nv)).pin_memory().to(p32.device, non_blocking=True)
     d = [float(s) / n for s, n in zip(sVoxel, nv)]
-    return _backproject_rays(p32, rays, views[0].mode == 1, nv, d, accuracy, out)
+    return _backproject_rays(p32, rays, views[0].mode == 1, nv, d, accuracy, out, projection_type)
 
 
 # ---- the operator pair in config units --------------------------------------------------------------------------------------
 
 class Operator:
     """A = ``project(., angles, cfg)`` and its transpose on one device, with the rays computed once: ``A(x, v0, v1)`` projects
-    views v0..v1-1, ``At(p, v0, v1)`` back-projects them."""
+    views v0..v1-1, ``At(p, v0, v1)`` back-projects them.  ``projection_type``: "interpolated" or "siddon" (which ignores
+    ``accuracy``), the model of both."""
 
-    def __init__(self, angles, cfg, accuracy=None, device="cuda"):
+    def __init__(self, angles, cfg, accuracy=None, device="cuda", projection_type="interpolated"):
+        self.projection_type = P.check_projection_type(projection_type)
         self.cfg = cfg
         acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
-        if not acc > 0:
+        if projection_type == "interpolated" and not acc > 0:
             raise ValueError("accuracy must be > 0, got %r" % (acc,))
         self.accuracy = float(acc)
         self.device = torch.device(device)
@@ -141,7 +156,7 @@ class Operator:
             raise ValueError("volume shape %s differs from the config's nVoxel %s" % (tuple(x.shape), self.nVoxel))
         if out is None:
             out = torch.empty((v1 - v0, self.H, self.W), dtype=_F32, device=self.device)
-        _project_rays(x, self.rays[v0:v1], self.cone, self.H, self.W, self.dVoxel, self.accuracy, out)
+        _project_rays(x, self.rays[v0:v1], self.cone, self.H, self.W, self.dVoxel, self.accuracy, out, self.projection_type)
         return out.mul_(self.inv_scale)
 
     def At(self, p, v0=0, v1=None, out=None):
@@ -150,7 +165,8 @@ class Operator:
             raise ValueError("projections %s are not views %d..%d of [%d,%d]" % (tuple(p.shape), v0, v1 - 1, self.H, self.W))
         if out is None:
             out = torch.empty(self.nVoxel, dtype=_F32, device=self.device)
-        _backproject_rays(p, self.rays[v0:v1], self.cone, self.nVoxel, self.dVoxel, self.accuracy, out)
+        _backproject_rays(p, self.rays[v0:v1], self.cone, self.nVoxel, self.dVoxel, self.accuracy, out,
+                          self.projection_type)
         return out.mul_(self.inv_scale)
 
 
@@ -166,10 +182,10 @@ def _projections(projs, op):
     return p.to(device=op.device, dtype=_F32, non_blocking=True).contiguous()
 
 
-def backproject(projs, angles, scanner_cfg, accuracy=None, device="cuda"):
+def backproject(projs, angles, scanner_cfg, accuracy=None, device="cuda", projection_type="interpolated"):
     """The transpose of ``projector.project``: vol [nx,ny,nz] (GPU tensor) = A^T projs for projections [V,H,W] at ``angles``
     with the raw scanner config, including ``project``'s 1 / scale."""
-    op = Operator(angles, scanner_cfg, accuracy, device)
+    op = Operator(angles, scanner_cfg, accuracy, device, projection_type)
     return op.At(_projections(projs, op))
 
 
@@ -179,10 +195,10 @@ def _sq(t):
 
 # ---- CGLS -----------------------------------------------------------------------------------------------------------------
 
-def cgls(projs, angles, cfg, niter=60, computel2=False, accuracy=None, device="cuda"):
+def cgls(projs, angles, cfg, niter=60, computel2=False, accuracy=None, device="cuda", projection_type="interpolated"):
     """CGLS from x0 = 0: ``niter`` iterations on |A x - b|_2.  -> x [nx,ny,nz] (GPU), or (x, l2) with computel2, l2 the
     residual norms |b - A x_k| after each iteration (a host list: one synchronisation per iteration)."""
-    op = Operator(angles, cfg, accuracy, device)
+    op = Operator(angles, cfg, accuracy, device, projection_type)
     b = _projections(projs, op)
     if int(niter) < 0:
         raise ValueError("niter must be >= 0")
@@ -244,10 +260,10 @@ class _Sart:
 
 
 def ossart(projs, angles, cfg, niter=20, blocksize=10, lmbda=1.0, lmbda_red=0.999, init=None, nonneg=True, computel2=False,
-           accuracy=None, device="cuda"):
+           accuracy=None, device="cuda", projection_type="interpolated"):
     """OS-SART: ``niter`` sweeps over blocks of ``blocksize`` consecutive views (input order).  -> x (GPU), or (x, l2) with
     computel2 (|A x - b|_2 after each sweep; one synchronisation per sweep)."""
-    op = Operator(angles, cfg, accuracy, device)
+    op = Operator(angles, cfg, accuracy, device, projection_type)
     b = _projections(projs, op)
     st = _Sart(op, blocksize)
     x = _init(init, op)
@@ -262,9 +278,10 @@ def ossart(projs, angles, cfg, niter=20, blocksize=10, lmbda=1.0, lmbda_red=0.99
 
 
 def sart(projs, angles, cfg, niter=20, lmbda=1.0, lmbda_red=0.999, init=None, nonneg=True, computel2=False, accuracy=None,
-         device="cuda"):
+         device="cuda", projection_type="interpolated"):
     """SART: OS-SART with one view per block."""
-    return ossart(projs, angles, cfg, niter, 1, lmbda, lmbda_red, init, nonneg, computel2, accuracy, device)
+    return ossart(projs, angles, cfg, niter, 1, lmbda, lmbda_red, init, nonneg, computel2, accuracy, device,
+                  projection_type)
 
 
 def _init(init, op):
@@ -302,16 +319,16 @@ def tv_descent(vol, step, n_iter, scratch=None):
     return vol
 
 
-def maxl2err_default(projs, angles, cfg, device="cuda"):
+def maxl2err_default(projs, angles, cfg, device="cuda", projection_type="interpolated"):
     """The reference's ASD-POCS tolerance: 0.15 |A fdk(b) - b|_2 (a 0-d device tensor)."""
-    op = Operator(angles, cfg, None, device)
+    op = Operator(angles, cfg, None, device, projection_type)
     b = _projections(projs, op)
     return 0.15 * torch.linalg.vector_norm(op.A(F.fdk(b, angles, cfg, device=device)) - b, dtype=_F64)
 
 
 def os_asd_pocs(projs, angles, cfg, niter=10, blocksize=10, tviter=20, maxl2err=None, alpha=0.002, lmbda=1.0,
                 lmbda_red=0.9999, alpha_red=0.95, rmax=0.94, init=None, verbose=False, accuracy=None, device="cuda",
-                return_trace=False):
+                return_trace=False, projection_type="interpolated"):
     """OS-ASD-POCS (Sidky & Pan 2008, with OS-SART as the data step; ASD-POCS is blocksize 1).  Each iteration:
 
     1. x_prev = x; one (OS-)SART sweep with the current lambda, clipped to x >= 0; x_sart = x.
@@ -324,11 +341,11 @@ def os_asd_pocs(projs, angles, cfg, niter=10, blocksize=10, tviter=20, maxl2err=
     ``maxl2err`` None: 0.15 |A fdk(b) - b|_2.  The stop test is kept on the device: once it holds, later iterations leave x
     as it is, so no iteration waits for the host unless ``verbose``.  -> x (GPU); with return_trace also a dict of per-
     iteration device tensors (dd, dp, dg, dtvg, reduced, c, active, sart_min = min x_sart)."""
-    op = Operator(angles, cfg, accuracy, device)
+    op = Operator(angles, cfg, accuracy, device, projection_type)
     b = _projections(projs, op)
     st = _Sart(op, blocksize)
     if maxl2err is None:
-        maxl2err = maxl2err_default(b, angles, cfg, device)
+        maxl2err = maxl2err_default(b, angles, cfg, device, projection_type)
     eps = (maxl2err.to(device=op.device, dtype=_F64) if isinstance(maxl2err, torch.Tensor)
            else torch.full((), float(maxl2err), dtype=_F64, device=op.device))
     x = _init(init, op)
@@ -364,28 +381,31 @@ def os_asd_pocs(projs, angles, cfg, niter=10, blocksize=10, tviter=20, maxl2err=
 
 
 def asd_pocs(projs, angles, cfg, niter=10, tviter=20, maxl2err=None, alpha=0.002, lmbda=1.0, lmbda_red=0.9999,
-             alpha_red=0.95, rmax=0.94, init=None, verbose=False, accuracy=None, device="cuda", return_trace=False):
+             alpha_red=0.95, rmax=0.94, init=None, verbose=False, accuracy=None, device="cuda", return_trace=False,
+             projection_type="interpolated"):
     """ASD-POCS: ``os_asd_pocs`` with one view per block (SART as the data step)."""
     return os_asd_pocs(projs, angles, cfg, niter, 1, tviter, maxl2err, alpha, lmbda, lmbda_red, alpha_red, rmax, init,
-                       verbose, accuracy, device, return_trace)
+                       verbose, accuracy, device, return_trace, projection_type)
 
 
 # ---- the reference's entry points -------------------------------------------------------------------------------------------
 
-def reconstruct(projs, angles, cfg, method, device="cuda"):
-    """One of METHODS with the parameters ct_utils.py:60-175 passes -> x [nx,ny,nz] (GPU)."""
+def reconstruct(projs, angles, cfg, method, device="cuda", projection_type="interpolated"):
+    """One of METHODS with the parameters ct_utils.py:60-175 passes -> x [nx,ny,nz] (GPU).  ``projection_type``: the model
+    of the iterative methods' operator pair (FDK has none)."""
+    pt = P.check_projection_type(projection_type)
     if method == "fdk":
         return F.fdk(projs, angles, cfg, device=device)
     if method == "sart":
-        return sart(projs, angles, cfg, 20, 1.0, 0.999, device=device)
+        return sart(projs, angles, cfg, 20, 1.0, 0.999, device=device, projection_type=pt)
     if method == "ossart":
-        return ossart(projs, angles, cfg, 20, 10, 1.0, 0.999, device=device)
+        return ossart(projs, angles, cfg, 20, 10, 1.0, 0.999, device=device, projection_type=pt)
     if method == "asd_pocs":
-        return asd_pocs(projs, angles, cfg, 10, device=device)
+        return asd_pocs(projs, angles, cfg, 10, device=device, projection_type=pt)
     if method == "os_asd_pocs":
-        return os_asd_pocs(projs, angles, cfg, 10, 10, device=device)
+        return os_asd_pocs(projs, angles, cfg, 10, 10, device=device, projection_type=pt)
     if method == "cgls":
-        return cgls(projs, angles, cfg, 60, device=device)
+        return cgls(projs, angles, cfg, 60, device=device, projection_type=pt)
     raise NotImplementedError("Unsupported reconstruction method!")
 
 
@@ -396,7 +416,7 @@ def recon_volume(projs, angles, scanner_cfg, recon_method="fdk"):
     return reconstruct(projs, angles, scanner_cfg, recon_method).cpu().numpy()
 
 
-def run_ct_recon_algs(projs, angles, cfg, ct_gt, save_path, method):
+def run_ct_recon_algs(projs, angles, cfg, ct_gt, save_path, method, projection_type="interpolated"):
     """ct_utils.py:60-215: reconstruct with ``method``, evaluate against ``ct_gt`` [nx,ny,nz] with ``metrics.metric_vol``, and
     write ``{save_path}/{method}/``: ct_gt.npy, ct_pred.npy, eval_3d.yml and slice_{method}/{i:05d}_gt.png / _pred.png
     (z slices).  -> (report, ct_pred, ct_gt), numpy volumes."""
@@ -406,13 +426,14 @@ def run_ct_recon_algs(projs, angles, cfg, ct_gt, save_path, method):
     import yaml
     from .metrics import metric_vol
     print("Run {}...".format(method))
+    P.check_projection_type(projection_type)
     if method not in METHODS:
         raise NotImplementedError("Unsupported reconstruction method!")
     save_path = osp.join(save_path, method)
     slice_save_path = osp.join(save_path, "slice_{}".format(method))
     os.makedirs(slice_save_path, exist_ok=True)
     start = time.time()
-    ct_pred = reconstruct(projs, angles, cfg, method).cpu().numpy()
+    ct_pred = reconstruct(projs, angles, cfg, method, projection_type=projection_type).cpu().numpy()
     duration = time.time() - start
     ct_gt = np.asarray(ct_gt, dtype=np.float32)
     psnr_3d, _ = metric_vol(ct_gt, ct_pred, "psnr")
@@ -446,11 +467,13 @@ def _read_case(case_dir):
     return out
 
 
-def run_traditional_methods(source_path, model_path, methods=("fdk", "sart", "asd_pocs")):
+def run_traditional_methods(source_path, model_path, methods=("fdk", "sart", "asd_pocs"), projection_type="interpolated"):
     """scripts/run_traditional_methods.py for a case in datagen's layout: every method's reconstruction and report, and its
     test-view projections ``{model_path}/{method}/projs/{i:05d}_render.npy/.png`` next to ``_gt.npy/.png``.  Like the
     reference (which reads them through Scene), the saved projections are in the normalised scene's units (times
-    scene_scale).  -> the dict written to ``{model_path}/eval_3d.yml``."""
+    scene_scale).  ``projection_type``: the model of the reconstructions and of the test-view projections.  -> the dict
+    written to ``{model_path}/eval_3d.yml``."""
+    P.check_projection_type(projection_type)
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
@@ -462,8 +485,8 @@ def run_traditional_methods(source_path, model_path, methods=("fdk", "sart", "as
     print("Run traditional algorithms on {}".format(osp.basename(osp.normpath(source_path))))
     out = {}
     for method in methods:
-        out[method], ct_pred, _ = run_ct_recon_algs(projs, angles, cfg, case["vol"], model_path, method)
-        render = (P.project(ct_pred, test_angles, cfg) * scale).cpu().numpy()
+        out[method], ct_pred, _ = run_ct_recon_algs(projs, angles, cfg, case["vol"], model_path, method, projection_type)
+        render = (P.project(ct_pred, test_angles, cfg, projection_type=projection_type) * scale).cpu().numpy()
         gt = test_projs * np.float32(scale)
         proj_save_path = osp.join(model_path, method, "projs")
         os.makedirs(proj_save_path, exist_ok=True)
@@ -482,8 +505,10 @@ def main(argv=None):
     ap.add_argument("-s", "--source_path", required=True, help="case directory as datagen writes it")
     ap.add_argument("-m", "--model_path", required=True, help="output directory")
     ap.add_argument("--methods", nargs="+", default=["fdk", "sart", "asd_pocs"], choices=METHODS)
+    ap.add_argument("--projection_type", default="interpolated", choices=P.PROJECTION_TYPES,
+                    help="projector model of the iterative methods and of the test-view projections")
     a = ap.parse_args(argv)
-    run_traditional_methods(a.source_path, a.model_path, a.methods)
+    run_traditional_methods(a.source_path, a.model_path, a.methods, a.projection_type)
 
 
 if __name__ == "__main__":
