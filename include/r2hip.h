@@ -446,6 +446,49 @@ R2_API int r2_backproject_volume_siddon(int V, int H, int W, const float *rays /
                                         float dVoxel_x, float dVoxel_y, float dVoxel_z, const float *projs /* [V,H,W] */,
                                         float *vol /* [nx,ny,nz] */, void *stream);
 
+/* ---- exact projection of the Gaussian model itself (no counterpart in the reference, whose only Gaussian renderer is the
+ * splatting rasterizer: affine at each centre, cut at 3 sigma, culled at the near plane) -------------------------------------
+ * r2_project_gaussians: out[V][H][W] = the sum over the P Gaussians of the exact integral of rho exp(-x^T Sigma^-1 x / 2)
+ * along the ray of every detector pixel.  Everything is in world (scene) coordinates; rays[V][12] = {a, p00, pu, pv} as for
+ * r2_project_volume, read by the same pixel_ray (csrc/ray_sampling.hpp): cone != 0: start s = a, direction d = P - a with
+ * P = p00 + c pu + r pv; cone == 0: s = P, d = a.  d is not normalised.
+ * One (Gaussian, ray) pair: mean mu, density rho, sigma = scale_modifier * scales (3), quaternion (r, x, y, z) used AS IT
+ * COMES (not normalised; the rasterizer's quat_to_rot), R its matrix, Sigma = R S^2 R^T.  With
+ *     u = S^-1 R^T d,   w = S^-1 R^T (s - mu),   A = u.u,   B = u.w,   wp = w - (B / A) u,   q = wp.wp,   t* = -B / A,
+ *     term = rho sqrt(2 pi / A) exp(-q / 2) |d|,
+ * the integral over the WHOLE line.  q is computed from wp, never as w.w - B^2 / A (which cancels when the source is far and
+ * sigma small).  For a cone ray a pair with t* <= 0 (closest approach at or behind the source) contributes exactly 0, and a
+ * pair with t* > 0 its whole-line term: this differs from the integral over the half line t >= 0 by at most
+ * erfc(t* sqrt(A / 2)) / 2 of the term, negligible whenever the source lies several sigma outside the cloud.  There is no
+ * near-plane culling and no cut at 3 sigma.
+ * Culling: a pair with q <= 32 is always summed; a pair with q > 32 (below exp(-16) of that Gaussian's peak) is summed or
+ * skipped: a pixel sums a Gaussian when it lies in the conservative detector rectangle of the sphere of radius
+ * 1.01 sqrt(32) sigma_max / s_min(R) around mu (s_min = 1 for a unit quaternion; csrc/gaussian_rays.hpp).  A sphere that
+ * contains the cone source or straddles the plane through it parallel to the detector takes the whole detector.
+ * A pair with A = 0 or a non-finite result (a ray with no direction) contributes 0, and so does every pair of a Gaussian with
+ * a non-finite parameter or a scale <= 0.  P = 0 writes zeros.
+ * out[v][r][c] adds its pairs in ascending Gaussian index in one thread: no atomics, no workspace, no allocation and no host
+ * synchronisation; bit-reproducible, and a view's image does not depend on the other views of the call.  All arithmetic is
+ * separately rounded float32 in the order written above.  V <= 65535, P <= 2^29.
+ * r2_project_gaussians_backward: given G = dL/dout [V,H,W], the gradients of L with respect to means [P,3], density [P,1],
+ * scales [P,3] (the unmodified ones: the scale_modifier factor is included) and rotations [P,4] (the quaternion as given, no
+ * normalisation Jacobian).  Per pair, with T = term / |d|, g_w = -T wp, g_u = T (-u / A + (B / A) wp) and e = s - mu:
+ *     d mu = -|d| R S^-1 g_w,     d scale_i = -|d| (g_u,i u_i + g_w,i w_i) / scale_i,     d rho = term / rho (no division),
+ *     d R   = |d| (d (x) S^-1 g_u + e (x) S^-1 g_w),  d quaternion = the derivative of quat_to_rot applied to d R,
+ * each times G of the pixel.  A pair is differentiated exactly when the forward summed it (same rectangle, same cone rule,
+ * same arithmetic: the header is shared).  Gaussian-major: one wave walks the Gaussian's rectangle view by view and adds its
+ * 64 partial sums in a fixed order: no atomics, no workspace, bit-reproducible; every output element is written, exact zeros
+ * for a Gaussian no ray touches.  H * W < 2^30. */
+R2_API int r2_project_gaussians(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                const float *means /* [P,3] */, const float *density /* [P] */, const float *scales /* [P,3] */,
+                                float scale_modifier, const float *rotations /* [P,4] */, float *out /* [V,H,W] */,
+                                void *stream);
+R2_API int r2_project_gaussians_backward(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                         const float *means, const float *density, const float *scales, float scale_modifier,
+                                         const float *rotations, const float *dL_dout /* [V,H,W] */, float *dL_dmeans /* [P,3] */,
+                                         float *dL_ddensity /* [P] */, float *dL_dscales /* [P,3] */,
+                                         float *dL_drotations /* [P,4] */, void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -49,6 +49,10 @@ SOURCES = {
     "backprojector.hip": EXACT,
     "projector_siddon.hip": EXACT,
     "backprojector_siddon.hip": EXACT,
+    # EXACT: the per-pair arithmetic is then, operation for operation, the float32 restatement whose measured error sets the
+    # tests' tolerance (tests/gaussian_project_ref.py), and forward and backward round a pair identically (gaussian_rays.hpp)
+    "gaussian_project.hip": EXACT,
+    "gaussian_project_bwd.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

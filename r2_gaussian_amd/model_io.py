@@ -115,11 +115,14 @@ def metric_vol(vol_gt, vol_pred, metric="psnr", pixel_max=1.0):
 
 
 @torch.no_grad()
-def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="host"):
+def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="host", exact_views=None, exact_projs=None):
     """query() of render_query.py:27-77 at the scanner's full resolution on the HIP voxelizer, + test.py's 3D metrics.
     model: dict from load_point_cloud (raw parameters).  -> dict(vol, psnr_3d, ssim_3d, ...).
     metrics="device": the metrics on the HIP kernels (r2_gaussian_amd.metrics, one host sync, the reference's NaN when no
-    slice of an axis counts); "host": the torch restatement above on a CPU copy."""
+    slice of an axis counts); "host": the torch restatement above on a CPU copy.
+    exact_views (scene.View list) with exact_projs [V,H,W] (the measured projections in scene units): also the 2D metrics of the
+    model's exact projections (gaussian_projector.project_gaussians) against them, as psnr_2d_exact / ssim_2d_exact (+ _projs)
+    and the projections themselves as projs_exact."""
     assert metrics in ("host", "device")
     from .voxelization import GaussianVoxelizationSettings, GaussianVoxelizer
     xyz, dens, scal, rot = activate(model)
@@ -140,4 +143,12 @@ def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="hos
             out["ssim_3d"], (out["ssim_3d_x"], out["ssim_3d_y"], out["ssim_3d_z"]) = metric_vol(gt.cpu(), vol.cpu(), "ssim")
         if save_dir:
             save_volumes(save_dir, gt, vol)
+    if exact_views is not None:
+        from .gaussian_projector import project_gaussians
+        from .metrics import metric_proj
+        out["projs_exact"] = pe = project_gaussians(exact_views, xyz, dens, scal, rot)
+        if exact_projs is not None:
+            gts = torch.as_tensor(np.asarray(_np(exact_projs)), dtype=torch.float32).to(pe.device).permute(1, 2, 0)
+            out["psnr_2d_exact"], out["psnr_2d_exact_projs"] = metric_proj(gts, pe.permute(1, 2, 0), "psnr")
+            out["ssim_2d_exact"], out["ssim_2d_exact_projs"] = metric_proj(gts, pe.permute(1, 2, 0), "ssim")
     return out

@@ -8,7 +8,8 @@ Flag names and defaults are the reference's (ModelParams, OptimizationParams, Pi
 flag is an error.  ``training()`` is the loop itself: it takes views, projections, the ground truth, the geometry and the
 initial points, so it runs as well on an in-memory case.  Outputs, in the reference's layout under the model path:
 ``point_cloud/iteration_N/{point_cloud.pickle, vol_gt.npy, vol_pred.npy}``, ``eval/iter_NNNNNN/{eval3d.yml,
-eval2d_render_train.yml, eval2d_render_test.yml}``, ``ckpt/chkpnt{N}.pth``.
+eval2d_render_train.yml, eval2d_render_test.yml}``, ``ckpt/chkpnt{N}.pth``.  ``--eval_exact`` (not a flag of the reference; off
+by default) adds ``eval2d_render_{train,test}_exact.yml``: the same 2D metrics on the exact projection of the model.
 
 ``--views_per_step W`` (not a flag of the reference; default 1 = its loop): one optimiser step on W views -- one batched
 render, one batched loss node (the mean over the views), one backward, one batched statistics launch, one model step.
@@ -95,8 +96,18 @@ def render_views(gaussians, views, dev, batch=8):
 
 
 @torch.no_grad()
-def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals):
-    """training_report of train.py:262-330 without tensorboard: eval2d_<name>.yml per view set, eval3d.yml.  -> eval3d dict."""
+def project_views_exact(gaussians, views, batch=8):
+    """[V, H, W] exact line integrals of the model on the views (gaussian_projector.project_gaussians), `batch` views per call."""
+    from .gaussian_projector import project_gaussians
+    xyz, d, s, r = (t.detach() for t in gaussians.activated())
+    return torch.cat([project_gaussians(views[i:i + batch], xyz, d, s, r) for i in range(0, len(views), batch)], 0)
+
+
+@torch.no_grad()
+def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals, eval_exact=False):
+    """training_report of train.py:262-330 without tensorboard: eval2d_<name>.yml per view set, eval3d.yml.  -> eval3d dict.
+    eval_exact: also eval2d_<name>_exact.yml, the same metrics on the exact projection of the model instead of the
+    rasterizer's image of it."""
     import yaml
     dev = gaussians.device
     path = osp.join(model_path, "eval", "iter_%06d" % iteration)
@@ -104,12 +115,16 @@ def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals):
     for name, views, gts in evals:
         if not views:
             continue
-        images = render_views(gaussians, views, dev).permute(1, 2, 0)
-        psnr_2d, psnr_projs = M.metric_proj(gts, images, "psnr")
-        ssim_2d, ssim_projs = M.metric_proj(gts, images, "ssim")
-        with open(osp.join(path, "eval2d_%s.yml" % name), "w") as f:
-            yaml.dump({"psnr_2d": float(psnr_2d), "ssim_2d": float(ssim_2d), "psnr_2d_projs": [float(x) for x in psnr_projs],
-                       "ssim_2d_projs": [float(x) for x in ssim_projs]}, f, default_flow_style=False, sort_keys=False)
+        renders = [("", render_views(gaussians, views, dev))]
+        if eval_exact:
+            renders.append(("_exact", project_views_exact(gaussians, views)))
+        for suffix, stack in renders:
+            images = stack.permute(1, 2, 0)
+            psnr_2d, psnr_projs = M.metric_proj(gts, images, "psnr")
+            ssim_2d, ssim_projs = M.metric_proj(gts, images, "ssim")
+            with open(osp.join(path, "eval2d_%s%s.yml" % (name, suffix)), "w") as f:
+                yaml.dump({"psnr_2d": float(psnr_2d), "ssim_2d": float(ssim_2d), "psnr_2d_projs": [float(x) for x in psnr_projs],
+                           "ssim_2d_projs": [float(x) for x in ssim_projs]}, f, default_flow_style=False, sort_keys=False)
     xyz, d, s, r = (t.detach() for t in gaussians.activated())
     vol = _query(xyz, d, s, r, geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"])
     psnr_3d, ssim_3d, axes = M.metric_vol_both(vol_gt, vol)
@@ -147,7 +162,7 @@ def pick_views(stack, n_views, count, rng):
 
 def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry, init_points, opt, model_path,
              scale_bound=None, test_iterations=(), save_iterations=(), checkpoint_iterations=(), start_checkpoint=None,
-             seed=0, log=print, device="cuda", views_per_step=1):
+             seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False):
     """The training loop of train.py:34-216.  views: scene.View lists; projections: [V, H, W] in scene units (times
     scene_scale); vol_gt [nx, ny, nz]; geometry: the NORMALISED scanner config (nVoxel, sVoxel, offOrigin, dVoxel);
     init_points [N, 4] = xyz | density; scale_bound: (lo, hi) in scene units or None.  Randomness (view order, TV patch centres,
@@ -157,6 +172,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     losses.image_loss_batch (the MEAN over the views, so the parameter gradients are the views' mean) plus ONE TV patch, and
     one batched statistics call with grad_scale = W: the statistics see every view's own screen-space gradient, which keeps
     densify_grad_threshold a per-view quantity whatever W is.  W = 1 is the single-view loop, unchanged.
+    eval_exact: every evaluation also writes eval2d_<name>_exact.yml (evaluate); training itself is untouched.
     -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P)."""
     W = int(views_per_step)
     if W < 1:
@@ -189,7 +205,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     os.makedirs(ckpt_path, exist_ok=True)
     out = {"evals": {}}
     if first_iter == 0 and 0 in test_iterations:
-        out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals)
+        out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals, eval_exact)
     stack = []
     t_train, n_timed = 0.0, 0
     for iteration in range(first_iter + 1, opt.iterations + 1):
@@ -234,7 +250,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
         if iteration in checkpoint_iterations:
             model_io.save_checkpoint(osp.join(ckpt_path, "chkpnt%d.pth" % iteration), gaussians.capture(), iteration)
         if iteration in test_iterations:
-            out["evals"][iteration] = e = evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals)
+            out["evals"][iteration] = e = evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals, eval_exact)
             log("[ITER %d] Evaluating: psnr3d %.3f, ssim3d %.3f, P %d" % (iteration, e["psnr_3d"], e["ssim_3d"], gaussians.P))
     out["it_per_s"] = n_timed / t_train if t_train > 0 else float("nan")
     out["views_per_s"] = W * out["it_per_s"]
@@ -318,6 +334,9 @@ def build_parser():
                          "the learning rates are NOT rescaled.  Measured (DESIGN.md section 6): 8 with the default schedule "
                          "gains 3.6 dB of 3D PSNR at equal steps; for equal views divide iterations, densification window and "
                          "interval and *_lr_max_steps by 8 and multiply the eight *_lr_init / *_lr_final by 8 (+0.48 dB)")
+    ap.add_argument("--eval_exact", action="store_true", default=False,
+                    help="every evaluation also writes eval2d_render_{train,test}_exact.yml: the 2D metrics on the exact line "
+                         "integrals of the model (gaussian_projector) next to those on the rasterizer's image of it")
     return ap
 
 
@@ -356,7 +375,7 @@ def main(argv=None):
     out = training(case["train_views"], case["train_projs"], case["test_views"], case["test_projs"], case["vol_gt"],
                    case["geometry"], case["init_points"], opt, args.model_path, scale_bound, set(args.test_iterations),
                    set(args.save_iterations), set(args.checkpoint_iterations), args.start_checkpoint, log=log,
-                   views_per_step=args.views_per_step)
+                   views_per_step=args.views_per_step, eval_exact=args.eval_exact)
     print("Training complete. " + _rate(out, args.views_per_step))
     return out
 
