@@ -21,28 +21,22 @@
 // This TU is compiled with -ffp-contract=off (build.py: EXACT): the clip points and n are separately rounded float32
 // operations, so the float64 restatement (tests/projector_ref.py) can tell which pixels sit on a decision boundary.  The
 // sampling loop contracts by hand (fmaf), where the restatement's bound covers it.
-#include "r2_common.hpp"
 #include "ray_sampling.hpp"
+#include "volume_entry.hpp"
 #include <math.h>
 
 namespace r2 {
 
 namespace {
 
-constexpr int PT = 8;          // wave tile: PT x PT pixels
-constexpr int PB = 256;        // threads per block: 2 x 2 wave tiles
-constexpr int BW = 2 * PT, BH = 2 * PT;
-
 template <typename OFF>
 __global__ void __launch_bounds__(PB) project_kernel(int H, int W, const float *__restrict__ rays, int cone, int nx, int ny,
                                                      int nz, float3 dv, float accuracy, const float *__restrict__ vol,
                                                      float *__restrict__ out)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x * BW + (wave & 1) * PT + (lane & (PT - 1));
-    const int r = blockIdx.y * BH + (wave >> 1) * PT + (lane / PT);
+    int r, c;
+    if (!thread_pixel(H, W, r, c)) return;
     const int view = blockIdx.z;
-    if (c >= W || r >= H) return;
     const Ray y = pixel_ray(rays + 12 * view, cone, r, c);
     float t0, t1;
     const bool hit = clip_ray(y, cone, nx, ny, nz, t0, t1);
@@ -84,17 +78,11 @@ extern "C" int r2_project_volume(int V, int H, int W, const float *rays, int con
                                  float dVoxel_y, float dVoxel_z, float accuracy, const float *vol, float *out, void *stream)
 {
     using namespace r2;
-    if (V <= 0 || H <= 0 || W <= 0 || nx <= 0 || ny <= 0 || nz <= 0 || !rays || !vol || !out || !(accuracy > 0.f) ||
-        !(dVoxel_x > 0.f) || !(dVoxel_y > 0.f) || !(dVoxel_z > 0.f)) {
-        set_error("r2_project_volume: invalid argument");
-        return R2_ERR_INVALID;
-    }
-    if ((long long)ny * nz >= (1LL << 32) || V > 65535 || (H + BH - 1) / BH > 65535) {
-        set_error("r2_project_volume: shape out of range (V %d, H %d, ny*nz %lld)", V, H, (long long)ny * nz);
-        return R2_ERR_INVALID;
-    }
+    if (const int rc = check_forward_args("r2_project_volume", V, H, W, rays, nx, ny, nz, dVoxel_x, dVoxel_y, dVoxel_z,
+                                          &accuracy, vol, out))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((W + BW - 1) / BW, (H + BH - 1) / BH, V);
+    const dim3 grid = volume_pixel_grid(V, H, W);
     const float3 d = make_float3(dVoxel_x, dVoxel_y, dVoxel_z);
     if ((unsigned long long)nx * ny * nz < (1ULL << 32))
         project_kernel<unsigned><<<grid, dim3(PB), 0, s>>>(H, W, rays, cone, nx, ny, nz, d, accuracy, vol, out);

@@ -86,12 +86,7 @@ def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, sc
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != _F32 or not out.is_cuda or not out.is_contiguous()
                             or tuple(out.shape) != (V, H, W) or out.device != xyz.device):
         raise ValueError("out must be a contiguous float32 tensor [%d,%d,%d] on %s" % (V, H, W, xyz.device))
-    if rays.is_cuda:
-        if rays.device != xyz.device:
-            raise ValueError("rays are on %s, xyz on %s" % (rays.device, xyz.device))
-        rays = _f32c(rays)
-    else:
-        rays = _f32c(rays).pin_memory().to(xyz.device, non_blocking=True)
+    rays = projector.device_rays(rays, xyz.device)
     if out is None:
         out = torch.empty((V, H, W), dtype=_F32, device=xyz.device)
     return _ProjectGaussians.apply(xyz, density, scaling, rotation, rays, int(bool(cone)), H, W, float(scale_modifier), out)
@@ -100,13 +95,6 @@ def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, sc
 def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
     """Exact projections [V,H,W] of the cloud on ``views`` (``scene.View`` list: one detector size, one beam mode), registered
     to the rasterizer's image of the same view.  See ``project_gaussians_rays``."""
-    views = list(views)
-    if not views:
-        raise ValueError("no views to project")
-    H, W = views[0].image_height, views[0].image_width
-    if any((v.image_height, v.image_width) != (H, W) for v in views):
-        raise ValueError("all views must share one detector size")
-    if any(v.mode != views[0].mode for v in views):
-        raise ValueError("all views must share one beam mode")
+    views, H, W = projector.check_views(views)
     return project_gaussians_rays(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
                                   rotation, scale_modifier, out)

@@ -17,6 +17,11 @@ n = max(1, ceil(L / accuracy)) equal pieces of the clipped chord (include/r2hip.
 That is ``projection_type="interpolated"``, the default.  ``projection_type="siddon"`` takes the ray-voxel intersection model
 instead (csrc/projector_siddon.hip, ``r2_project_volume_siddon``): the exact integral of the piecewise-constant volume, voxel
 (i,j,k) being a cube of constant value; it has no ``accuracy``.
+
+Both directions of both models live here: the exact transposes ``r2_backproject_volume`` and ``r2_backproject_volume_siddon``
+(csrc/backprojector.hip, csrc/backprojector_siddon.hip on the gather of csrc/voxel_gather.hpp), the rays-level pair
+``project_rays`` / ``backproject_rays`` for detectors a camera cannot describe, and ``Operator``, the pair in the raw scanner
+config's units that the iterative reconstructions (recon.py) are built on.
 """
 import numpy as np
 import torch
@@ -27,13 +32,112 @@ from ._C import _on_device, _require_gpu, _stream
 
 _F32 = torch.float32
 PROJECTION_TYPES = ("interpolated", "siddon")
+# (direction, projection_type) -> the C function and whether it takes ``accuracy``
+_ENTRY_POINTS = {
+    ("project", "interpolated"): ("r2_project_volume", True),
+    ("project", "siddon"): ("r2_project_volume_siddon", False),
+    ("backproject", "interpolated"): ("r2_backproject_volume", True),
+    ("backproject", "siddon"): ("r2_backproject_volume_siddon", False),
+}
 
+
+# ---- the checks, one of each ------------------------------------------------------------------------------------------------
 
 def check_projection_type(projection_type):
     """-> ``projection_type``, or ValueError for anything but the two models."""
     if projection_type not in PROJECTION_TYPES:
         raise ValueError("projection_type must be one of %s, got %r" % (PROJECTION_TYPES, projection_type))
     return projection_type
+
+
+def check_accuracy(accuracy, projection_type):
+    """ValueError unless ``accuracy`` > 0; "siddon" has none and does not look at it."""
+    if projection_type == "interpolated" and not accuracy > 0:
+        raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
+
+
+def check_views(views):
+    """-> (list of views, H, W), or ValueError unless there is a view and all share one detector size and one beam mode."""
+    views = list(views)
+    if not views:
+        raise ValueError("no views")
+    H, W = views[0].image_height, views[0].image_width
+    if any((v.image_height, v.image_width) != (H, W) for v in views):
+        raise ValueError("all views must share one detector size")
+    if any(v.mode != views[0].mode for v in views):
+        raise ValueError("all views must share one beam mode")
+    return views, H, W
+
+
+def _check_extent(sVoxel, center):
+    if len(sVoxel) != 3 or len(center) != 3 or not all(s > 0 for s in sVoxel):
+        raise ValueError("sVoxel must be three positive sizes and center three coordinates")
+
+
+def _check_operand(t, name, layout, projection_type):
+    """The model first, then the GPU requirement, then the operand's rank."""
+    check_projection_type(projection_type)
+    _require_gpu(t, name)
+    if t.dim() != 3:
+        raise ValueError("%s must be %s, got shape %s" % (name, layout, tuple(t.shape)))
+
+
+def _f32c(t):
+    return t if t.dtype == _F32 and t.is_contiguous() else t.to(_F32).contiguous()
+
+
+def device_rays(rays, device):
+    """[V,12] ray parameters as a contiguous float32 tensor on ``device``: host rays go through pinned memory without a
+    host synchronisation, rays already there are taken as they are."""
+    rays = torch.as_tensor(rays)
+    if rays.dim() != 2 or rays.shape[1] != 12:
+        raise ValueError("rays must be [V,12], got shape %s" % (tuple(rays.shape),))
+    if rays.is_cuda:
+        if rays.device != device:
+            raise ValueError("rays are on %s, the operand on %s" % (rays.device, device))
+        return _f32c(rays)
+    return _f32c(rays).pin_memory().to(device, non_blocking=True)
+
+
+def _output(out, shape, device, layout):
+    """``out`` checked against ``shape`` (None: any 3D shape), or a new tensor of that shape."""
+    if out is None:
+        return torch.empty(shape, dtype=_F32, device=device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != _F32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 3
+            or out.device != device or (shape is not None and tuple(out.shape) != tuple(shape))):
+        raise ValueError("out must be a contiguous float32 tensor %s on %s" % (layout, device))
+    return out
+
+
+def _volume_output(out, nVoxel, device):
+    """The volume an adjoint writes: ``out``, of the shape ``nVoxel`` where that is given, or a new one of that shape."""
+    if nVoxel is not None:
+        if len(nVoxel) != 3 or not all(int(n) > 0 for n in nVoxel):
+            raise ValueError("nVoxel must be three positive sizes, got %r" % (nVoxel,))
+        nVoxel = tuple(int(n) for n in nVoxel)
+    elif out is None:
+        raise ValueError("give the volume's shape: nVoxel (three positive sizes) or out")
+    return _output(out, nVoxel, device, "[nx,ny,nz]")
+
+
+def _voxel_sizes(dVoxel):
+    if len(dVoxel) != 3 or not all(d > 0 for d in dVoxel):
+        raise ValueError("dVoxel must be three positive sizes, got %r" % (dVoxel,))
+    return [float(d) for d in dVoxel]
+
+
+# ---- the one launch site ------------------------------------------------------------------------------------------------------
+
+def _launch(direction, projection_type, rays, cone, H, W, nVoxel, dVoxel, accuracy, src, dst):
+    """``dst`` = A ``src`` ("project") or A^T ``src`` ("backproject") on checked, contiguous float32 GPU operands."""
+    name, takes_accuracy = _ENTRY_POINTS[direction, projection_type]
+    args = [rays.shape[0], H, W, rays.data_ptr(), int(bool(cone))] + list(nVoxel) + list(dVoxel)
+    if takes_accuracy:
+        args.append(float(accuracy))
+    with _on_device(src.device):
+        rc = getattr(_lib.lib(), name)(*args, src.data_ptr(), dst.data_ptr(), _stream(src.device))
+    _lib.check(rc, name)
+    return dst
 
 
 def ray_params(views, sVoxel, center, nVoxel):
@@ -64,48 +168,68 @@ def ray_params(views, sVoxel, center, nVoxel):
     return out.astype(np.float32)
 
 
+# ---- rays level: caller-supplied rays ---------------------------------------------------------------------------------------
+
+def project_rays(vol, rays, cone, H, W, dVoxel, accuracy=0.5, out=None, projection_type="interpolated"):
+    """Line integrals [V,H,W] (GPU, float32) of ``vol`` [nx,ny,nz] (GPU) along caller-supplied rays: ``rays`` [V,12]
+    {a, p00, pu, pv} in voxel-index coordinates (include/r2hip.h), ``cone`` the beam (True: from the source a through the
+    pixel points; False: through the pixel points along a), ``dVoxel`` the three voxel sizes that scale index lengths to
+    world lengths.  No host synchronisation; ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
+    _check_operand(vol, "vol", "a 3D array [nx,ny,nz]", projection_type)
+    check_accuracy(accuracy, projection_type)
+    rays = device_rays(rays, vol.device)
+    H, W = int(H), int(W)
+    out = _output(out, (rays.shape[0], H, W), vol.device, "[%d,%d,%d]" % (rays.shape[0], H, W))
+    v32 = _f32c(vol)
+    return _launch("project", projection_type, rays, cone, H, W, v32.shape, _voxel_sizes(dVoxel), accuracy, v32, out)
+
+
+def backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy=0.5, out=None, projection_type="interpolated"):
+    """The exact transpose of ``project_rays``: vol [nx,ny,nz] (GPU, float32) = A^T projs for projections [V,H,W] (GPU) of
+    the same ``rays``.  The volume's shape is ``nVoxel``, or that of ``out`` (a contiguous float32 GPU tensor, overwritten)
+    where ``nVoxel`` is None.  No host synchronisation."""
+    _check_operand(projs, "projs", "[V,H,W]", projection_type)
+    check_accuracy(accuracy, projection_type)
+    rays = device_rays(rays, projs.device)
+    V, H, W = projs.shape
+    if rays.shape[0] != V:
+        raise ValueError("%d projections for %d views' rays" % (V, rays.shape[0]))
+    out = _volume_output(out, nVoxel, projs.device)
+    return _launch("backproject", projection_type, rays, cone, H, W, out.shape, _voxel_sizes(dVoxel), accuracy, _f32c(projs),
+                   out)
+
+
+# ---- views level: the rasterizer's cameras --------------------------------------------------------------------------------------
+
 def project_views(vol, views, sVoxel, center, accuracy=0.5, out=None, projection_type="interpolated"):
     """Line integrals of ``vol`` [nx,ny,nz] (GPU, the query() / voxelizer layout) along the rays of every pixel of ``views``
     (``scene.View`` list, one detector size): a GPU tensor [V,H,W] in scene units.  ``sVoxel`` / ``center``: the volume's
     extent and centre in the views' (scene) units.  No host synchronisation; ``out`` may be a preallocated [V,H,W] float32
     contiguous GPU tensor.  ``projection_type``: "interpolated" or "siddon" (which ignores ``accuracy``)."""
-    check_projection_type(projection_type)
-    _require_gpu(vol, "vol")
-    if vol.dim() != 3:
-        raise ValueError("vol must be a 3D array [nx,ny,nz], got shape %s" % (tuple(vol.shape),))
-    if projection_type == "interpolated" and not accuracy > 0:
-        raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
-    views = list(views)
-    if not views:
-        raise ValueError("no views to project")
-    H, W = views[0].image_height, views[0].image_width
-    if any((v.image_height, v.image_width) != (H, W) for v in views):
-        raise ValueError("all views must share one detector size")
-    if any(v.mode != views[0].mode for v in views):
-        raise ValueError("all views must share one beam mode")
-    if len(sVoxel) != 3 or len(center) != 3 or not all(s > 0 for s in sVoxel):
-        raise ValueError("sVoxel must be three positive sizes and center three coordinates")
-    v32 = vol if vol.dtype == _F32 and vol.is_contiguous() else vol.to(_F32).contiguous()
-    nx, ny, nz = v32.shape
-    V = len(views)
-    if out is None:
-        out = torch.empty((V, H, W), dtype=_F32, device=v32.device)
-    elif (out.dtype != _F32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (V, H, W)
-          or out.device != v32.device):
-        raise ValueError("out must be a contiguous float32 tensor [%d,%d,%d] on %s" % (V, H, W, v32.device))
-    rays = torch.from_numpy(ray_params(views, sVoxel, center, (nx, ny, nz))).pin_memory().to(v32.device, non_blocking=True)
-    d = [float(s) / n for s, n in zip(sVoxel, (nx, ny, nz))]
-    L = _lib.lib()
-    with _on_device(v32.device):
-        if projection_type == "siddon":
-            rc = L.r2_project_volume_siddon(V, H, W, rays.data_ptr(), int(views[0].mode == 1), nx, ny, nz, d[0], d[1], d[2],
-                                            v32.data_ptr(), out.data_ptr(), _stream(v32.device))
-        else:
-            rc = L.r2_project_volume(V, H, W, rays.data_ptr(), int(views[0].mode == 1), nx, ny, nz, d[0], d[1], d[2],
-                                     float(accuracy), v32.data_ptr(), out.data_ptr(), _stream(v32.device))
-    _lib.check(rc, "r2_project_volume_siddon" if projection_type == "siddon" else "r2_project_volume")
-    return out
+    _check_operand(vol, "vol", "a 3D array [nx,ny,nz]", projection_type)
+    views, H, W = check_views(views)
+    _check_extent(sVoxel, center)
+    n = tuple(vol.shape)
+    return project_rays(vol, ray_params(views, sVoxel, center, n), views[0].mode == 1, H, W,
+                        [float(s) / m for s, m in zip(sVoxel, n)], accuracy, out, projection_type)
 
+
+def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVoxel=None, projection_type="interpolated"):
+    """The exact transpose of ``project_views``: vol [nx,ny,nz] (GPU) = A^T projs for projections [V,H,W] (GPU, float32) of
+    ``views`` (scene units).  The volume's shape comes from ``out`` (a contiguous float32 GPU tensor, overwritten) or
+    ``nVoxel``.  No host synchronisation.  ``projection_type`` as in ``project_views``."""
+    _check_operand(projs, "projs", "[V,H,W]", projection_type)
+    views, H, W = check_views(views)
+    if tuple(projs.shape) != (len(views), H, W):
+        raise ValueError("projs shape %s differs from the views' [%d,%d,%d]" % (tuple(projs.shape), len(views), H, W))
+    _check_extent(sVoxel, center)
+    out = _volume_output(out, nVoxel, projs.device)
+    n = tuple(out.shape)
+    return backproject_rays(projs, ray_params(views, sVoxel, center, n), views[0].mode == 1, None,
+                            [float(s) / m for s, m in zip(sVoxel, n)], accuracy, out, projection_type)
+
+
+# ---- config level: the raw scanner config and its length units -------------------------------------------------------------------
 
 def project(vol, angles, scanner_cfg, accuracy=None, device="cuda", projection_type="interpolated"):
     """``tigre.Ax(vol, geo, angles)[:, ::-1, :]`` as generate_data.py saves it: projections [V,H,W] (GPU tensor) of ``vol``
@@ -121,8 +245,7 @@ def project(vol, angles, scanner_cfg, accuracy=None, device="cuda", projection_t
     if tuple(int(n) for n in cfg["nVoxel"]) != tuple(v.shape):
         raise ValueError("vol shape %s differs from the config's nVoxel %s" % (tuple(v.shape), list(cfg["nVoxel"])))
     acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
-    if projection_type == "interpolated" and not acc > 0:
-        raise ValueError("accuracy must be > 0, got %r" % (acc,))
+    check_accuracy(acc, projection_type)
     if not v.is_cuda:
         v = v.to(device)
     scale = 2.0 / max(cfg["sVoxel"])   # make_view works in the normalised scene (dataset_readers.py:62-76)
@@ -131,3 +254,67 @@ def project(vol, angles, scanner_cfg, accuracy=None, device="cuda", projection_t
     out = project_views(v, views, [s * scale for s in cfg["sVoxel"]], [o * scale for o in cfg["offOrigin"]], acc,
                         projection_type=projection_type)
     return out.mul_(1.0 / scale)
+
+
+class Operator:
+    """A = ``project(., angles, cfg)`` and its transpose on one device, with the rays computed once: ``A(x, v0, v1)`` projects
+    views v0..v1-1, ``At(p, v0, v1)`` back-projects them.  ``projection_type``: "interpolated" or "siddon" (which ignores
+    ``accuracy``), the model of both."""
+
+    def __init__(self, angles, cfg, accuracy=None, device="cuda", projection_type="interpolated"):
+        self.projection_type = check_projection_type(projection_type)
+        self.cfg = cfg
+        acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
+        check_accuracy(acc, projection_type)
+        self.accuracy = float(acc)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.R2HipError("the reconstructions run on the MI355X kernels: device must be a GPU, got %s" % device)
+        self.nVoxel = tuple(int(n) for n in cfg["nVoxel"])
+        self.H, self.W = (int(n) for n in cfg["nDetector"])
+        scale = 2.0 / max(cfg["sVoxel"])   # make_view works in the normalised scene (dataset_readers.py:62-76)
+        self.inv_scale = 1.0 / scale
+        ang = np.asarray(angles, dtype=np.float64).reshape(-1)
+        if ang.size == 0:
+            raise ValueError("no angles")
+        self.V = int(ang.size)
+        views = [S.make_view(float(a), (self.H, self.W), cfg) for a in ang]
+        self.cone = views[0].mode == 1
+        sV = [s * scale for s in cfg["sVoxel"]]
+        self.dVoxel = [s / n for s, n in zip(sV, self.nVoxel)]
+        self.rays = device_rays(ray_params(views, sV, [o * scale for o in cfg["offOrigin"]], self.nVoxel), self.device)
+
+    def A(self, x, v0=0, v1=None, out=None):
+        v1 = self.V if v1 is None else v1
+        if tuple(x.shape) != self.nVoxel:
+            raise ValueError("volume shape %s differs from the config's nVoxel %s" % (tuple(x.shape), self.nVoxel))
+        out = project_rays(x, self.rays[v0:v1], self.cone, self.H, self.W, self.dVoxel, self.accuracy, out,
+                           self.projection_type)
+        return out.mul_(self.inv_scale)
+
+    def At(self, p, v0=0, v1=None, out=None):
+        v1 = self.V if v1 is None else v1
+        if tuple(p.shape) != (v1 - v0, self.H, self.W):
+            raise ValueError("projections %s are not views %d..%d of [%d,%d]" % (tuple(p.shape), v0, v1 - 1, self.H, self.W))
+        out = backproject_rays(p, self.rays[v0:v1], self.cone, self.nVoxel, self.dVoxel, self.accuracy, out,
+                               self.projection_type)
+        return out.mul_(self.inv_scale)
+
+
+def _projections(projs, op):
+    p = projs if isinstance(projs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(projs))
+    if p.dim() != 3 or tuple(p.shape) != (op.V, op.H, op.W):
+        raise ValueError("projections must be [%d,%d,%d] (one per angle, the config's nDetector), got %s"
+                         % (op.V, op.H, op.W, tuple(p.shape)))
+    if p.is_floating_point() is False:
+        raise ValueError("projections must be floating point, got %s" % (p.dtype,))
+    if not p.is_cuda:
+        p = p.to(_F32).contiguous().pin_memory()
+    return p.to(device=op.device, dtype=_F32, non_blocking=True).contiguous()
+
+
+def backproject(projs, angles, scanner_cfg, accuracy=None, device="cuda", projection_type="interpolated"):
+    """The transpose of ``project``: vol [nx,ny,nz] (GPU tensor) = A^T projs for projections [V,H,W] at ``angles`` with the raw
+    scanner config, including ``project``'s 1 / scale."""
+    op = Operator(angles, scanner_cfg, accuracy, device, projection_type)
+    return op.At(_projections(projs, op))

@@ -1,11 +1,12 @@
 """Classical iterative CT reconstructions without TIGRE: CGLS, SART, OS-SART, ASD-POCS and OS-ASD-POCS, the baselines of
 the reference's ``run_ct_recon_algs`` (r2_gaussian/utils/ct_utils.py:60-215) and ``scripts/run_traditional_methods.py``.
 
-They stand on two MI355X kernels behind the C ABI: the forward projector ``r2_project_volume`` (``A``, projector.py) and its
-exact transpose ``r2_backproject_volume`` (``A^T``, csrc/backprojector.hip), plus ``r2_tv_descent`` (csrc/tv_descent.hip) for
-the TV steps of ASD-POCS.  ``projection_type="siddon"`` swaps the pair for the ray-voxel intersection model,
+They stand on two MI355X kernels behind the C ABI: the forward projector ``r2_project_volume`` (``A``) and its exact
+transpose ``r2_backproject_volume`` (``A^T``, csrc/backprojector.hip), plus ``r2_tv_descent`` (csrc/tv_descent.hip) for the TV
+steps of ASD-POCS.  ``projection_type="siddon"`` swaps the pair for the ray-voxel intersection model,
 ``r2_project_volume_siddon`` and its exact transpose ``r2_backproject_volume_siddon`` (csrc/backprojector_siddon.hip); the
-default everywhere is ``"interpolated"``.  The vector updates between them are elementwise tensor operations; every data-dependent scalar
+default everywhere is ``"interpolated"``.  Both directions live in projector.py: ``Operator``, ``backproject`` and
+``backproject_views`` are its names, imported here for the callers that know them as this module's.  The vector updates between them are elementwise tensor operations; every data-dependent scalar
 stays a 0-d device tensor, so an iteration makes no host synchronisation unless ``computel2`` or ``verbose`` asks for one.
 
 Conventions are those of ``projector.project`` and ``fdk.fdk``: the raw scanner config and its length units, projections
@@ -34,159 +35,12 @@ import torch
 from . import _lib
 from . import fdk as F
 from . import projector as P
-from . import scene as S
 from ._C import _on_device, _require_gpu, _stream
+from .projector import Operator, _projections, backproject, backproject_views   # noqa: F401
 
 _F32 = torch.float32
 _F64 = torch.float64
 METHODS = ("fdk", "sart", "ossart", "asd_pocs", "os_asd_pocs", "cgls")
-
-
-# ---- the adjoint ----------------------------------------------------------------------------------------------------------
-
-def _backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy, out, projection_type="interpolated"):
-    V, H, W = projs.shape
-    nx, ny, nz = nVoxel
-    L = _lib.lib()
-    with _on_device(projs.device):
-        if projection_type == "siddon":
-            rc = L.r2_backproject_volume_siddon(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
-                                                float(dVoxel[1]), float(dVoxel[2]), projs.data_ptr(), out.data_ptr(),
-                                                _stream(projs.device))
-        else:
-            rc = L.r2_backproject_volume(V, H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]), float(dVoxel[1]),
-                                         float(dVoxel[2]), float(accuracy), projs.data_ptr(), out.data_ptr(),
-                                         _stream(projs.device))
-    _lib.check(rc, "r2_backproject_volume_siddon" if projection_type == "siddon" else "r2_backproject_volume")
-    return out
-
-
-def _project_rays(vol, rays, cone, H, W, dVoxel, accuracy, out, projection_type="interpolated"):
-    nx, ny, nz = vol.shape
-    L = _lib.lib()
-    with _on_device(vol.device):
-        if projection_type == "siddon":
-            rc = L.r2_project_volume_siddon(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
-                                            float(dVoxel[1]), float(dVoxel[2]), vol.data_ptr(), out.data_ptr(),
-                                            _stream(vol.device))
-        else:
-            rc = L.r2_project_volume(rays.shape[0], H, W, rays.data_ptr(), int(cone), nx, ny, nz, float(dVoxel[0]),
-                                     float(dVoxel[1]), float(dVoxel[2]), float(accuracy), vol.data_ptr(), out.data_ptr(),
-                                     _stream(vol.device))
-    _lib.check(rc, "r2_project_volume_siddon" if projection_type == "siddon" else "r2_project_volume")
-    return out
-
-
-def _check_views(views):
-    views = list(views)
-    if not views:
-        raise ValueError("no views to back-project")
-    H, W = views[0].image_height, views[0].image_width
-    if any((v.image_height, v.image_width) != (H, W) for v in views):
-        raise ValueError("all views must share one detector size")
-    if any(v.mode != views[0].mode for v in views):
-        raise ValueError("all views must share one beam mode")
-    return views, H, W
-
-
-def backproject_views(projs, views, sVoxel, center, accuracy=0.5, out=None, nVoxel=None, projection_type="interpolated"):
-    """The exact transpose of ``projector.project_views``: vol [nx,ny,nz] (GPU) = A^T projs for projections [V,H,W] (GPU,
-    float32) of ``views`` (scene units).  The volume's shape comes from ``out`` (a contiguous float32 GPU tensor, overwritten)
-    or ``nVoxel``.  No host synchronisation.  ``projection_type`` as in ``project_views``."""
-    P.check_projection_type(projection_type)
-    _require_gpu(projs, "projs")
-    if projs.dim() != 3:
-        raise ValueError("projs must be [V,H,W], got shape %s" % (tuple(projs.shape),))
-    if projection_type == "interpolated" and not accuracy > 0:
-        raise ValueError("accuracy must be > 0, got %r" % (accuracy,))
-    views, H, W = _check_views(views)
-    if tuple(projs.shape) != (len(views), H, W):
-        raise ValueError("projs shape %s differs from the views' [%d,%d,%d]" % (tuple(projs.shape), len(views), H, W))
-    if len(sVoxel) != 3 or len(center) != 3 or not all(s > 0 for s in sVoxel):
-        raise ValueError("sVoxel must be three positive sizes and center three coordinates")
-    if out is None:
-        if nVoxel is None or len(nVoxel) != 3 or not all(int(n) > 0 for n in nVoxel):
-            raise ValueError("give the volume's shape: nVoxel (three positive sizes) or out")
-        out = torch.empty(tuple(int(n) for n in nVoxel), dtype=_F32, device=projs.device)
-    elif (out.dtype != _F32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 3 or out.device != projs.device
-          or (nVoxel is not None and tuple(out.shape) != tuple(int(n) for n in nVoxel))):
-        raise ValueError("out must be a contiguous float32 tensor [nx,ny,nz] on %s" % (projs.device,))
-    p32 = projs if projs.dtype == _F32 and projs.is_contiguous() else projs.to(_F32).contiguous()
-    nv = tuple(out.shape)
-    rays = torch.from_numpy(P.ray_params(views, sVoxel, center, nv)).pin_memory().to(p32.device, non_blocking=True)
-    d = [float(s) / n for s, n in zip(sVoxel, nv)]
-    return _backproject_rays(p32, rays, views[0].mode == 1, nv, d, accuracy, out, projection_type)
-
-
-# ---- the operator pair in config units --------------------------------------------------------------------------------------
-
-class Operator:
-    """A = ``project(., angles, cfg)`` and its transpose on one device, with the rays computed once: ``A(x, v0, v1)`` projects
-    views v0..v1-1, ``At(p, v0, v1)`` back-projects them.  ``projection_type``: "interpolated" or "siddon" (which ignores
-    ``accuracy``), the model of both."""
-
-    def __init__(self, angles, cfg, accuracy=None, device="cuda", projection_type="interpolated"):
-        self.projection_type = P.check_projection_type(projection_type)
-        self.cfg = cfg
-        acc = cfg.get("accuracy", 0.5) if accuracy is None else accuracy
-        if projection_type == "interpolated" and not acc > 0:
-            raise ValueError("accuracy must be > 0, got %r" % (acc,))
-        self.accuracy = float(acc)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.R2HipError("the reconstructions run on the MI355X kernels: device must be a GPU, got %s" % device)
-        self.nVoxel = tuple(int(n) for n in cfg["nVoxel"])
-        self.H, self.W = (int(n) for n in cfg["nDetector"])
-        scale = 2.0 / max(cfg["sVoxel"])   # make_view works in the normalised scene (dataset_readers.py:62-76)
-        self.inv_scale = 1.0 / scale
-        ang = np.asarray(angles, dtype=np.float64).reshape(-1)
-        if ang.size == 0:
-            raise ValueError("no angles")
-        self.V = int(ang.size)
-        views = [S.make_view(float(a), (self.H, self.W), cfg) for a in ang]
-        self.cone = views[0].mode == 1
-        sV = [s * scale for s in cfg["sVoxel"]]
-        self.dVoxel = [s / n for s, n in zip(sV, self.nVoxel)]
-        rays = P.ray_params(views, sV, [o * scale for o in cfg["offOrigin"]], self.nVoxel)
-        self.rays = torch.from_numpy(rays).pin_memory().to(self.device, non_blocking=True)
-
-    def A(self, x, v0=0, v1=None, out=None):
-        v1 = self.V if v1 is None else v1
-        if tuple(x.shape) != self.nVoxel:
-            raise ValueError("volume shape %s differs from the config's nVoxel %s" % (tuple(x.shape), self.nVoxel))
-        if out is None:
-            out = torch.empty((v1 - v0, self.H, self.W), dtype=_F32, device=self.device)
-        _project_rays(x, self.rays[v0:v1], self.cone, self.H, self.W, self.dVoxel, self.accuracy, out, self.projection_type)
-        return out.mul_(self.inv_scale)
-
-    def At(self, p, v0=0, v1=None, out=None):
-        v1 = self.V if v1 is None else v1
-        if tuple(p.shape) != (v1 - v0, self.H, self.W):
-            raise ValueError("projections %s are not views %d..%d of [%d,%d]" % (tuple(p.shape), v0, v1 - 1, self.H, self.W))
-        if out is None:
-            out = torch.empty(self.nVoxel, dtype=_F32, device=self.device)
-        _backproject_rays(p, self.rays[v0:v1], self.cone, self.nVoxel, self.dVoxel, self.accuracy, out,
-                          self.projection_type)
-        return out.mul_(self.inv_scale)
-
-
-def _projections(projs, op):
-    p = projs if isinstance(projs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(projs))
-    if p.dim() != 3 or tuple(p.shape) != (op.V, op.H, op.W):
-        raise ValueError("projections must be [%d,%d,%d] (one per angle, the config's nDetector), got %s"
-                         % (op.V, op.H, op.W, tuple(p.shape)))
-    if p.is_floating_point() is False:
-        raise ValueError("projections must be floating point, got %s" % (p.dtype,))
-    if not p.is_cuda:
-        p = p.to(_F32).contiguous().pin_memory()
-    return p.to(device=op.device, dtype=_F32, non_blocking=True).contiguous()
-
-
-def backproject(projs, angles, scanner_cfg, accuracy=None, device="cuda", projection_type="interpolated"):
-    """The transpose of ``projector.project``: vol [nx,ny,nz] (GPU tensor) = A^T projs for projections [V,H,W] at ``angles``
-    with the raw scanner config, including ``project``'s 1 / scale."""
-    op = Operator(angles, scanner_cfg, accuracy, device, projection_type)
-    return op.At(_projections(projs, op))
 
 
 def _sq(t):

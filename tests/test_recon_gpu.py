@@ -18,41 +18,11 @@ from r2_gaussian_amd import scene as S
 from tests import helpers as Hh
 from tests import projector_ref as PR
 from tests import recon_ref as RR
+from tests.operator_cases import TINY_ANGLES, TRANSPOSE, _tiny_cfg, one_hot_matrices, tiny_system
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
-
-# name, scanner, (H, W), nVoxel, sVoxel, center, angles, accuracy
-TRANSPOSE = [
-    ("cone_aniso_offset", S.CONE_BEAM, (11, 13), (9, 7, 8), (1.8, 1.4, 1.7), (0.1, -0.05, 0.07), (0.3, 2.1, 4.0), 0.5),
-    ("parallel_aniso_offset", S.PARALLEL_BEAM, (11, 13), (9, 7, 8), (1.8, 1.4, 1.7), (0.1, -0.05, 0.07), (0.3, 2.1, 4.0), 0.5),
-    ("cone_misses", S.CONE_BEAM, (11, 13), (9, 7, 8), (0.6, 0.7, 0.5), (0.35, -0.3, 0.2), (0.2, 2.0, 4.1), 0.25),
-    ("parallel_misses", S.PARALLEL_BEAM, (11, 13), (9, 7, 8), (0.6, 0.7, 0.5), (0.35, -0.3, 0.2), (0.2, 2.0, 4.1), 1.0),
-    ("cone_45s_grazing", S.CONE_BEAM, (16, 17), (6, 6, 6), (2.0, 2.0, 2.0), (0.0, 0.0, 0.0), (0.0, np.pi / 4, np.pi / 2), 0.5),
-    # the source (5 scene units from the origin) inside the support: the gather takes the whole detector there
-    ("cone_source_inside", S.CONE_BEAM, (11, 13), (7, 6, 5), (12.0, 11.0, 10.0), (0.2, 0.0, 0.1), (0.3, 2.1, 4.0), 0.5),
-]
-
-
-def _matrices(dev, scanner, det, n, s, ctr, angles, acc):
-    views = [S.make_view(a, det, scanner) for a in angles]
-    H, W = det
-    N, M = int(np.prod(n)), len(views) * H * W
-    fwd = np.zeros((M, N))
-    vol = torch.zeros(N, device=dev)
-    for v in range(N):
-        vol.zero_()
-        vol[v] = 1.0
-        fwd[:, v] = K.project_views(vol.reshape(n), views, s, ctr, acc).reshape(-1).cpu().numpy()
-    bwd = np.zeros((M, N))
-    pr = torch.zeros(M, device=dev)
-    out = torch.empty(n, device=dev)
-    for r in range(M):
-        pr.zero_()
-        pr[r] = 1.0
-        bwd[r] = RC.backproject_views(pr.reshape(len(views), H, W), views, s, ctr, acc, out=out).reshape(-1).cpu().numpy()
-    return views, fwd, bwd
 
 
 @pytest.mark.parametrize("case", TRANSPOSE, ids=[c[0] for c in TRANSPOSE])
@@ -61,7 +31,8 @@ def test_transpose_entry_by_entry(gpu, case):
     pattern exactly, and every entry within (2 n + 8) u |entry| (n: the ray's sample count; per side a product of three
     weights, a sum of at most n sample terms and two scalings)."""
     name, scanner, det, n, s, ctr, angles, acc = case
-    views, fwd, bwd = _matrices(gpu, scanner, det, n, s, ctr, angles, acc)
+    views = [S.make_view(a, det, scanner) for a in angles]
+    fwd, bwd = (m.astype(np.float64) for m in one_hot_matrices(gpu, views, det, n, s, ctr, acc))   # exact widening
     assert np.array_equal(fwd == 0, bwd == 0), (name, int(((fwd == 0) != (bwd == 0)).sum()))
     rays32 = K.ray_params(views, s, ctr, n)
     ref = PR.project(np.zeros(n), rays32, views[0].mode == 1, np.asarray(s) / np.asarray(n), acc, *det)
@@ -98,29 +69,11 @@ def test_dot_test_128(gpu):
     assert abs(lhs - rhs) <= bound, st
 
 
-def _tiny_cfg(mode="cone", n=(6, 5, 7), det=(9, 10), sVoxel=(1.9, 1.7, 2.0), off=(0.05, -0.04, 0.03)):
-    base = S.CONE_BEAM if mode == "cone" else S.PARALLEL_BEAM
-    return dict(base, nVoxel=list(n), nDetector=list(det), sVoxel=list(sVoxel), offOrigin=list(off), sDetector=[3.4, 3.6],
-                accuracy=0.5, filter=None)
-
-
-TINY_ANGLES = np.linspace(0, 2 * np.pi, 7)[:-1] + 0.21
-
-
 def _tiny_system(mode):
     cfg = _tiny_cfg(mode)
     A, bd = RR.dense_A_cfg(cfg, TINY_ANGLES)
     assert not bd.any(), "a ray of the tiny geometry sits on an n or hit/miss boundary: choose another"
-    n = tuple(cfg["nVoxel"])
-    ax = [(np.arange(m) + 0.5) / m * 2 - 1 for m in n]
-    X, Y, Z = np.meshgrid(*ax, indexing="ij")
-    truth = (0.6 * np.exp(-(X ** 2 + Y ** 2 + Z ** 2) / 0.4) + 0.3 * ((X - 0.3) ** 2 + Y ** 2 < 0.1)).astype(np.float32)
-    b = (A @ truth.ravel().astype(np.float64)).astype(np.float32)
-    rng = np.random.RandomState(5)
-    # multiplicative noise: a ray that only grazes the volume keeps a residual of its own size (an additive one would be
-    # amplified by W = 1 / (A 1) into an ill-conditioned comparison)
-    b = (b * (1.0 + 0.01 * rng.normal(0, 1, b.shape))).astype(np.float32)
-    return cfg, A, b, n
+    return cfg, A, tiny_system(cfg, A), tuple(cfg["nVoxel"])
 
 
 def _rel(a, b):

@@ -17,7 +17,7 @@ from r2_gaussian_amd import scene as S
 from tests import helpers as Hh
 from tests import recon_ref as RR
 from tests import siddon_ref as SR
-from tests.test_recon_gpu import TINY_ANGLES, TRANSPOSE, _tiny_cfg
+from tests.operator_cases import TINY_ANGLES, TRANSPOSE, _tiny_cfg, one_hot_matrices, tiny_system
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -39,15 +39,11 @@ ALIGNED = np.array([
 
 def _aligned_forward(vol, dev):
     H, W = ALIGNED_DET
-    rays = torch.from_numpy(ALIGNED).to(dev)
-    out = torch.empty((len(ALIGNED), H, W), device=dev)
-    return RC._project_rays(vol, rays, False, H, W, (1.0, 1.0, 1.0), 0.5, out, SID)
+    return K.project_rays(vol, ALIGNED, False, H, W, (1.0, 1.0, 1.0), projection_type=SID)
 
 
 def _aligned_adjoint(p, dev):
-    rays = torch.from_numpy(ALIGNED).to(dev)
-    out = torch.empty(ALIGNED_N, device=dev)
-    return RC._backproject_rays(p, rays, False, ALIGNED_N, (1.0, 1.0, 1.0), 0.5, out, SID)
+    return K.backproject_rays(p, ALIGNED, False, ALIGNED_N, (1.0, 1.0, 1.0), projection_type=SID)
 
 
 def _check(got, ref, label):
@@ -133,26 +129,6 @@ def test_constant_volume_is_the_chord_and_separates_the_models(gpu, case):
     assert st["hits"] > 0 and over.any() and np.median(err[hit]) > np.median(ref["bound"][hit]), info
 
 
-def _matrices(dev, views, det, n, s, ctr):
-    H, W = det
-    N, M = int(np.prod(n)), len(views) * H * W
-    fwd = np.zeros((M, N), np.float32)
-    vol = torch.zeros(N, device=dev)
-    for v in range(N):
-        vol.zero_()
-        vol[v] = 1.0
-        fwd[:, v] = K.project_views(vol.reshape(n), views, s, ctr, projection_type=SID).reshape(-1).cpu().numpy()
-    bwd = np.zeros((M, N), np.float32)
-    pr = torch.zeros(M, device=dev)
-    out = torch.empty(n, device=dev)
-    for r in range(M):
-        pr.zero_()
-        pr[r] = 1.0
-        bwd[r] = RC.backproject_views(pr.reshape(len(views), H, W), views, s, ctr, out=out,
-                                      projection_type=SID).reshape(-1).cpu().numpy()
-    return fwd, bwd
-
-
 def _same_bits(fwd, bwd, label):
     st = {"nonzero": int((fwd != 0).sum()), "pattern_differs": int(((fwd == 0) != (bwd == 0)).sum()),
           "entries_differ": int((fwd.view(np.uint32) != bwd.view(np.uint32)).sum()),
@@ -172,7 +148,7 @@ def test_transpose_bit_for_bit(gpu, case):
     restatement's dense matrix within (8 u + the entry's endpoint errors)."""
     name, scanner, det, n, s, ctr, angles, _ = case
     views = [S.make_view(a, det, scanner) for a in angles]
-    fwd, bwd = _matrices(gpu, views, det, n, s, ctr)
+    fwd, bwd = one_hot_matrices(gpu, views, det, n, s, ctr, projection_type=SID)
     st = _same_bits(fwd, bwd, "transpose " + name)
     if "misses" in name:
         assert st["rays_missing"] > 0.2 * st["rays"]
@@ -253,14 +229,7 @@ def test_bit_reproducible_and_independent_of_the_batch(gpu):
 def _tiny_system(mode):
     cfg = _tiny_cfg(mode)
     A = SR.dense_A_cfg(cfg, TINY_ANGLES)
-    n = tuple(cfg["nVoxel"])
-    ax = [(np.arange(m) + 0.5) / m * 2 - 1 for m in n]
-    X, Y, Z = np.meshgrid(*ax, indexing="ij")
-    truth = (0.6 * np.exp(-(X ** 2 + Y ** 2 + Z ** 2) / 0.4) + 0.3 * ((X - 0.3) ** 2 + Y ** 2 < 0.1)).astype(np.float32)
-    b = (A @ truth.ravel().astype(np.float64)).astype(np.float32)
-    rng = np.random.RandomState(5)
-    b = (b * (1.0 + 0.01 * rng.normal(0, 1, b.shape))).astype(np.float32)   # multiplicative, as in test_recon_gpu.py
-    return cfg, A, b
+    return cfg, A, tiny_system(cfg, A)
 
 
 def _rel(a, b):
