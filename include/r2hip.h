@@ -489,6 +489,48 @@ R2_API int r2_project_gaussians_backward(int V, int H, int W, const float *rays 
                                          float *dL_ddensity /* [P] */, float *dL_dscales /* [P,3] */,
                                          float *dL_drotations /* [P,4] */, void *stream);
 
+/* ---- exact evaluation of the Gaussian density field at caller-supplied points (no counterpart in the reference, whose only
+ * 3D evaluation is the voxelizer: one axis-aligned grid, every Gaussian cut at a cube of ceil(3 max(scale) / dVoxel) voxels
+ * and at alpha >= 1e-6) -----------------------------------------------------------------------------------------------------
+ * r2_query_gaussians: out[n] = the sum over the P Gaussians of rho exp(-q / 2) at points[n] ([N,3], world (scene)
+ * coordinates).  One (Gaussian, point) pair: mean mu, density rho, sigma = scale_modifier * scales (3), quaternion
+ * (r, x, y, z) used AS IT COMES (not normalised; the rasterizer's quat_to_rot), R its matrix.  With
+ *     e = x - mu,   w = S^-1 R^T e,   q = w.w,   term = rho exp(-q / 2).
+ * Culling: a pair with q <= 32 is always summed; a pair with q > 32 (below exp(-16) of that Gaussian's peak) is summed or
+ * skipped by one rule that the forward and both backwards share (csrc/gaussian_points.hpp).  That rule cuts per pair, at a
+ * float32 q of 32.001, so that values and gradients do not depend on the order of the points; in front of it, and without
+ * effect on any bit, the points are taken in blocks of 256 consecutive ones, a block skips a Gaussian whose sphere of radius
+ * 1.01 sqrt(32) sigma_max / s_min(R) around mu (s_min = 1 for a unit quaternion; csrc/gaussian_rays.hpp) misses the
+ * axis-aligned box of the block's finite points, and a point skips a Gaussian whose sphere it lies outside.  Coherent point
+ * sets (planes, lines, patches) therefore cost far less than scattered ones.
+ * Every pair of a Gaussian with a non-finite parameter or a scale <= 0 contributes 0, and so does a pair whose q is not
+ * a number.  A point with a non-finite coordinate gets out = 0 and zero gradients, and does not enter its block's box.  P = 0
+ * writes zeros; N = 0 returns success and touches nothing.  N < 2^31, P <= 2^29.
+ * out[n] adds its pairs in ascending Gaussian index in one thread: no atomics, no workspace, no allocation and no host
+ * synchronisation; bit-reproducible.  All arithmetic is separately rounded float32 in the order written above.
+ * r2_query_gaussians_backward: given G = dL/dout [N], the gradients of L with respect to means [P,3], density [P], scales
+ * [P,3] (the unmodified ones: the scale_modifier factor is included) and rotations [P,4] (the quaternion as given, no
+ * normalisation Jacobian), and, if dL_dpoints is not NULL, with respect to the points [N,3].  Per pair, with g_w = -term w:
+ *     d rho = exp(-q / 2) (no division by rho),   d mu = -R S^-1 g_w,   d x = +R S^-1 g_w,   d scale_i = -g_w,i w_i / scale_i,
+ *     d R = e (x) S^-1 g_w,   d quaternion = the derivative of quat_to_rot applied to d R,
+ * each times G[n].  A pair is differentiated exactly when the forward summed it (same boxes, same sphere, same arithmetic:
+ * the header is shared).  Parameter gradients are Gaussian-major: a first kernel writes the block boxes into `workspace`
+ * (r2_query_gaussians_workspace_bytes(N) = 24 bytes per block of 256 points; NULL or fewer bytes with N > 0: R2_ERR_INVALID
+ * and a message), then one wave per Gaussian tests the boxes 64 at a time, walks the blocks that meet its sphere in
+ * ascending order and adds its 64 partial sums in a fixed order; every output element is written, exact zeros for a
+ * Gaussian no point touches (all of them when N = 0).  Point gradients are point-major, in the forward's order.  No atomics,
+ * no allocation, no host synchronisation; bit-reproducible. */
+R2_API int r2_query_gaussians(int N, const float *points /* [N,3] */, int P, const float *means /* [P,3] */,
+                              const float *density /* [P] */, const float *scales /* [P,3] */, float scale_modifier,
+                              const float *rotations /* [P,4] */, float *out /* [N] */, void *stream);
+R2_API size_t r2_query_gaussians_workspace_bytes(int N);
+R2_API int r2_query_gaussians_backward(int N, const float *points /* [N,3] */, int P, const float *means, const float *density,
+                                       const float *scales, float scale_modifier, const float *rotations,
+                                       const float *dL_dout /* [N] */, float *dL_dmeans /* [P,3] */, float *dL_ddensity /* [P] */,
+                                       float *dL_dscales /* [P,3] */, float *dL_drotations /* [P,4] */,
+                                       float *dL_dpoints /* [N,3] or NULL */, void *workspace, size_t workspace_bytes,
+                                       void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -53,6 +53,9 @@ SOURCES = {
     # tests' tolerance (tests/gaussian_project_ref.py), and forward and backward round a pair identically (gaussian_rays.hpp)
     "gaussian_project.hip": EXACT,
     "gaussian_project_bwd.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_field_ref.py, gaussian_points.hpp)
+    "gaussian_query.hip": EXACT,
+    "gaussian_query_bwd.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

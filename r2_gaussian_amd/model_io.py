@@ -115,14 +115,17 @@ def metric_vol(vol_gt, vol_pred, metric="psnr", pixel_max=1.0):
 
 
 @torch.no_grad()
-def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="host", exact_views=None, exact_projs=None):
+def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="host", exact_views=None, exact_projs=None,
+                    exact_field=False):
     """query() of render_query.py:27-77 at the scanner's full resolution on the HIP voxelizer, + test.py's 3D metrics.
     model: dict from load_point_cloud (raw parameters).  -> dict(vol, psnr_3d, ssim_3d, ...).
     metrics="device": the metrics on the HIP kernels (r2_gaussian_amd.metrics, one host sync, the reference's NaN when no
     slice of an axis counts); "host": the torch restatement above on a CPU copy.
     exact_views (scene.View list) with exact_projs [V,H,W] (the measured projections in scene units): also the 2D metrics of the
     model's exact projections (gaussian_projector.project_gaussians) against them, as psnr_2d_exact / ssim_2d_exact (+ _projs)
-    and the projections themselves as projs_exact."""
+    and the projections themselves as projs_exact.
+    exact_field: also the model's density field itself at the voxel centres (field.query_points: no cube, no alpha cut) as
+    vol_exact, and with vol_gt its 3D metrics as psnr_3d_exact / ssim_3d_exact.  Off by default; nothing else changes."""
     assert metrics in ("host", "device")
     from .voxelization import GaussianVoxelizationSettings, GaussianVoxelizer
     xyz, dens, scal, rot = activate(model)
@@ -151,4 +154,14 @@ def evaluate_volume(model, scanner_cfg, vol_gt=None, save_dir=None, metrics="hos
             gts = torch.as_tensor(np.asarray(_np(exact_projs)), dtype=torch.float32).to(pe.device).permute(1, 2, 0)
             out["psnr_2d_exact"], out["psnr_2d_exact_projs"] = metric_proj(gts, pe.permute(1, 2, 0), "psnr")
             out["ssim_2d_exact"], out["ssim_2d_exact_projs"] = metric_proj(gts, pe.permute(1, 2, 0), "ssim")
+    if exact_field:
+        from .field import query_points, voxel_centres
+        out["vol_exact"] = ve = query_points(voxel_centres(c, n, s, vol.device), xyz, dens, scal, rot)
+        if vol_gt is not None:
+            if metrics == "device":
+                from .metrics import metric_vol_both
+                out["psnr_3d_exact"], out["ssim_3d_exact"], _ = metric_vol_both(gt, ve)
+            else:
+                out["psnr_3d_exact"] = metric_vol(gt, ve, "psnr")[0]
+                out["ssim_3d_exact"] = metric_vol(gt.cpu(), ve.cpu(), "ssim")[0]
     return out
