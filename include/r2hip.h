@@ -488,6 +488,30 @@ R2_API int r2_project_gaussians_backward(int V, int H, int W, const float *rays 
                                          const float *rotations, const float *dL_dout /* [V,H,W] */, float *dL_dmeans /* [P,3] */,
                                          float *dL_ddensity /* [P] */, float *dL_dscales /* [P,3] */,
                                          float *dL_drotations /* [P,4] */, void *stream);
+/* r2_project_gaussians_rays_backward: given G = dL/dout [V,H,W], the gradient of L with respect to rays [V,12] = {a, p00, pu,
+ * pv}, the cloud held fixed.  A pair is differentiated exactly when the forward summed it (same rectangle, same cone rule,
+ * same pair: csrc/gaussian_rays.hpp).  Per pair, with T, g_w, g_u as above, M = S^-1 R^T and G of the pixel:
+ *     g_s = (G |d|) M^T g_w                                (the ray start; the negative of d mu above)
+ *     g_d = (G |d|) M^T g_u + ((G T) / |d|) d              (the ray direction; the second term is the derivative of |d|)
+ * A pixel (r, c) adds g_s and g_d over its pairs in ascending Gaussian index, in one thread, and with P = p00 + c pu + r pv
+ * hands on  g_P = g_d, g_a = g_s - g_d  in cone beam (s = a, d = P - a)  and  g_P = g_s, g_a = g_d  in parallel beam (s = P,
+ * d = a).  Over the pixels of view v:
+ *     dL/da = sum g_a,    dL/dp00 = sum g_P,    dL/dpu = sum c g_P,    dL/dpv = sum r g_P.
+ * NOT differentiated, being piecewise constant in the rays: which pairs are summed -- the rectangle and with it the cut of
+ * the terms with q > 32, each below exp(-16) of its Gaussian's peak -- and the cone rule t* <= 0.
+ * Pixel-major: one workgroup per 16 x 16 tile and view adds its 256 x 12 values in one fixed order into
+ * partial[view][tile][12] in `workspace` (r2_project_gaussians_rays_backward_workspace_bytes(V, H, W) = 48 bytes per tile and
+ * view; NULL or fewer bytes with P > 0: R2_ERR_INVALID and a message, nothing written), then one workgroup per view adds
+ * that view's tiles in one fixed order.  dL_drays is always fully written; P = 0 writes zeros and needs no workspace.  No
+ * atomics, no allocation and no host synchronisation; bit-reproducible, and a view's twelve numbers do not depend on the
+ * other views of the call.  All arithmetic is separately rounded float32 in the order written above.  V <= 65535,
+ * P <= 2^29, H * W < 2^30. */
+R2_API size_t r2_project_gaussians_rays_backward_workspace_bytes(int V, int H, int W);
+R2_API int r2_project_gaussians_rays_backward(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                              const float *means, const float *density, const float *scales,
+                                              float scale_modifier, const float *rotations, const float *dL_dout /* [V,H,W] */,
+                                              float *dL_drays /* [V,12] */, void *workspace, size_t workspace_bytes,
+                                              void *stream);
 
 /* ---- exact evaluation of the Gaussian density field at caller-supplied points (no counterpart in the reference, whose only
  * 3D evaluation is the voxelizer: one axis-aligned grid, every Gaussian cut at a cube of ceil(3 max(scale) / dVoxel) voxels

@@ -77,6 +77,8 @@ _SIGNATURES = {
     "r2_backproject_volume_siddon": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _p]),
     "r2_project_gaussians": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
     "r2_project_gaussians_backward": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
+    "r2_project_gaussians_rays_backward_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "r2_project_gaussians_rays_backward": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _p, C.c_size_t, _p]),
     "r2_query_gaussians": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
     "r2_query_gaussians_workspace_bytes": (C.c_size_t, [_i]),
     "r2_query_gaussians_backward": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _p, C.c_size_t, _p]),

@@ -53,6 +53,8 @@ SOURCES = {
     # tests' tolerance (tests/gaussian_project_ref.py), and forward and backward round a pair identically (gaussian_rays.hpp)
     "gaussian_project.hip": EXACT,
     "gaussian_project_bwd.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_project_rays_ref.py, gaussian_ray_grad.hpp on gaussian_rays.hpp)
+    "gaussian_project_rays_bwd.hip": EXACT,
     # EXACT for the same two reasons (tests/gaussian_field_ref.py, gaussian_points.hpp)
     "gaussian_query.hip": EXACT,
     "gaussian_query_bwd.hip": EXACT,

@@ -1,6 +1,6 @@
 """Exact projection of the Gaussian model: the line integrals of the cloud itself along the rays of every detector pixel, on
-the kernels of csrc/gaussian_project.hip and csrc/gaussian_project_bwd.hip (``r2_project_gaussians`` and its backward;
-include/r2hip.h states the contract).
+the kernels of csrc/gaussian_project.hip, csrc/gaussian_project_bwd.hip and csrc/gaussian_project_rays_bwd.hip
+(``r2_project_gaussians`` and its two backwards; include/r2hip.h states the contract).
 
 The splatting rasterizer is the reference's approximation of this image: affine at each Gaussian's centre in cone beam, cut
 at a square of ceil(3 sigma_max) pixels, culled at the near plane.  Here every (Gaussian, ray) pair is the closed-form integral
@@ -33,6 +33,7 @@ class _ProjectGaussians(torch.autograd.Function):
     def forward(ctx, xyz, density, scaling, rotation, rays, cone, H, W, scale_modifier, out):
         V, P = rays.shape[0], xyz.shape[0]
         x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+        rays = rays.detach()
         with _on_device(x.device):
             rc = _lib.lib().r2_project_gaussians(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
                                                  float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(x.device))
@@ -48,21 +49,35 @@ class _ProjectGaussians(torch.autograd.Function):
         cone, H, W, mod = ctx.args
         V, P = rays.shape[0], x.shape[0]
         G = _f32c(G)
-        gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
-        with _on_device(x.device):
-            rc = _lib.lib().r2_project_gaussians_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
-                                                          s.data_ptr(), mod, r.data_ptr(), G.data_ptr(), gx.data_ptr(),
-                                                          gd.data_ptr(), gs.data_ptr(), gr.data_ptr(), _stream(x.device))
-        _lib.check(rc, "r2_project_gaussians_backward")
-        return gx, gd, gs, gr, None, None, None, None, None, None
+        L = _lib.lib()
+        gx = gd = gs = gr = grays = None
+        if any(ctx.needs_input_grad[:4]):
+            gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
+            with _on_device(x.device):
+                rc = L.r2_project_gaussians_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                                     mod, r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(),
+                                                     gr.data_ptr(), _stream(x.device))
+            _lib.check(rc, "r2_project_gaussians_backward")
+        if ctx.needs_input_grad[4]:
+            grays = torch.empty_like(rays)
+            ws = torch.empty((max(int(L.r2_project_gaussians_rays_backward_workspace_bytes(V, H, W)), 1),), dtype=torch.uint8,
+                             device=x.device)
+            with _on_device(x.device):
+                rc = L.r2_project_gaussians_rays_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
+                                                          s.data_ptr(), mod, r.data_ptr(), G.data_ptr(), grays.data_ptr(),
+                                                          ws.data_ptr(), ws.numel(), _stream(x.device))
+            _lib.check(rc, "r2_project_gaussians_rays_backward")
+        return gx, gd, gs, gr, grays, None, None, None, None, None
 
 
 def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
     """Exact projections [V,H,W] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
     ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along caller-supplied rays: ``rays`` [V,12]
     {a, p00, pu, pv} in world coordinates (include/r2hip.h), ``cone`` the beam (True: from the source a through the pixel
-    points; False: through the pixel points along a).  Differentiable in the four parameter tensors.  No host
-    synchronisation; ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
+    points; False: through the pixel points along a).  Differentiable in the four parameter tensors, and in ``rays`` when they
+    require grad (``r2_project_gaussians_rays_backward``, launched only then): a ``rays`` tensor on the device or on the host,
+    of any float dtype, receives its gradient where and as it is.  No host synchronisation (host rays that require grad are
+    copied synchronously); ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
     rays = torch.as_tensor(rays)
     if rays.dim() != 2 or rays.shape[1] != 12 or rays.shape[0] < 1:
         raise ValueError("rays must be [V,12] with V >= 1, got shape %s" % (tuple(rays.shape),))
@@ -86,7 +101,10 @@ def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, sc
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != _F32 or not out.is_cuda or not out.is_contiguous()
                             or tuple(out.shape) != (V, H, W) or out.device != xyz.device):
         raise ValueError("out must be a contiguous float32 tensor [%d,%d,%d] on %s" % (V, H, W, xyz.device))
-    rays = projector.device_rays(rays, xyz.device)
+    if rays.requires_grad:   # differentiable torch ops carry the gradient back to the caller's tensor, device and dtype
+        rays = rays.to(device=xyz.device, dtype=_F32).contiguous()
+    else:
+        rays = projector.device_rays(rays, xyz.device)
     if out is None:
         out = torch.empty((V, H, W), dtype=_F32, device=xyz.device)
     return _ProjectGaussians.apply(xyz, density, scaling, rotation, rays, int(bool(cone)), H, W, float(scale_modifier), out)

@@ -1,0 +1,147 @@
+"""Scan geometry as differentiable ray parameters, and its refinement against the model's exact projection.
+
+``scan_rays`` builds the [V,12] world rays {a, p00, pu, pv} (include/r2hip.h) of a circular scan whose detector may be shifted
+in its plane, rolled about its normal and tilted about its two axes, view by view, with jittered angles -- what
+``scene.make_view`` (and with it ``gaussian_projector.world_ray_params``) cannot describe.  It is torch, float64 inside, and
+differentiable in every continuous argument; ``gaussian_projector.project_gaussians_rays`` is differentiable in its rays
+(``r2_project_gaussians_rays_backward``), so a loss on exact projections reaches the geometry.  ``refine_geometry`` is that
+loop: the cloud held fixed, Adam on the chosen geometry parameters.
+"""
+import torch
+
+_F64 = torch.float64
+
+
+def _per_view(x, V, device):
+    """A scalar or a per-view tensor [V] as a float64 tensor [V] on ``device``."""
+    t = x.to(device=device, dtype=_F64) if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=_F64, device=device)
+    if t.dim() > 1 or (t.dim() == 1 and t.shape[0] not in (1, V)):
+        raise ValueError("a geometry argument must be a scalar or a tensor [V] with V = %d, got shape %s" % (V, tuple(t.shape)))
+    return t.reshape(-1).expand(V)
+
+
+def _several(x, n, name, V, device):
+    if isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[-1] == n:
+        x = x.unbind(-1)
+    if len(x) != n:
+        raise ValueError("%s must have %d entries" % (name, n))
+    return [_per_view(e, V, device) for e in x]
+
+
+def scan_rays(angles, DSO, DSD, dDetector, nDetector, offDetector=(0.0, 0.0), roll=0.0, tilt=(0.0, 0.0),
+              offOrigin=(0.0, 0.0, 0.0), mode="cone", d_angle=None):
+    """[V,12] float64 world rays {a, p00, pu, pv} of a circular scan about the z axis.
+
+    ``angles`` [V] (plus ``d_angle``, a per-view correction, when given); ``DSO`` / ``DSD`` the source-to-axis and
+    source-to-detector distances; ``dDetector`` = (row pitch, column pitch) and ``nDetector`` = (H, W), in the order of the
+    scanner configs (``scene.CONE_BEAM``: sDetector = nDetector * dDetector); lengths in world (scene) units, so a raw scanner
+    config is scaled first (``scanner_args``).  Every continuous argument is a scalar or a per-view tensor [V] (the pairs and
+    the triple: sequences of such, or tensors [..., n]) and is differentiated when it requires grad.
+
+    The source of view i sits at DSO (cos t, sin t, 0), t = angles_i + d_angle_i; the detector frame is
+    eu = (-sin t, cos t, 0) (columns), ev = (0, 0, -1) (rows), en = (-cos t, -sin t, 0) (from the source to the axis), as
+    ``scene.make_view`` has it.  The detector is rotated about its centre by Rn(roll) Ru(tilt[0]) Rv(tilt[1]) (about its
+    normal, then its column axis, then its row axis, angles in radians, right-handed in (eu, ev, en)), then moved by
+    offDetector = (along its rows' direction ev', along its columns' direction eu') in its own rotated plane.  ``offOrigin``
+    (x, y, z) is the position of the object relative to the rotation centre: in world coordinates, which are the object's,
+    source and detector move by -offOrigin.  Pixel (r, c) is the point p00 + c pu + r pv.
+
+    ``mode="cone"``: a = the source, and the detector is drawn towards the source by the factor 1 / DSD (the rays are the same
+    lines), which is where ``world_ray_params`` puts it.  ``mode="parallel"``: a = en, the common direction, and the detector
+    plane passes through the source position; DSD does not enter.  At offDetector = roll = tilt = offOrigin = 0 the result
+    restates ``world_ray_params([make_view(t, nDetector, scanner)])`` for the lengths ``scanner_args`` takes from ``scanner``.
+    """
+    if mode not in ("cone", "parallel"):
+        raise ValueError("mode must be 'cone' or 'parallel', got %r" % (mode,))
+    H, W = int(nDetector[0]), int(nDetector[1])
+    if H < 1 or W < 1:
+        raise ValueError("the detector must have at least one pixel, got %d x %d" % (H, W))
+    tensors = [x for x in (angles, d_angle, DSO, DSD, roll) if isinstance(x, torch.Tensor)]
+    for group in (dDetector, offDetector, tilt, offOrigin):
+        tensors += [x for x in ([group] if isinstance(group, torch.Tensor) else group) if isinstance(x, torch.Tensor)]
+    device = tensors[0].device if tensors else torch.device("cpu")
+    ang = (angles.to(device=device, dtype=_F64) if isinstance(angles, torch.Tensor)
+           else torch.as_tensor(angles, dtype=_F64, device=device)).reshape(-1)
+    V = ang.shape[0]
+    if V < 1:
+        raise ValueError("no views")
+    if d_angle is not None:
+        ang = ang + _per_view(d_angle, V, device)
+    DSO, DSD, roll = (_per_view(x, V, device) for x in (DSO, DSD, roll))
+    dV, dU = _several(dDetector, 2, "dDetector", V, device)
+    oV, oU = _several(offDetector, 2, "offDetector", V, device)
+    tU, tV = _several(tilt, 2, "tilt", V, device)
+    org = torch.stack(_several(offOrigin, 3, "offOrigin", V, device), 1)
+    c, s = torch.cos(ang), torch.sin(ang)
+    zero, one = torch.zeros_like(c), torch.ones_like(c)
+    eu = torch.stack([-s, c, zero], 1)
+    ev = torch.stack([zero, zero, -one], 1)
+    en = torch.stack([-c, -s, zero], 1)
+    # the first two columns of Rn(roll) Ru(tU) Rv(tV) in the frame (eu, ev, en)
+    cr, sr, cu, su, cv, sv = torch.cos(roll), torch.sin(roll), torch.cos(tU), torch.sin(tU), torch.cos(tV), torch.sin(tV)
+    col_u = (cr * cv - sr * su * sv, sr * cv + cr * su * sv, -cu * sv)
+    col_v = (-sr * cu, cr * cu, su)
+    fu = col_u[0][:, None] * eu + col_u[1][:, None] * ev + col_u[2][:, None] * en
+    fv = col_v[0][:, None] * eu + col_v[1][:, None] * ev + col_v[2][:, None] * en
+    src = DSO[:, None] * torch.stack([c, s, zero], 1) - org
+    centre = src + DSD[:, None] * en if mode == "cone" else src
+    centre = centre + oU[:, None] * fu + oV[:, None] * fv
+    pu, pv = dU[:, None] * fu, dV[:, None] * fv
+    p00 = centre + (0.5 - 0.5 * W) * pu + (0.5 - 0.5 * H) * pv
+    if mode == "cone":
+        k = 1.0 / DSD[:, None]
+        return torch.cat([src, src + (p00 - src) * k, pu * k, pv * k], 1)
+    return torch.cat([en, p00, pu, pv], 1)
+
+
+def scanner_args(scanner, nDetector):
+    """The keyword arguments of ``scan_rays`` that describe ``scanner`` (a config such as ``scene.CONE_BEAM``) on a detector
+    of ``nDetector`` = (H, W) pixels, in world units: lengths times the scene scale 2 / max(sVoxel), as ``scene.make_view``
+    scales them.  ``offDetector`` and ``offOrigin`` are the config's, which ``make_view`` ignores.  Parallel beam: the
+    rasterizer's parallel detector spans the view-space square [-1, 1]^2 whatever sDetector says (projector.py), and so does
+    this one."""
+    scale = 2.0 / max(scanner["sVoxel"])
+    H, W = int(nDetector[0]), int(nDetector[1])
+    sDet = [s * scale for s in scanner["sDetector"]] if scanner["mode"] == "cone" else [2.0, 2.0]
+    return dict(DSO=scanner["DSO"] * scale, DSD=scanner["DSD"] * scale, dDetector=(sDet[0] / H, sDet[1] / W), nDetector=(H, W),
+                offDetector=tuple(o * scale for o in scanner.get("offDetector", (0.0, 0.0))),
+                offOrigin=tuple(o * scale for o in scanner.get("offOrigin", (0.0, 0.0, 0.0))), mode=scanner["mode"])
+
+
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
+
+
+def refine_geometry(projs, cloud, rays_fn, params, iters, lr, loss="l2", cone=True, callback=None):
+    """Geometric self-calibration: minimise the error of the cloud's exact projection against ``projs`` [V,H,W] (GPU) over
+    the geometry, the cloud held fixed.
+
+    ``cloud`` = (xyz, density, scaling, rotation), activated GPU tensors; ``params``: a dict of tensors, the starting values
+    of the parameters to refine (copied; keep them on the cloud's device to avoid copies in the loop); ``rays_fn(params)``
+    -> rays [V,12], differentiable torch code, typically ``scan_rays`` with some arguments taken from the dict.  Each of the
+    ``iters`` steps projects exactly along rays_fn(params), takes ``loss`` ("l2": mean squared error, "l1": mean absolute
+    error) and makes one step of torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, learning rate ``lr``) on the parameters.
+    -> (refined parameters: a dict of detached tensors, loss history: a tensor [iters] on the device, the loss BEFORE each
+    step).  Nothing in the loop waits for the device; ``callback(step, loss, params)``, when given, runs after every step and
+    may.
+    """
+    from .gaussian_projector import project_gaussians_rays
+    if loss not in ("l2", "l1"):
+        raise ValueError("loss must be 'l2' or 'l1', got %r" % (loss,))
+    if not isinstance(projs, torch.Tensor) or projs.dim() != 3 or not projs.is_cuda:
+        raise ValueError("projs must be a GPU tensor [V,H,W]")
+    V, H, W = projs.shape
+    cloud = tuple(t.detach() for t in cloud)
+    p = {k: torch.as_tensor(v).detach().clone().requires_grad_(True) for k, v in params.items()}
+    opt = torch.optim.Adam(list(p.values()), lr=lr, betas=ADAM_BETAS, eps=ADAM_EPS)
+    history = torch.zeros((int(iters),), dtype=torch.float32, device=projs.device)
+    target = projs.detach().to(torch.float32)
+    for it in range(int(iters)):
+        opt.zero_grad(set_to_none=True)
+        diff = project_gaussians_rays(rays_fn(p), cone, H, W, *cloud) - target
+        value = (diff * diff).mean() if loss == "l2" else diff.abs().mean()
+        value.backward()
+        opt.step()
+        history[it] = value.detach()
+        if callback is not None:
+            callback(it, value.detach(), p)
+    return {k: v.detach() for k, v in p.items()}, history
