@@ -555,6 +555,62 @@ R2_API int r2_query_gaussians_backward(int N, const float *points /* [N,3] */, i
                                        float *dL_dpoints /* [N,3] or NULL */, void *workspace, size_t workspace_bytes,
                                        void *stream);
 
+/* ---- exact line integrals of the Gaussian model along caller-supplied rays (the line form of r2_query_gaussians: curved
+ * detectors, measured pixel positions, a random subset of the pixels of many views, per-ray geometry gradients) -------------
+ * r2_integrate_gaussians: out[n] = the sum over the P Gaussians of the pair of r2_project_gaussians along ray n, given as
+ * rays[n][6] = {start s, direction d} in world (scene) coordinates; d is not normalised.  One (Gaussian, ray) pair is that
+ * projector's, operation for operation (csrc/gaussian_rays.hpp: gauss_pair): u, w, A, B, wp = w - (B / A) u, q = wp.wp formed
+ * from wp, term = rho sqrt(2 pi / A) exp(-q / 2) |d| over the WHOLE line; half_line != 0 applies the cone rule, a pair with
+ * t* = -B / A <= 0 contributes exactly 0 (and one with t* > 0 its whole-line term).
+ * Which pairs are summed is a property of the pair alone: a pair is summed when its float32 q is <= 32.001, and only then
+ * (every pair with q <= 32 is summed, and of those above, which the projector's contract leaves free, only that sliver; the
+ * cut of r2_query_gaussians, for its reason: a tail that depended on the other rays would put gradients outside the float64
+ * bracket).  A ray's value and its ray gradient therefore do not depend on which other rays are in the call or on their
+ * order, bit for bit; the parameter gradients depend on the order only through the association of their sums.
+ * Culling comes in front of the cut, saves work and changes no bit (csrc/gaussian_bundle.hpp derives every allowance below;
+ * eps = 2^-24, the allowances are 16 eps of the quantity that rounds).  (0) Two small kernels write the cloud box, the
+ * bounding box of the spheres of radius 1.01 sqrt(32) sigma_max / s_min(R) around the means (csrc/gaussian_rays.hpp:
+ * gauss_radius; Gaussians that contribute nothing are skipped, an infinite radius makes the box infinite), into the
+ * workspace: one partial box per workgroup, then their reduction; no atomics, and min / max are exact in any order.  (1) The
+ * rays are taken in blocks of 256 consecutive ones.  Each ray is clipped to the cloud box by the slab method along its unit
+ * direction, a half-line ray to t >= 0 as well (the Mahalanobis-closest point of a summed pair lies at t* > 0 and inside its
+ * sphere); bounds and t move outwards by 16 eps of themselves.  A ray that misses the cloud box sums nothing.  (2) A block's
+ * box is the bounding box of its rays' clipped end points, each moved outwards by 16 eps (|s_k| + |t|); a block skips a
+ * Gaussian whose sphere misses its box.  Any point of a line that lies in a sphere lies in the cloud box, hence on the
+ * clipped segment, hence in the block's box.  (3) A ray skips a Gaussian whose sphere its line misses,
+ * |e x d|^2 > (radius + 16 eps |e|_1)^2 |d|^2 (1 + 1e-5), e = s - mu: the cross product cancels from |e| down to the line's
+ * distance, so its rounding is relative to |e| and not to the radius, which the sphere's 1 % could not cover for a small
+ * Gaussian seen from afar.  Coherent blocks of rays (a detector tile, sorted rays) cost far less than scattered ones.
+ * A ray with a non-finite component or d = 0 (its float32 |d| is 0 or not finite) gets out = 0 and zero gradients and does
+ * not enter its block's box.  Every pair of a Gaussian with a non-finite parameter or a scale <= 0 contributes 0.  P = 0
+ * writes zeros and needs no workspace; N = 0 returns success and touches nothing.  `workspace`: r2_integrate_gaussians_
+ * workspace_bytes(N, P) bytes (24 per box: the cloud box, at most 1024 partial boxes, one box per block of 256 rays; 0 when N
+ * or P is 0), not kept between calls; NULL or fewer bytes with N > 0 and P > 0: R2_ERR_INVALID and a message, nothing
+ * written.  N < 2^31, P <= 2^29.
+ * out[n] adds its pairs in ascending Gaussian index in one thread: no atomics, no allocation, no host synchronisation;
+ * bit-reproducible.  All arithmetic is separately rounded float32 in the order written above.
+ * r2_integrate_gaussians_backward: given G = dL/dout [N], the gradients of L with respect to means [P,3], density [P], scales
+ * [P,3] and rotations [P,4] by the per-pair formulas of r2_project_gaussians_backward, and, if dL_drays is not NULL, with
+ * respect to the rays: dL_drays[n] = {sum g_s, sum g_d} over the ray's pairs in ascending Gaussian index, g_s and g_d as
+ * r2_project_gaussians_rays_backward has them, written per ray.  A pair is differentiated exactly when the forward summed it;
+ * the cut and the cone rule are piecewise constant and NOT differentiated.  Parameter gradients are Gaussian-major: a kernel
+ * writes the block boxes into the workspace, then one wave per Gaussian tests the boxes 64 at a time, walks the blocks that
+ * meet its sphere in ascending order (lane l takes rays l, l + 64, l + 128, l + 192) and adds its 64 x 11 partial sums in
+ * one fixed order; every output element is written, exact zeros for a Gaussian no ray touches (all of them when N = 0, the
+ * one thing the backward writes then).  Ray gradients are ray-major, in the forward's skeleton.  No atomics, no allocation,
+ * no host synchronisation; bit-reproducible. */
+R2_API int r2_integrate_gaussians(int N, const float *rays /* [N,6] = start s, direction d */, int half_line, int P,
+                                  const float *means /* [P,3] */, const float *density /* [P] */,
+                                  const float *scales /* [P,3] */, float scale_modifier, const float *rotations /* [P,4] */,
+                                  float *out /* [N] */, void *workspace, size_t workspace_bytes, void *stream);
+R2_API size_t r2_integrate_gaussians_workspace_bytes(int N, int P);
+R2_API int r2_integrate_gaussians_backward(int N, const float *rays /* [N,6] */, int half_line, int P, const float *means,
+                                           const float *density, const float *scales, float scale_modifier,
+                                           const float *rotations, const float *dL_dout /* [N] */, float *dL_dmeans /* [P,3] */,
+                                           float *dL_ddensity /* [P] */, float *dL_dscales /* [P,3] */,
+                                           float *dL_drotations /* [P,4] */, float *dL_drays /* [N,6] or NULL */,
+                                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

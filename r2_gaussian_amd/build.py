@@ -58,6 +58,9 @@ SOURCES = {
     # EXACT for the same two reasons (tests/gaussian_field_ref.py, gaussian_points.hpp)
     "gaussian_query.hip": EXACT,
     "gaussian_query_bwd.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_bundle_ref.py, gaussian_bundle.hpp on the three headers above)
+    "gaussian_bundle.hip": EXACT,
+    "gaussian_bundle_bwd.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

@@ -8,12 +8,15 @@ over the whole line; in cone beam a pair whose closest approach lies at or behin
 skipped when its exponent q exceeds 32 (below exp(-16) of the Gaussian's peak), and nothing is culled at a near plane.  The
 rays are the [V,12] parameters of the volume projectors (projector.py), in world coordinates, so a detector the rasterizer's
 camera cannot describe (shifted, tilted) can be projected with ``project_gaussians_rays``.
+
+``integrate_rays`` is the same line integral along rays that are no detector's: any [..., 3] starts and directions, on the
+kernels of csrc/gaussian_bundle.hip and csrc/gaussian_bundle_bwd.hip (``r2_integrate_gaussians`` and its backward).
 """
 import torch
 
 from . import _lib
 from . import projector
-from ._C import _on_device, _stream
+from ._C import _on_device, _require_gpu, _stream
 
 _F32 = torch.float32
 
@@ -116,3 +119,120 @@ def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0
     views, H, W = projector.check_views(views)
     return project_gaussians_rays(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
                                   rotation, scale_modifier, out)
+
+
+class _IntegrateRays(torch.autograd.Function):
+    """origins, directions [N,3] -> [N].  ``perm`` (or None): the order the kernels see the rays in; values and gradients
+    come back in the caller's order, by gathers alone."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm):
+        N, P = origins.shape[0], xyz.shape[0]
+        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+        rays = torch.cat([origins.detach().to(_F32), directions.detach().to(_F32)], 1)
+        inv = None
+        if perm is not None:
+            from .field import inverse_permutation
+            rays, inv = rays[perm].contiguous(), inverse_permutation(perm)
+        out = torch.empty((N,), dtype=_F32, device=x.device)
+        L = _lib.lib()
+        ws = torch.empty((max(int(L.r2_integrate_gaussians_workspace_bytes(N, P)), 1),), dtype=torch.uint8, device=x.device)
+        with _on_device(x.device):
+            rc = L.r2_integrate_gaussians(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                          float(scale_modifier), r.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream(x.device))
+        _lib.check(rc, "r2_integrate_gaussians")
+        ctx.save_for_backward(rays, x, d, s, r, perm, inv)
+        ctx.args = (float(scale_modifier), half_line)
+        return out if inv is None else out[inv]
+
+    @staticmethod
+    def backward(ctx, G):
+        rays, x, d, s, r, perm, inv = ctx.saved_tensors
+        mod, half_line = ctx.args
+        N, P = rays.shape[0], x.shape[0]
+        G = _f32c(G)
+        if perm is not None:
+            G = G[perm].contiguous()
+        gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
+        grays = torch.empty_like(rays) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None
+        L = _lib.lib()
+        ws = torch.empty((max(int(L.r2_integrate_gaussians_workspace_bytes(N, P)), 1),), dtype=torch.uint8, device=x.device)
+        with _on_device(x.device):
+            rc = L.r2_integrate_gaussians_backward(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(), mod,
+                                                   r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(),
+                                                   gr.data_ptr(), None if grays is None else grays.data_ptr(), ws.data_ptr(),
+                                                   ws.numel(), _stream(x.device))
+        _lib.check(rc, "r2_integrate_gaussians_backward")
+        go = gdir = None
+        if grays is not None:
+            if inv is not None:
+                grays = grays[inv]
+            go, gdir = grays[:, :3], grays[:, 3:]
+        return go, gdir, gx, gd, gs, gr, None, None, None
+
+
+def ray_order(origins, directions, xyz):
+    """Permutation [N] (int64) that makes blocks of consecutive rays coherent: a stable sort by a 30-bit Morton key of the
+    two points where a ray's line enters and leaves a sphere around the cloud (5 bits for each of the six coordinates; a line
+    that misses the sphere takes its closest point twice), so that rays next to each other in the order are close all the way
+    through the cloud.  The sphere: the centre of the box of the finite means, 0.55 of its diagonal.  Rays with a
+    non-finite component or no direction get key 0.  torch ops only, on the rays' device; no host synchronisation."""
+    o, d, m = origins.detach().to(torch.float64), directions.detach().to(torch.float64), xyz.detach().to(torch.float64)
+    if o.shape[0] == 0 or m.shape[0] == 0:
+        return torch.arange(o.shape[0], device=o.device)
+    big = torch.finfo(torch.float64).max
+    fin = torch.isfinite(m).all(1, keepdim=True)
+    lo = torch.where(fin, m, torch.full_like(m, big)).amin(0)
+    hi = torch.where(fin, m, torch.full_like(m, -big)).amax(0)
+    some = (hi >= lo).all()
+    centre = torch.where(some, 0.5 * lo + 0.5 * hi, torch.zeros_like(lo))
+    radius = torch.where(some, 0.55 * (hi - lo).norm(), torch.ones_like(lo[0])) + 1e-30
+    length = d.norm(dim=1, keepdim=True)
+    good = torch.isfinite(o).all(1, keepdim=True) & torch.isfinite(d).all(1, keepdim=True) & (length > 0) & torch.isfinite(length)
+    h = torch.where(good, d / torch.where(good, length, torch.ones_like(length)), torch.zeros_like(d))
+    e = torch.where(good, o - centre, torch.zeros_like(o))
+    t = -(e * h).sum(1, keepdim=True)
+    near = e + t * h
+    half = (radius * radius - (near * near).sum(1, keepdim=True)).clamp_min(0.0).sqrt()
+    ends = torch.cat([near - half * h, near + half * h], 1)
+    cell = ((ends / radius + 1.0) * 16.0).floor().clamp_(0, 31)
+    cell = torch.where(good, cell, torch.zeros_like(cell)).to(torch.int64)
+    key = torch.zeros_like(cell[:, 0])
+    for bit in range(5):
+        for j in range(6):
+            key = key | (((cell[:, j] >> bit) & 1) << (6 * bit + j))
+    return torch.sort(key, stable=True)[1]
+
+
+def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_modifier=1.0, half_line=False, sort=False):
+    """Exact line integrals [...] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
+    ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along the rays ``origins`` + t ``directions``,
+    both [..., 3] of one shape, in world coordinates; the directions need not be normalised.  A pair is the projector's:
+    the integral over the whole line, and with ``half_line`` the cone rule (a Gaussian whose closest approach lies at or
+    behind the origin contributes 0), so ``integrate_rays(*geometry.pixel_rays(rays, cone, H, W), ..., half_line=cone)`` is
+    the image of ``project_gaussians_rays`` up to which pairs beyond q = 32 are summed.  Differentiable in the four parameter
+    tensors, and in ``origins`` and ``directions`` when they require grad.  No host synchronisation.
+
+    The kernels cull by blocks of 256 consecutive rays (include/r2hip.h: r2_integrate_gaussians), so coherent inputs -- the
+    pixels of a detector tile, the columns of a curved detector -- cull well as they are.  ``sort=True`` is meant for
+    scattered rays: it orders them by ``ray_order`` before the kernels see them and un-permutes values and gradients.
+    Which pairs a ray sums does not depend on the other rays, so sorting changes the cost alone: the values and the ray
+    gradients are the same bits."""
+    for name, t in (("origins", origins), ("directions", directions)):
+        if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[-1] != 3:
+            raise ValueError("%s must be a tensor [..., 3], got %s" % (name, tuple(getattr(t, "shape", ()))))
+    if origins.shape != directions.shape:
+        raise ValueError("origins and directions differ in shape: %s, %s" % (tuple(origins.shape), tuple(directions.shape)))
+    _require_gpu(origins, "origins")
+    _require_gpu(directions, "directions")
+    from .field import _check_cloud
+    _check_cloud(xyz, density, scaling, rotation)
+    if origins.device != xyz.device or directions.device != xyz.device:
+        raise ValueError("the rays are on %s and %s, xyz on %s" % (origins.device, directions.device, xyz.device))
+    o, d = origins.reshape(-1, 3), directions.reshape(-1, 3)
+    if o.shape[0] >= (1 << 31):
+        raise ValueError("fewer than 2^31 rays, got %d" % o.shape[0])
+    perm = ray_order(o, d, xyz) if sort else None
+    out = _IntegrateRays.apply(o, d, xyz, density, scaling, rotation, float(scale_modifier), int(bool(half_line)), perm)
+    return out.reshape(origins.shape[:-1])

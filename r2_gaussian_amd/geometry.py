@@ -6,6 +6,10 @@ in its plane, rolled about its normal and tilted about its two axes, view by vie
 differentiable in every continuous argument; ``gaussian_projector.project_gaussians_rays`` is differentiable in its rays
 (``r2_project_gaussians_rays_backward``), so a loss on exact projections reaches the geometry.  ``refine_geometry`` is that
 loop: the cloud held fixed, Adam on the chosen geometry parameters.
+
+``pixel_rays`` turns [V,12] views into per-pixel starts and directions, the whole detector or chosen pixels, and
+``curved_detector_rays`` builds those of an equiangular cylindrical detector, for ``gaussian_projector.integrate_rays``,
+which takes any rays and is differentiable in them.
 """
 import torch
 
@@ -92,6 +96,81 @@ def scan_rays(angles, DSO, DSD, dDetector, nDetector, offDetector=(0.0, 0.0), ro
         k = 1.0 / DSD[:, None]
         return torch.cat([src, src + (p00 - src) * k, pu * k, pv * k], 1)
     return torch.cat([en, p00, pu, pv], 1)
+
+
+def pixel_rays(rays, cone, H, W, rows=None, cols=None):
+    """(origins, directions), each [V, ..., 3]: the rays of detector pixels of the views ``rays`` [V,12] = {a, p00, pu, pv}, by
+    the formula the kernels read them with (csrc/ray_sampling.hpp: pixel_ray).  Pixel (r, c) is the point
+    P = (p00 + c pu) + r pv; ``cone``: start a, direction P - a; parallel beam: start P, direction a.  Plain torch in the
+    dtype and on the device of ``rays``, one rounded operation per step in that order (float32 rays give the projector's own
+    rays bit for bit), and differentiable in ``rays``.
+
+    ``rows`` = ``cols`` = None: the whole detector, [V,H,W,3].  Otherwise two integer tensors of one shape [V, ...] or
+    [1, ...]: view v takes the pixels (rows[v], cols[v]) (the same ones in every view when the leading size is 1), and the
+    result is [V, ..., 3].  A random subset of K pixels per view is rows, cols [V,K]; scattered (view, r, c) triples are
+    ``pixel_rays(rays[view], cone, H, W, r[:, None], c[:, None])``."""
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 12 or not rays.is_floating_point():
+        raise ValueError("rays must be a float tensor [V,12], got %s" % (tuple(getattr(rays, "shape", ())),))
+    H, W, V = int(H), int(W), rays.shape[0]
+    if H < 1 or W < 1:
+        raise ValueError("the detector must have at least one pixel, got %d x %d" % (H, W))
+    if (rows is None) != (cols is None):
+        raise ValueError("rows and cols come together")
+    if rows is None:
+        r = torch.arange(H, device=rays.device)[None, :, None].expand(1, H, W)
+        c = torch.arange(W, device=rays.device)[None, None, :].expand(1, H, W)
+    else:
+        r, c = torch.as_tensor(rows, device=rays.device), torch.as_tensor(cols, device=rays.device)
+        if r.shape != c.shape or r.dim() < 1 or r.shape[0] not in (1, V) or r.is_floating_point() or c.is_floating_point():
+            raise ValueError("rows and cols must be integer tensors of one shape [V, ...] or [1, ...] with V = %d, got %s and %s"
+                             % (V, tuple(r.shape), tuple(c.shape)))
+    par = rays.reshape((V,) + (1,) * (r.dim() - 1) + (12,))
+    fr, fc = r.to(rays.dtype)[..., None], c.to(rays.dtype)[..., None]
+    point = (par[..., 3:6] + fc * par[..., 6:9]) + fr * par[..., 9:12]
+    a = par[..., 0:3].expand_as(point)
+    if cone:
+        return a, point - a
+    return point, a
+
+
+def curved_detector_rays(angles, DSO, DSD, dGamma, dV, nDetector, offDetector=(0.0, 0.0)):
+    """(origins, directions), each [V,H,W,3] float64: the rays of a circular scan about the z axis with an equiangular
+    cylindrical detector focused on the source (the third-generation CT detector), which no [V,12] describes.
+
+    ``angles`` [V]; ``DSO`` / ``DSD`` the source-to-axis and source-to-detector distances (the cylinder's radius);
+    ``dGamma`` the fan angle between neighbouring columns in radians, ``dV`` the row pitch; ``nDetector`` = (H, W);
+    ``offDetector`` = (along the rows' direction, along the arc: a length, DSD times the angle it adds).  Every continuous
+    argument is a scalar or a per-view tensor [V]; float64 torch inside, differentiable in each, like ``scan_rays``, whose
+    frame this is: the source of view i at DSO (cos t, sin t, 0), eu = (-sin t, cos t, 0), ev = (0, 0, -1),
+    en = (-cos t, -sin t, 0).  Pixel (r, c) sits at the fan angle g = (c + 1/2 - W / 2) dGamma + offDetector[1] / DSD and the
+    height v = (r + 1/2 - H / 2) dV + offDetector[0]:
+        pixel = source + DSD (cos g en + sin g eu) + v ev.
+    origins = the source; directions = (pixel - source) / DSD, the scale ``scan_rays`` gives its cone rays, so that on the
+    column with g = 0 the rays are those of the flat detector of the same row pitch."""
+    H, W = int(nDetector[0]), int(nDetector[1])
+    if H < 1 or W < 1:
+        raise ValueError("the detector must have at least one pixel, got %d x %d" % (H, W))
+    tensors = [x for x in (angles, DSO, DSD, dGamma, dV) if isinstance(x, torch.Tensor)]
+    tensors += [x for x in ([offDetector] if isinstance(offDetector, torch.Tensor) else offDetector) if isinstance(x, torch.Tensor)]
+    device = tensors[0].device if tensors else torch.device("cpu")
+    ang = (angles.to(device=device, dtype=_F64) if isinstance(angles, torch.Tensor)
+           else torch.as_tensor(angles, dtype=_F64, device=device)).reshape(-1)
+    V = ang.shape[0]
+    if V < 1:
+        raise ValueError("no views")
+    DSO, DSD, dGamma, dV = (_per_view(x, V, device)[:, None, None] for x in (DSO, DSD, dGamma, dV))
+    oV, oU = (x[:, None, None] for x in _several(offDetector, 2, "offDetector", V, device))
+    c, s = torch.cos(ang), torch.sin(ang)
+    zero, one = torch.zeros_like(c), torch.ones_like(c)
+    eu = torch.stack([-s, c, zero], 1)[:, None, None, :]
+    ev = torch.stack([zero, zero, -one], 1)[:, None, None, :]
+    en = torch.stack([-c, -s, zero], 1)[:, None, None, :]
+    src = DSO[..., None] * torch.stack([c, s, zero], 1)[:, None, None, :]
+    g = (torch.arange(W, dtype=_F64, device=device)[None, None, :] + (0.5 - 0.5 * W)) * dGamma + oU / DSD
+    v = (torch.arange(H, dtype=_F64, device=device)[None, :, None] + (0.5 - 0.5 * H)) * dV + oV
+    g, v = g.expand(V, H, W)[..., None], v.expand(V, H, W)[..., None]
+    direction = torch.cos(g) * en + torch.sin(g) * eu + (v / DSD[..., None]) * ev
+    return src.expand_as(direction), direction
 
 
 def scanner_args(scanner, nDetector):
