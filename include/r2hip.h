@@ -611,6 +611,50 @@ R2_API int r2_integrate_gaussians_backward(int N, const float *rays /* [N,6] */,
                                            float *dL_drotations /* [P,4] */, float *dL_drays /* [N,6] or NULL */,
                                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the same line integrals, culled by leaves of Gaussians (scattered rays: a random subset of the pixels of many views) ----
+ * r2_integrate_gaussians_leaves: the values of r2_integrate_gaussians by the same rule -- a valid ray and a Gaussian with
+ * gauss_radius >= 0 are summed exactly when the pair's float32 q, formed from wp, is <= 32.001 (csrc/gaussian_bundle.hpp:
+ * bundle_pair), the cone rule with half_line != 0, invalid rays and Gaussians as there -- with the culling done from the other
+ * side, so that no ray waits for another ray's Gaussians and N rays make N waves of work.  Culling is by leaves of 64
+ * consecutive Gaussians, so an index order that is spatially coherent and keeps large Gaussians together culls well, and any
+ * other order costs time and nothing else.
+ * A prepare kernel, on every forward and backward call, writes into the workspace a float4 {mean, radius} per Gaussian (the
+ * radius of r2_integrate_gaussians' sphere; -1 for a Gaussian that contributes nothing), the 64-byte record S^-1 R^T, 1 / sigma,
+ * mean and density of every Gaussian that has a radius (csrc/gaussian_rays.hpp: gauss_rec), and per leaf the bounding box of its
+ * members' spheres mu -+ radius (empty, lo > hi, when no member has one; infinite when a radius is; the last leaf may be
+ * partial; a min / max butterfly over the wave, exact in any order).  The leaf test: a ray meets a leaf when its line meets the
+ * leaf's box under the slab test (1) of r2_integrate_gaussians, with (1)'s allowances: bounds moved outwards by 16 eps of
+ * themselves, every t by 16 eps of itself, half-line rays clipped to t >= 0, a ray whose |d|^2 is outside [1e-30, 1e30] meeting
+ * every leaf.  A summed pair's closest point lies in the Gaussian's sphere, hence in its leaf's box: the test is conservative
+ * for the infinite line and changes which pairs are summed by nothing.  Inside a met leaf a ray skips a Gaussian by (3).
+ * Forward: one wave per ray; lane l tests the box of leaf base + l, the wave walks the met leaves in ascending order, lane l
+ * taking Gaussian 64 leaf + l and adding its pairs in that order; one fixed xor butterfly adds the 64 lanes and lane 0 writes.
+ * out[n] depends on the cloud, its order and ray n alone, bit for bit; an invalid ray gets an exact 0.  Against
+ * r2_integrate_gaussians the sums associate differently: the values agree to rounding, and bit for bit where a ray sums one
+ * pair.  P = 0 writes zeros and needs no workspace; N = 0 returns success and touches nothing.  `workspace`:
+ * r2_integrate_gaussians_leaves_workspace_bytes(N, P) bytes (80 per Gaussian, 24 per leaf; 0 when N or P is 0), aligned to 16
+ * bytes, not kept between calls; NULL or fewer bytes with N > 0 and P > 0: R2_ERR_INVALID and a message naming the size
+ * needed, nothing launched.  N < 2^31, P <= 2^29.  No atomics, no allocation, no host synchronisation; bit-reproducible.
+ * r2_integrate_gaussians_leaves_backward: the gradients of r2_integrate_gaussians_backward, pair for pair.  Parameters: one
+ * wave per leaf, one lane per Gaussian; the wave takes the rays 64 at a time, lane l testing ray base + l against the leaf's
+ * box, compacts the hits in ray order, and every lane adds the pairs of its own Gaussian: a Gaussian's gradient is summed by
+ * one lane in ascending ray index, without butterfly or atomics; every output element is written, exact zeros for a Gaussian
+ * no ray touches or one that contributes nothing (all of them when N = 0, the one thing the backward writes then).  Rays, if
+ * dL_drays is not NULL: the forward's skeleton with six sums, dL_drays[n] depending on ray n alone. */
+R2_API size_t r2_integrate_gaussians_leaves_workspace_bytes(int N, int P);
+R2_API int r2_integrate_gaussians_leaves(int N, const float *rays /* [N,6] = start s, direction d */, int half_line, int P,
+                                         const float *means /* [P,3] */, const float *density /* [P] */,
+                                         const float *scales /* [P,3] */, float scale_modifier,
+                                         const float *rotations /* [P,4] */, float *out /* [N] */, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+R2_API int r2_integrate_gaussians_leaves_backward(int N, const float *rays /* [N,6] */, int half_line, int P, const float *means,
+                                                  const float *density, const float *scales, float scale_modifier,
+                                                  const float *rotations, const float *dL_dout /* [N] */,
+                                                  float *dL_dmeans /* [P,3] */, float *dL_ddensity /* [P] */,
+                                                  float *dL_dscales /* [P,3] */, float *dL_drotations /* [P,4] */,
+                                                  float *dL_drays /* [N,6] or NULL */, void *workspace, size_t workspace_bytes,
+                                                  void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -61,6 +61,9 @@ SOURCES = {
     # EXACT for the same two reasons (tests/gaussian_bundle_ref.py, gaussian_bundle.hpp on the three headers above)
     "gaussian_bundle.hip": EXACT,
     "gaussian_bundle_bwd.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_leaves_ref.py, gaussian_leaves.hpp on gaussian_bundle.hpp)
+    "gaussian_leaves.hip": EXACT,
+    "gaussian_leaves_bwd.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

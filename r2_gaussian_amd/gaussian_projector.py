@@ -10,7 +10,8 @@ rays are the [V,12] parameters of the volume projectors (projector.py), in world
 camera cannot describe (shifted, tilted) can be projected with ``project_gaussians_rays``.
 
 ``integrate_rays`` is the same line integral along rays that are no detector's: any [..., 3] starts and directions, on the
-kernels of csrc/gaussian_bundle.hip and csrc/gaussian_bundle_bwd.hip (``r2_integrate_gaussians`` and its backward).
+kernels of csrc/gaussian_bundle.hip and csrc/gaussian_bundle_bwd.hip (``r2_integrate_gaussians`` and its backward), or, with
+``method="leaves"``, of csrc/gaussian_leaves.hip and csrc/gaussian_leaves_bwd.hip (``r2_integrate_gaussians_leaves``).
 """
 import torch
 
@@ -121,55 +122,120 @@ def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0
                                   rotation, scale_modifier, out)
 
 
+_BLOCKS = ("r2_integrate_gaussians", "r2_integrate_gaussians_backward", "r2_integrate_gaussians_workspace_bytes")
+_LEAVES = ("r2_integrate_gaussians_leaves", "r2_integrate_gaussians_leaves_backward",
+           "r2_integrate_gaussians_leaves_workspace_bytes")
+
+
+def _integrate_forward(ctx, entries, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm,
+                       gperm=None):
+    """origins, directions [N,3] -> [N] through the C entries ``entries``.  ``perm`` (or None): the order the kernels see the
+    rays in; ``gperm`` (or None): the order they see the Gaussians in.  Values and gradients come back in the caller's
+    orders, by gathers alone."""
+    from .field import inverse_permutation
+    N, P = origins.shape[0], xyz.shape[0]
+    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    ginv = None
+    if gperm is not None:
+        x, d, s, r = (t[gperm].contiguous() for t in (x, d, s, r))
+        ginv = inverse_permutation(gperm)
+    rays = torch.cat([origins.detach().to(_F32), directions.detach().to(_F32)], 1)
+    inv = None
+    if perm is not None:
+        rays, inv = rays[perm].contiguous(), inverse_permutation(perm)
+    out = torch.empty((N,), dtype=_F32, device=x.device)
+    L = _lib.lib()
+    ws = torch.empty((max(int(getattr(L, entries[2])(N, P)), 1),), dtype=torch.uint8, device=x.device)
+    with _on_device(x.device):
+        rc = getattr(L, entries[0])(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                    float(scale_modifier), r.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    _stream(x.device))
+    _lib.check(rc, entries[0])
+    ctx.save_for_backward(rays, x, d, s, r, perm, inv, ginv)
+    ctx.args = (float(scale_modifier), half_line)
+    return out if inv is None else out[inv]
+
+
+def _integrate_backward(ctx, entries, G):
+    rays, x, d, s, r, perm, inv, ginv = ctx.saved_tensors
+    mod, half_line = ctx.args
+    N, P = rays.shape[0], x.shape[0]
+    G = _f32c(G)
+    if perm is not None:
+        G = G[perm].contiguous()
+    gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
+    grays = torch.empty_like(rays) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None
+    L = _lib.lib()
+    ws = torch.empty((max(int(getattr(L, entries[2])(N, P)), 1),), dtype=torch.uint8, device=x.device)
+    with _on_device(x.device):
+        rc = getattr(L, entries[1])(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(), mod,
+                                    r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(), gr.data_ptr(),
+                                    None if grays is None else grays.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device))
+    _lib.check(rc, entries[1])
+    if ginv is not None:
+        gx, gd, gs, gr = gx[ginv], gd[ginv], gs[ginv], gr[ginv]
+    go = gdir = None
+    if grays is not None:
+        if inv is not None:
+            grays = grays[inv]
+        go, gdir = grays[:, :3], grays[:, 3:]
+    return go, gdir, gx, gd, gs, gr
+
+
 class _IntegrateRays(torch.autograd.Function):
-    """origins, directions [N,3] -> [N].  ``perm`` (or None): the order the kernels see the rays in; values and gradients
-    come back in the caller's order, by gathers alone."""
+    """origins, directions [N,3] -> [N] on r2_integrate_gaussians (culling by blocks of rays)."""
 
     @staticmethod
     def forward(ctx, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm):
-        N, P = origins.shape[0], xyz.shape[0]
-        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
-        rays = torch.cat([origins.detach().to(_F32), directions.detach().to(_F32)], 1)
-        inv = None
-        if perm is not None:
-            from .field import inverse_permutation
-            rays, inv = rays[perm].contiguous(), inverse_permutation(perm)
-        out = torch.empty((N,), dtype=_F32, device=x.device)
-        L = _lib.lib()
-        ws = torch.empty((max(int(L.r2_integrate_gaussians_workspace_bytes(N, P)), 1),), dtype=torch.uint8, device=x.device)
-        with _on_device(x.device):
-            rc = L.r2_integrate_gaussians(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                          float(scale_modifier), r.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _stream(x.device))
-        _lib.check(rc, "r2_integrate_gaussians")
-        ctx.save_for_backward(rays, x, d, s, r, perm, inv)
-        ctx.args = (float(scale_modifier), half_line)
-        return out if inv is None else out[inv]
+        return _integrate_forward(ctx, _BLOCKS, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm)
 
     @staticmethod
     def backward(ctx, G):
-        rays, x, d, s, r, perm, inv = ctx.saved_tensors
-        mod, half_line = ctx.args
-        N, P = rays.shape[0], x.shape[0]
-        G = _f32c(G)
-        if perm is not None:
-            G = G[perm].contiguous()
-        gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
-        grays = torch.empty_like(rays) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None
-        L = _lib.lib()
-        ws = torch.empty((max(int(L.r2_integrate_gaussians_workspace_bytes(N, P)), 1),), dtype=torch.uint8, device=x.device)
-        with _on_device(x.device):
-            rc = L.r2_integrate_gaussians_backward(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(), mod,
-                                                   r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(),
-                                                   gr.data_ptr(), None if grays is None else grays.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), _stream(x.device))
-        _lib.check(rc, "r2_integrate_gaussians_backward")
-        go = gdir = None
-        if grays is not None:
-            if inv is not None:
-                grays = grays[inv]
-            go, gdir = grays[:, :3], grays[:, 3:]
-        return go, gdir, gx, gd, gs, gr, None, None, None
+        return _integrate_backward(ctx, _BLOCKS, G) + (None, None, None)
+
+
+class _IntegrateRaysLeaves(torch.autograd.Function):
+    """origins, directions [N,3] -> [N] on r2_integrate_gaussians_leaves (culling by leaves of Gaussians); ``gperm`` (or
+    None): the order of the Gaussians the kernels see."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm, gperm):
+        return _integrate_forward(ctx, _LEAVES, origins, directions, xyz, density, scaling, rotation, scale_modifier, half_line, perm,
+                                  gperm)
+
+    @staticmethod
+    def backward(ctx, G):
+        return _integrate_backward(ctx, _LEAVES, G) + (None, None, None, None)
+
+
+def cloud_order(xyz, scaling, scale_modifier=1.0):
+    """Permutation [P] (int64) that makes leaves of 64 consecutive Gaussians compact: a stable sort by (size class, 30-bit
+    Morton key of the mean), large Gaussians first.  The size class is floor(log2(diagonal of the box of the means /
+    radius)) with the radius proxy ``scale_modifier`` * max scale * 5.72 (the bounding sphere of a unit quaternion): Gaussians
+    within a factor two in size share a class, so that one large Gaussian does not inflate the box of a leaf of small ones.
+    The Morton key has 10 bits for each coordinate of the mean in the box of the means.  Rows with a non-finite mean or
+    scale, or no positive radius, get key 0 and come first.  It affects the cost of ``integrate_rays(method="leaves")``
+    alone.  torch ops only, on the tensors' device (CPU tensors too); no host synchronisation."""
+    m, s = xyz.detach().to(torch.float64), scaling.detach().to(torch.float64)
+    P = m.shape[0]
+    if P == 0:
+        return torch.arange(0, device=m.device)
+    radius = float(scale_modifier) * s.amax(1) * 5.72
+    good = torch.isfinite(m).all(1) & torch.isfinite(s).all(1) & torch.isfinite(radius) & (radius > 0)
+    big = torch.finfo(torch.float64).max
+    lo = torch.where(good[:, None], m, torch.full_like(m, big)).amin(0)
+    hi = torch.where(good[:, None], m, torch.full_like(m, -big)).amax(0)
+    ext = torch.where(hi > lo, hi - lo, torch.ones_like(lo))   # no good row, or a flat box: any positive number
+    diag = torch.where(hi > lo, hi - lo, torch.zeros_like(lo)).norm()
+    safe = torch.where(good, radius, torch.ones_like(radius))
+    cls = torch.log2(diag / safe).floor().clamp(0.0, 60.0)     # log2(0) = -inf clamps to 0
+    cell = ((torch.where(good[:, None], m, lo.expand_as(m)) - lo) / ext * 1024.0).floor().clamp(0.0, 1023.0).to(torch.int64)
+    key = (cls.to(torch.int64) + 1) << 30
+    for bit in range(10):
+        for j in range(3):
+            key = key | (((cell[:, j] >> bit) & 1) << (3 * bit + j))
+    key = torch.where(good, key, torch.zeros_like(key))
+    return torch.sort(key, stable=True)[1]
 
 
 def ray_order(origins, directions, xyz):
@@ -205,7 +271,8 @@ def ray_order(origins, directions, xyz):
     return torch.sort(key, stable=True)[1]
 
 
-def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_modifier=1.0, half_line=False, sort=False):
+def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_modifier=1.0, half_line=False, sort=False,
+                   method="blocks", order=False):
     """Exact line integrals [...] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
     ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along the rays ``origins`` + t ``directions``,
     both [..., 3] of one shape, in world coordinates; the directions need not be normalised.  A pair is the projector's:
@@ -218,7 +285,23 @@ def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_m
     pixels of a detector tile, the columns of a curved detector -- cull well as they are.  ``sort=True`` is meant for
     scattered rays: it orders them by ``ray_order`` before the kernels see them and un-permutes values and gradients.
     Which pairs a ray sums does not depend on the other rays, so sorting changes the cost alone: the values and the ray
-    gradients are the same bits."""
+    gradients are the same bits.
+
+    ``method``: "blocks" (the default) is the path above; "leaves" culls from the other side, by leaves of 64 consecutive
+    Gaussians (include/r2hip.h: r2_integrate_gaussians_leaves): one wave per ray walks only the leaves its line meets, so the
+    cost follows the number of rays and no ray waits for another ray's Gaussians.  "blocks" suits whole detectors, tiles and
+    other coherent rays, where 256 rays share every Gaussian they stage; "leaves" suits scattered rays, such as a random
+    subset of the pixels of many views.  The rule that decides which pairs are summed is the same; the sums associate
+    differently, so the two methods agree to rounding.  "leaves" culls well when the index order of the cloud is spatially
+    coherent and keeps large Gaussians together, and any other order costs time and nothing else: ``order=True`` (valid with
+    "leaves" only) gathers the four parameter tensors by ``cloud_order`` before the kernels and scatters the four gradients
+    back.  Summation order follows the Gaussian order, so values with and without ``order`` differ by rounding, not by which
+    pairs are summed.  A cloud that is integrated many times is better ordered once, outside.  ``sort`` keeps its meaning with
+    "leaves" and, each ray being a wave of its own there, buys little."""
+    if method not in ("blocks", "leaves"):
+        raise ValueError("method must be 'blocks' or 'leaves', got %r" % (method,))
+    if order and method != "leaves":
+        raise ValueError("order=True is valid with method='leaves' only")
     for name, t in (("origins", origins), ("directions", directions)):
         if not isinstance(t, torch.Tensor) or t.dim() < 1 or t.shape[-1] != 3:
             raise ValueError("%s must be a tensor [..., 3], got %s" % (name, tuple(getattr(t, "shape", ()))))
@@ -234,5 +317,10 @@ def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_m
     if o.shape[0] >= (1 << 31):
         raise ValueError("fewer than 2^31 rays, got %d" % o.shape[0])
     perm = ray_order(o, d, xyz) if sort else None
-    out = _IntegrateRays.apply(o, d, xyz, density, scaling, rotation, float(scale_modifier), int(bool(half_line)), perm)
+    if method == "leaves":
+        gperm = cloud_order(xyz, scaling, scale_modifier) if order else None
+        out = _IntegrateRaysLeaves.apply(o, d, xyz, density, scaling, rotation, float(scale_modifier), int(bool(half_line)), perm,
+                                         gperm)
+    else:
+        out = _IntegrateRays.apply(o, d, xyz, density, scaling, rotation, float(scale_modifier), int(bool(half_line)), perm)
     return out.reshape(origins.shape[:-1])

@@ -190,7 +190,7 @@ def scanner_args(scanner, nDetector):
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
 
 
-def refine_geometry(projs, cloud, rays_fn, params, iters, lr, loss="l2", cone=True, callback=None):
+def refine_geometry(projs, cloud, rays_fn, params, iters, lr, loss="l2", cone=True, callback=None, rays_per_step=None, seed=0):
     """Geometric self-calibration: minimise the error of the cloud's exact projection against ``projs`` [V,H,W] (GPU) over
     the geometry, the cloud held fixed.
 
@@ -202,21 +202,46 @@ def refine_geometry(projs, cloud, rays_fn, params, iters, lr, loss="l2", cone=Tr
     -> (refined parameters: a dict of detached tensors, loss history: a tensor [iters] on the device, the loss BEFORE each
     step).  Nothing in the loop waits for the device; ``callback(step, loss, params)``, when given, runs after every step and
     may.
+
+    ``rays_per_step`` = None: every step projects the V whole views.  An integer K: every step draws K of the V * H * W pixels
+    without replacement (``torch.randperm(V * H * W, generator=<CPU generator seeded once with seed>)[:K]``, then (view, row,
+    col) by division), forms their rays with ``pixel_rays`` from the float32 rays_fn(params), integrates them with
+    ``integrate_rays(..., half_line=cone, method="leaves")`` and takes the same loss over the K pixels.  The cloud is held
+    fixed, so it is put into ``cloud_order`` once, before the loop.  With K = V * H * W every pixel appears once per step and
+    the loss is the full loss up to the association of its sum.
     """
-    from .gaussian_projector import project_gaussians_rays
+    from .gaussian_projector import cloud_order, integrate_rays, project_gaussians_rays
     if loss not in ("l2", "l1"):
         raise ValueError("loss must be 'l2' or 'l1', got %r" % (loss,))
     if not isinstance(projs, torch.Tensor) or projs.dim() != 3 or not projs.is_cuda:
         raise ValueError("projs must be a GPU tensor [V,H,W]")
     V, H, W = projs.shape
+    if rays_per_step is not None and not 1 <= int(rays_per_step) <= V * H * W:
+        raise ValueError("rays_per_step must lie in 1 .. V * H * W = %d, got %r" % (V * H * W, rays_per_step))
     cloud = tuple(t.detach() for t in cloud)
     p = {k: torch.as_tensor(v).detach().clone().requires_grad_(True) for k, v in params.items()}
     opt = torch.optim.Adam(list(p.values()), lr=lr, betas=ADAM_BETAS, eps=ADAM_EPS)
     history = torch.zeros((int(iters),), dtype=torch.float32, device=projs.device)
     target = projs.detach().to(torch.float32)
+    gen = None
+    if rays_per_step is not None:
+        K, total = int(rays_per_step), V * H * W
+        perm = cloud_order(cloud[0], cloud[2])
+        cloud = tuple(t[perm].contiguous() for t in cloud)
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        flat = target.reshape(-1)
     for it in range(int(iters)):
         opt.zero_grad(set_to_none=True)
-        diff = project_gaussians_rays(rays_fn(p), cone, H, W, *cloud) - target
+        if gen is None:
+            diff = project_gaussians_rays(rays_fn(p), cone, H, W, *cloud) - target
+        else:
+            pick = torch.randperm(total, generator=gen)[:K].to(projs.device)
+            view = pick // (H * W)
+            rest = pick - view * (H * W)
+            row = rest // W
+            col = rest - row * W
+            o, d = pixel_rays(rays_fn(p).to(device=projs.device, dtype=torch.float32)[view], cone, H, W, row[:, None], col[:, None])
+            diff = integrate_rays(o, d, *cloud, half_line=cone, method="leaves").reshape(-1) - flat[pick]
         value = (diff * diff).mean() if loss == "l2" else diff.abs().mean()
         value.backward()
         opt.step()

@@ -10,6 +10,9 @@ parameter tensors require grad) and forward + ray backward (only the rays do).
       the largest difference between the two images relative to the image's maximum;
   (b) 4096 and 65 536 random pixels over `views` views, as drawn and with sort=True;
   (c) a 512 x 64 curved detector (64 rows of 512 columns on the arc of the flat detector's width), one view.
+Under every row the same rays with method="leaves" (culling by leaves of 64 Gaussians), in the same process by the same
+protocol; on (b) also with order=True (the gathers by cloud_order inside the timing) and with the cloud put into
+cloud_order once, outside the timing.
 Not a test and not a gate.
 """
 import argparse
@@ -26,7 +29,7 @@ sys.path.insert(0, ROOT)
 
 from r2_gaussian_amd import geometry                                                          # noqa: E402
 from r2_gaussian_amd import scene as S                                                        # noqa: E402
-from r2_gaussian_amd.gaussian_projector import integrate_rays, project_gaussians_rays         # noqa: E402
+from r2_gaussian_amd.gaussian_projector import cloud_order, integrate_rays, project_gaussians_rays   # noqa: E402
 
 
 def timed(fn, reps, dev, warm=3):
@@ -44,10 +47,10 @@ def timed(fn, reps, dev, warm=3):
     return {"median_ms": t[len(t) // 2], "min_ms": t[0], "max_ms": t[-1], "reps": reps, "warm": warm}
 
 
-def three(o, d, leaves, half_line, sort, reps, dev):
+def three(o, d, leaves, half_line, sort, reps, dev, method="blocks", order=False):
     """Forward, forward + parameter backward, forward + ray backward of integrate_rays on the rays (o, d)."""
     G = torch.rand(o.shape[:-1], device=dev)
-    call = lambda o, d, lv: integrate_rays(o, d, *lv, half_line=half_line, sort=sort)
+    call = lambda o, d, lv: integrate_rays(o, d, *lv, half_line=half_line, sort=sort, method=method, order=order)
     r = {"rays": int(G.numel())}
     with torch.no_grad():
         r["fwd"] = timed(lambda: call(o, d, leaves), reps, dev)
@@ -105,6 +108,7 @@ def main():
     rg = rays.clone().requires_grad_(True)
     proj["fwd_rays_bwd"] = timed(lambda: torch.autograd.grad(project_gaussians_rays(rg, True, n, n, *leaves), [rg], G), a.reps, dev)
     emit("a_view_tile_order", one)
+    emit("a_view_tile_order_leaves", three(o, d, leaves, True, False, a.reps, dev, method="leaves"))
     emit("a_projector", proj)
     emit("a_max_difference_over_image_max", float((mine - img).abs().max() / img.abs().max()))
 
@@ -112,6 +116,8 @@ def main():
     angles = torch.linspace(0.0, 2.0 * math.pi, a.views + 1, dtype=torch.float64, device=dev)[:-1]
     many = geometry.scan_rays(angles, **kw).float()
     g = torch.Generator(device="cpu").manual_seed(3)
+    perm = cloud_order(leaves[0], leaves[2])
+    ordered = [t[perm].contiguous() for t in leaves]   # the cloud put into cloud_order once, outside the timing
     for total in (4096, 65536):
         k = total // a.views
         rows = torch.randint(n, (a.views, k), generator=g).to(dev)
@@ -120,14 +126,20 @@ def main():
         mix = torch.randperm(a.views * k, generator=g).to(dev)   # drawn across the views, not view by view
         o, d = o.reshape(-1, 3)[mix].contiguous(), d.reshape(-1, 3)[mix].contiguous()
         for sort in (False, True):
-            emit("b_random_%d%s" % (total, "_sorted" if sort else ""), three(o, d, leaves, True, sort, a.reps, dev))
+            key = "b_random_%d%s" % (total, "_sorted" if sort else "")
+            emit(key, three(o, d, leaves, True, sort, a.reps, dev))
+            emit(key + "_leaves", three(o, d, leaves, True, sort, a.reps, dev, method="leaves"))
+        emit("b_random_%d_leaves_order" % total, three(o, d, leaves, True, False, a.reps, dev, method="leaves", order=True))
+        emit("b_random_%d_leaves_preordered" % total, three(o, d, ordered, True, False, a.reps, dev, method="leaves"))
 
     # (c) a curved detector: 64 rows of 512 columns, the arc as long as the flat detector is wide
     W, H = 512, 64
     width = kw["dDetector"][1] * n
     o, d = geometry.curved_detector_rays(torch.tensor([0.6], dtype=torch.float64, device=dev), kw["DSO"], kw["DSD"],
                                          width / kw["DSD"] / W, kw["dDetector"][0] * n / H, (H, W))
-    emit("c_curved_512x64", three(o.float().contiguous(), d.float().contiguous(), leaves, True, False, a.reps, dev))
+    o, d = o.float().contiguous(), d.float().contiguous()
+    emit("c_curved_512x64", three(o, d, leaves, True, False, a.reps, dev))
+    emit("c_curved_512x64_leaves", three(o, d, leaves, True, False, a.reps, dev, method="leaves"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
