@@ -655,6 +655,61 @@ R2_API int r2_integrate_gaussians_leaves_backward(int N, const float *rays /* [N
                                                   float *dL_drays /* [N,6] or NULL */, void *workspace, size_t workspace_bytes,
                                                   void *stream);
 
+/* ---- Fisher information and predictive variance on the exact operators (no counterpart in the reference) ---------------------
+ * The image of r2_project_gaussians and the field of r2_query_gaussians are plain sums over the Gaussians, so the derivative
+ * of one pixel (or of the field at one point) with respect to parameter t of Gaussian i is ONE pair's number: o[t] of
+ * r2_project_gaussians_backward's per-pair formulas with G = 1 (csrc/gaussian_rays.hpp: gauss_pair_grad).  The eleven
+ * parameters, in that order: mean (3), density, the unmodified scales (3; the scale_modifier factor is included), the
+ * quaternion (4; as given, no normalisation Jacobian).  The three entries add squares of these numbers
+ * (csrc/gaussian_fisher.hpp: pair_squares, pair_variance); every addend is >= 0 for weights and variances >= 0.
+ * What the numbers mean: f is the DIAGONAL of J^T W J, the Fisher information of the parameters under independent pixel noise
+ * of variance 1 / w and the Gauss-Newton diagonal of the weighted least-squares fit.  1 / (f + prior precision) taken as a
+ * parameter variance, and the two predictive variances computed from it, ignore every correlation between the parameters of
+ * a Gaussian and between Gaussians: a Laplace approximation in the given parametrisation, not a posterior.
+ * r2_project_gaussians_fisher: f[i][t] = the sum over the pixels (v, r, c) of all V views of
+ *     w[v][r][c] * (o[t] * o[t]),     o = the pair's eleven derivatives with G = 1,
+ * written to f_means [P,3], f_density [P], f_scales [P,3], f_rotations [P,4].  weights [V,H,W] or NULL for w = 1 (the same
+ * bits as an array of ones); they are used as they come and are meant to be >= 0.  The pairs are exactly those
+ * r2_project_gaussians_backward differentiates: the detector rectangle of the Gaussian's sphere, then the pair rule of
+ * r2_project_gaussians (A > 0, the cone rule, a finite term).  Gaussian-major, the backward's skeleton: one wave per
+ * Gaussian, views in order, the rectangle's pixels row-major with lane l taking pixels l, l + 64, ..., eleven sums per lane
+ * (acc[t] += w * (o[t] * o[t])), one fixed xor butterfly, lane 0 writes.  No atomics, no workspace, no allocation, no host
+ * synchronisation; bit-reproducible; every output element is written, exact zeros for a Gaussian no ray touches and for one
+ * with a non-finite parameter or a scale <= 0.  P = 0 returns success and touches nothing.  Cost: that of the backward -- a
+ * Gaussian that covers the detector costs its wave V * H * W pairs, and the call waits for it.  P <= 2^29, H * W < 2^30;
+ * argument checks as r2_project_gaussians_backward.
+ * r2_query_gaussians_variance: out[n] = the sum over the pairs of points[n] of
+ *     pair_variance = sum_t v[i][t] * (o[t] * o[t])   (added in ascending t),
+ * the variance of the field at the point under independent parameter variances v (v_means [P,3], v_density [P], v_scales
+ * [P,3], v_rotations [P,4]; used as they come, meant to be >= 0).  The pairs are those of r2_query_gaussians: the per-pair
+ * cut at a float32 q of 32.001 behind the block-box and sphere tests, so out[n] depends on the cloud and point n alone, bit
+ * for bit, whatever the order of the points.  Point-major, the forward's skeleton with a 140-byte staged record: one
+ * workgroup per block of 256 points, ascending Gaussian index in one thread.  A point with a non-finite coordinate gets 0; P = 0
+ * writes zeros; N = 0 returns success and touches nothing.  N < 2^31, P <= 2^29.
+ * r2_project_gaussians_variance: out[v][r][c] = the sum over the pixel's pairs of pair_variance, the predictive variance of
+ * every pixel of r2_project_gaussians' image.  The pairs are those the forward sums (rectangle, then the pair rule), so
+ * sum_pixels w * out = sum_it f[i][t] v[i][t] with f of r2_project_gaussians_fisher up to rounding: the same pairs added in
+ * two orders.  Pixel-major, the forward's skeleton: one workgroup per 16 x 16 tile and view, ascending Gaussian index in one
+ * thread.  P = 0 writes zeros.  V <= 65535, P <= 2^29.
+ * All three: separately rounded float32 in the order written; no atomics, no workspace, no allocation, no host
+ * synchronisation; bit-reproducible. */
+R2_API int r2_project_gaussians_fisher(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                       const float *means /* [P,3] */, const float *density /* [P] */,
+                                       const float *scales /* [P,3] */, float scale_modifier, const float *rotations /* [P,4] */,
+                                       const float *weights /* [V,H,W] or NULL */, float *f_means /* [P,3] */,
+                                       float *f_density /* [P] */, float *f_scales /* [P,3] */, float *f_rotations /* [P,4] */,
+                                       void *stream);
+R2_API int r2_query_gaussians_variance(int N, const float *points /* [N,3] */, int P, const float *means, const float *density,
+                                       const float *scales, float scale_modifier, const float *rotations,
+                                       const float *v_means /* [P,3] */, const float *v_density /* [P] */,
+                                       const float *v_scales /* [P,3] */, const float *v_rotations /* [P,4] */,
+                                       float *out /* [N] */, void *stream);
+R2_API int r2_project_gaussians_variance(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                         const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                         const float *v_means /* [P,3] */, const float *v_density /* [P] */,
+                                         const float *v_scales /* [P,3] */, const float *v_rotations /* [P,4] */,
+                                         float *out /* [V,H,W] */, void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -64,6 +64,9 @@ SOURCES = {
     # EXACT for the same two reasons (tests/gaussian_leaves_ref.py, gaussian_leaves.hpp on gaussian_bundle.hpp)
     "gaussian_leaves.hip": EXACT,
     "gaussian_leaves_bwd.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_fisher_ref.py, gaussian_fisher.hpp on gaussian_rays.hpp / gaussian_points.hpp)
+    "gaussian_fisher.hip": EXACT,
+    "gaussian_variance.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

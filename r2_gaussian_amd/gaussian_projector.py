@@ -74,14 +74,9 @@ class _ProjectGaussians(torch.autograd.Function):
         return gx, gd, gs, gr, grays, None, None, None, None, None
 
 
-def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
-    """Exact projections [V,H,W] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
-    ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along caller-supplied rays: ``rays`` [V,12]
-    {a, p00, pu, pv} in world coordinates (include/r2hip.h), ``cone`` the beam (True: from the source a through the pixel
-    points; False: through the pixel points along a).  Differentiable in the four parameter tensors, and in ``rays`` when they
-    require grad (``r2_project_gaussians_rays_backward``, launched only then): a ``rays`` tensor on the device or on the host,
-    of any float dtype, receives its gradient where and as it is.  No host synchronisation (host rays that require grad are
-    copied synchronously); ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
+def check_projection_arguments(rays, H, W, xyz, density, scaling, rotation):
+    """The argument checks every operator on (rays, detector, cloud) shares: ``rays`` [V,12] with V >= 1, a detector of at least
+    one pixel, the four parameter tensors of one P on one GPU.  -> (rays as a tensor, H, W), or ValueError."""
     rays = torch.as_tensor(rays)
     if rays.dim() != 2 or rays.shape[1] != 12 or rays.shape[0] < 1:
         raise ValueError("rays must be [V,12] with V >= 1, got shape %s" % (tuple(rays.shape),))
@@ -101,6 +96,18 @@ def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, sc
             raise ValueError("%s must be a GPU tensor: the exact projector has no CPU fallback" % name)
         if t.device != xyz.device:
             raise ValueError("%s is on %s, xyz on %s" % (name, t.device, xyz.device))
+    return rays, H, W
+
+
+def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
+    """Exact projections [V,H,W] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
+    ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along caller-supplied rays: ``rays`` [V,12]
+    {a, p00, pu, pv} in world coordinates (include/r2hip.h), ``cone`` the beam (True: from the source a through the pixel
+    points; False: through the pixel points along a).  Differentiable in the four parameter tensors, and in ``rays`` when they
+    require grad (``r2_project_gaussians_rays_backward``, launched only then): a ``rays`` tensor on the device or on the host,
+    of any float dtype, receives its gradient where and as it is.  No host synchronisation (host rays that require grad are
+    copied synchronously); ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
+    rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
     V = rays.shape[0]
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != _F32 or not out.is_cuda or not out.is_contiguous()
                             or tuple(out.shape) != (V, H, W) or out.device != xyz.device):

@@ -10,6 +10,9 @@ initial points, so it runs as well on an in-memory case.  Outputs, in the refere
 ``point_cloud/iteration_N/{point_cloud.pickle, vol_gt.npy, vol_pred.npy}``, ``eval/iter_NNNNNN/{eval3d.yml,
 eval2d_render_train.yml, eval2d_render_test.yml}``, ``ckpt/chkpnt{N}.pth``.  ``--eval_exact`` (not a flag of the reference; off
 by default) adds ``eval2d_render_{train,test}_exact.yml``: the same 2D metrics on the exact projection of the model.
+``--save_uncertainty LAMBDA`` (not a flag of the reference; off by default) adds ``fisher.npz`` and ``vol_std.npy`` to the last
+``point_cloud/iteration_N``: the Fisher diagonal of the model over the training views and the standard deviation of the field
+on the evaluation grid under the prior precision LAMBDA (uncertainty.py).
 
 ``--views_per_step W`` (not a flag of the reference; default 1 = its loop): one optimiser step on W views -- one batched
 render, one batched loss node (the mean over the views), one backward, one batched statistics launch, one model step.
@@ -135,6 +138,27 @@ def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals, eval_exa
     return out
 
 
+@torch.no_grad()
+def write_uncertainty(gaussians, views, geometry, path, prior_precision, batch=8):
+    """fisher.npz (xyz [P,3], density [P,1], scaling [P,3], rotation [P,4]: the Fisher diagonal of the activated parameters
+    over `views` with unit weights, `batch` views per launch) and vol_std.npy ([nx, ny, nz]: the square root of the field's
+    predictive variance at the voxel centres of the evaluation grid, under the Laplace variances 1 / (F + prior_precision))
+    into `path`."""
+    from . import uncertainty as U
+    from .field import voxel_centres
+    xyz, d, s, r = (t.detach() for t in gaussians.activated())
+    F = None
+    for i in range(0, len(views), batch):
+        Fi = U.fisher_diagonal(views[i:i + batch], xyz, d, s, r)
+        F = Fi if F is None else U.CloudTuple(*(a + b for a, b in zip(F, Fi)))
+    var = U.parameter_variance(F, prior_precision)
+    pts = voxel_centres(geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"], xyz.device)
+    std = U.field_variance(pts, xyz, d, s, r, var).sqrt()
+    os.makedirs(path, exist_ok=True)
+    np.savez(osp.join(path, "fisher.npz"), **{k: v.cpu().numpy() for k, v in F._asdict().items()})
+    np.save(osp.join(path, "vol_std.npy"), std.cpu().numpy())
+
+
 def render_loss_batch(gaussians, views, gts, lambda_dssim, dev):
     """The image term of a step on several views: ONE GaussianRasterizerBatch call on `views` (scene.View list) and ONE
     losses.image_loss_batch node against `gts` (their ground truths, [H, W] device tensors).
@@ -162,7 +186,7 @@ def pick_views(stack, n_views, count, rng):
 
 def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry, init_points, opt, model_path,
              scale_bound=None, test_iterations=(), save_iterations=(), checkpoint_iterations=(), start_checkpoint=None,
-             seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False):
+             seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False, save_uncertainty=None):
     """The training loop of train.py:34-216.  views: scene.View lists; projections: [V, H, W] in scene units (times
     scene_scale); vol_gt [nx, ny, nz]; geometry: the NORMALISED scanner config (nVoxel, sVoxel, offOrigin, dVoxel);
     init_points [N, 4] = xyz | density; scale_bound: (lo, hi) in scene units or None.  Randomness (view order, TV patch centres,
@@ -173,10 +197,14 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     one batched statistics call with grad_scale = W: the statistics see every view's own screen-space gradient, which keeps
     densify_grad_threshold a per-view quantity whatever W is.  W = 1 is the single-view loop, unchanged.
     eval_exact: every evaluation also writes eval2d_<name>_exact.yml (evaluate); training itself is untouched.
+    save_uncertainty = lambda > 0 (None: off): after the last iteration ``save_uncertainty`` writes fisher.npz and vol_std.npy
+    into the last point_cloud/iteration_N; training itself is untouched.
     -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P)."""
     W = int(views_per_step)
     if W < 1:
         raise ValueError("views_per_step must be >= 1, got %r" % (views_per_step,))
+    if save_uncertainty is not None and not float(save_uncertainty) > 0:
+        raise ValueError("save_uncertainty must be a positive prior precision, got %r" % (save_uncertainty,))
     dev = torch.device(device)
     gaussians = GaussianModel(scale_bound, device=dev)
     gaussians.create_from_pcd(init_points[:, :3], init_points[:, 3:4], 1.0)
@@ -252,6 +280,9 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
         if iteration in test_iterations:
             out["evals"][iteration] = e = evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals, eval_exact)
             log("[ITER %d] Evaluating: psnr3d %.3f, ssim3d %.3f, P %d" % (iteration, e["psnr_3d"], e["ssim_3d"], gaussians.P))
+    if save_uncertainty is not None:
+        write_uncertainty(gaussians, train_views, geometry, osp.join(model_path, "point_cloud", "iteration_%d" % opt.iterations),
+                          float(save_uncertainty))
     out["it_per_s"] = n_timed / t_train if t_train > 0 else float("nan")
     out["views_per_s"] = W * out["it_per_s"]
     out["model"] = gaussians
@@ -337,6 +368,10 @@ def build_parser():
     ap.add_argument("--eval_exact", action="store_true", default=False,
                     help="every evaluation also writes eval2d_render_{train,test}_exact.yml: the 2D metrics on the exact line "
                          "integrals of the model (gaussian_projector) next to those on the rasterizer's image of it")
+    ap.add_argument("--save_uncertainty", type=float, default=None, metavar="LAMBDA",
+                    help="after the last iteration write fisher.npz (the Fisher diagonal of the activated parameters over the "
+                         "training views, unit weights) and vol_std.npy (the standard deviation of the field on the evaluation "
+                         "grid under the Laplace variances 1 / (F + LAMBDA)) into the last point_cloud/iteration_N")
     return ap
 
 
@@ -353,6 +388,8 @@ def main(argv=None):
             setattr(args, k, v)
     if args.views_per_step < 1:
         ap.error("--views_per_step must be >= 1")
+    if args.save_uncertainty is not None and not args.save_uncertainty > 0:
+        ap.error("--save_uncertainty needs a positive prior precision")
     if args.compute_cov3D_python:
         ap.error("--compute_cov3D_python is not supported: the kernels build the covariance from scales and rotations")
     args.save_iterations.append(args.iterations)
@@ -375,7 +412,7 @@ def main(argv=None):
     out = training(case["train_views"], case["train_projs"], case["test_views"], case["test_projs"], case["vol_gt"],
                    case["geometry"], case["init_points"], opt, args.model_path, scale_bound, set(args.test_iterations),
                    set(args.save_iterations), set(args.checkpoint_iterations), args.start_checkpoint, log=log,
-                   views_per_step=args.views_per_step, eval_exact=args.eval_exact)
+                   views_per_step=args.views_per_step, eval_exact=args.eval_exact, save_uncertainty=args.save_uncertainty)
     print("Training complete. " + _rate(out, args.views_per_step))
     return out
 
