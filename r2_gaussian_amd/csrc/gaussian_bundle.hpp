@@ -67,8 +67,7 @@ __host__ __device__ __forceinline__ size_t bundle_workspace_boxes(int N, int P)
 }
 
 // Launches the two kernels that write the cloud box (0) into boxes[0] (gaussian_bundle.hip); P > 0.
-void bundle_cloud_box(int P, const float *means, const float *density, const float *scales, float mod, const float *rotations,
-                      BlockBox *boxes, hipStream_t s);
+void bundle_cloud_box(const Cloud &cl, BlockBox *boxes, hipStream_t s);
 
 // What the kernels keep of a ray: the ray itself, its length and whether it is valid.
 struct BundleRay {
@@ -83,6 +82,17 @@ __device__ __forceinline__ BundleRay bundle_ray(const float *__restrict__ rays, 
     b.y = Ray{rays[6 * n], rays[6 * n + 1], rays[6 * n + 2], rays[6 * n + 3], rays[6 * n + 4], rays[6 * n + 5]};
     b.len = ray_length(b.y);
     b.valid = point_finite(b.y.sx, b.y.sy, b.y.sz) && point_finite(b.y.dx, b.y.dy, b.y.dz) && b.len > 0.0f && b.len < INFINITY;
+    return b;
+}
+
+// Ray n of N; n >= N: the ray that is not there, invalid.
+__device__ __forceinline__ BundleRay bundle_ray(const float *__restrict__ rays, long long n, long long N)
+{
+    BundleRay b;
+    b.y = Ray{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    b.len = 0.0f;
+    b.valid = false;
+    if (n < N) b = bundle_ray(rays, n);
     return b;
 }
 
@@ -205,75 +215,41 @@ struct StagedRayGauss {
     float radius;
 };
 
-// The ray-major skeleton of the forward (GRAD = false: out[n] = the integral along ray n) and of the ray gradient
-// (GRAD = true: out[6 n ..] = G[n] d integral / d (s, d)).  One workgroup per block of QB rays, one thread per ray.  The
-// workgroup walks the P Gaussians in index order, QB at a time: thread i tests the sphere of Gaussian base + i against the
-// block's box, the hits are compacted IN ORDER (wave ballots + the wave counts) into an LDS batch with their S^-1 R^T, and
-// every ray adds the batch's pairs in batch order: in ascending Gaussian index, in one thread.
+// The ray-major kernel of the forward (GRAD = false: out[n] = the integral along ray n) and of the ray gradient
+// (GRAD = true: out[6 n ..] = G[n] d integral / d (s, d)) on gaussian_skeleton.hpp's gather_rounds.  One workgroup per block of
+// QB rays, one thread per ray.  A Gaussian is a hit when its sphere meets the block's box; the hits are staged with their
+// S^-1 R^T, and every ray adds the batch's pairs in batch order: in ascending Gaussian index, in one thread.
 template <bool GRAD>
-__device__ __forceinline__ void integrate_rays_block(int N, const float *__restrict__ rays, int half_line, int P,
-                                                     const float *__restrict__ means, const float *__restrict__ density,
-                                                     const float *__restrict__ scales, float mod,
-                                                     const float *__restrict__ rotations, const float *__restrict__ G,
-                                                     const BlockBox *__restrict__ cloud, float *__restrict__ out)
+__device__ __forceinline__ void integrate_rays_block(int N, const float *__restrict__ rays, int half_line, const Cloud &cl,
+                                                     const float *__restrict__ G, const BlockBox *__restrict__ cloud,
+                                                     float *__restrict__ out)
 {
     __shared__ StagedRayGauss st[QB];
     __shared__ float wbox[QB / WAVE][6];
-    __shared__ int wcount[QB / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const long long n = (long long)blockIdx.x * QB + tid;   // < 2^31 + QB
-    BundleRay b;
-    b.y = Ray{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    b.len = 0.0f;
-    b.valid = false;
-    if (n < N) b = bundle_ray(rays, n);
+    const long long n = (long long)blockIdx.x * QB + threadIdx.x;   // < 2^31 + QB
+    const BundleRay b = bundle_ray(rays, n, N);
     const BundleDir u = bundle_dir(b);
     float acc[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-    if (P > 0) {   // uniform; the cloud box is only there when there is a cloud
+    if (cl.P > 0) {   // uniform; the cloud box is only there when there is a cloud
         float v[6];
         const bool live = bundle_ray_box(b, u, half_line, cloud[0], v);
         const BlockBox box = bundle_box_reduce(v, wbox);
         const float Gn = GRAD && live ? G[n] : 0.0f;
-        for (int base = 0; base < P; base += QB) {
-            const int i = base + tid;
-            bool hit = false;
-            float mx = 0.f, my = 0.f, mz = 0.f, rho = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, radius = 0.f;
-            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < P) {
-                mx = means[3 * i]; my = means[3 * i + 1]; mz = means[3 * i + 2];
-                rho = density[i];
-                sx = scales[3 * i]; sy = scales[3 * i + 1]; sz = scales[3 * i + 2];
-                q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-                radius = gauss_radius(mx, my, mz, rho, sx, sy, sz, mod, q);
-                hit = radius >= 0.0f && box_meets_sphere(box, mx, my, mz, radius);
-            }
-            const unsigned long long mask = __ballot(hit);
-            if (lane == 0) wcount[wave] = __popcll(mask);
-            __syncthreads();
-            int slot = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-            for (int w = 0; w < QB / WAVE; ++w) {
-                if (w < wave) slot += wcount[w];
-                total += wcount[w];
-            }
-            if (hit) {
-                st[slot].g = gauss_rec(mx, my, mz, rho, sx, sy, sz, mod, q);
-                st[slot].radius = radius;
-            }
-            __syncthreads();
-            if (live) {
-                for (int j = 0; j < total; ++j) {
-                    if (bundle_line_misses(b, u, st[j].g.mx, st[j].g.my, st[j].g.mz, st[j].radius)) continue;
-                    GaussPair p;
-                    if (!bundle_pair(st[j].g, b.y, half_line, p)) continue;
-                    if (GRAD)
-                        gauss_pair_ray_grad(st[j].g, p, b.y, b.len, Gn, acc, acc + 3);
-                    else
-                        acc[0] += gauss_term(st[j].g, p, b.len);
-                }
-            }
-            __syncthreads();   // the batch and the wave counts are rewritten by the next round
-        }
+        gather_rounds<QB>(
+            cl, st, live, [&](const Gauss &a, float radius) { return box_meets_sphere(box, a.mx, a.my, a.mz, radius); },
+            [&](StagedRayGauss &d, const Gauss &a, float radius, int) {
+                d.g = gauss_rec(a, cl.mod);
+                d.radius = radius;
+            },
+            [&](const StagedRayGauss &s) {
+                if (bundle_line_misses(b, u, s.g.mx, s.g.my, s.g.mz, s.radius)) return;
+                GaussPair p;
+                if (!bundle_pair(s.g, b.y, half_line, p)) return;
+                if (GRAD)
+                    gauss_pair_ray_grad(s.g, p, b.y, b.len, Gn, acc, acc + 3);
+                else
+                    acc[0] += gauss_term(s.g, p, b.len);
+            });
     }
     if (n < N) {
         if (GRAD) {

@@ -11,8 +11,6 @@
 
 namespace r2 {
 
-constexpr int NPAR = 11;   // parameters of a Gaussian: mean (3), density, scales (3), quaternion (4), in gauss_pair_grad's order
-
 // o[t] = (d term / d theta_t)^2 of one pair: gauss_pair_grad with G = 1, squared.
 __device__ __forceinline__ void pair_squares(const GaussRec &g, const GaussPair &p, const Ray &y, float len, const float *s,
                                              float4 q, float *o)
@@ -45,13 +43,13 @@ struct StagedVar {
     float v[NPAR];
 };
 
-__device__ __forceinline__ void stage_var(StagedVar &d, float mx, float my, float mz, float rho, float sx, float sy, float sz,
-                                          float mod, float4 q, const float *__restrict__ v_means, const float *__restrict__ v_density,
-                                          const float *__restrict__ v_scales, const float *__restrict__ v_rotations, int i)
+__device__ __forceinline__ void stage_var(StagedVar &d, const Gauss &a, float mod, const float *__restrict__ v_means,
+                                          const float *__restrict__ v_density, const float *__restrict__ v_scales,
+                                          const float *__restrict__ v_rotations, int i)
 {
-    d.g = gauss_rec(mx, my, mz, rho, sx, sy, sz, mod, q);
-    d.s[0] = sx; d.s[1] = sy; d.s[2] = sz;
-    d.q[0] = q.x; d.q[1] = q.y; d.q[2] = q.z; d.q[3] = q.w;
+    d.g = gauss_rec(a, mod);
+    d.s[0] = a.s[0]; d.s[1] = a.s[1]; d.s[2] = a.s[2];
+    d.q[0] = a.q.x; d.q[1] = a.q.y; d.q[2] = a.q.z; d.q[3] = a.q.w;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         d.v[k] = v_means[3 * i + k];
@@ -62,28 +60,29 @@ __device__ __forceinline__ void stage_var(StagedVar &d, float mx, float my, floa
     for (int k = 0; k < 4; ++k) d.v[7 + k] = v_rotations[4 * i + k];
 }
 
+// The staged Gaussian's share of the variance of one ray (or point, as point_ray) for the pair p.
+__device__ __forceinline__ float staged_variance(const StagedVar &a, const GaussPair &p, const Ray &y, float len)
+{
+    return pair_variance(a.g, p, y, len, a.s, make_float4(a.q[0], a.q[1], a.q[2], a.q[3]), a.v);
+}
+
 // The record of the point-major variance kernel: about 140 bytes, 35 kB for a batch of QB.
 struct StagedPointVar {
     StagedVar a;
     float r2;
 };
 
-// The point-major skeleton of r2_query_gaussians_variance: query_points_block (gaussian_points.hpp) restated for the larger
-// record.  One workgroup per block of QB points, one thread per point.  The workgroup walks the P Gaussians in index order, QB
-// at a time: thread i tests the sphere of Gaussian base + i against the block's box, the hits are compacted IN ORDER (wave
-// ballots + the wave counts) into an LDS batch, and every point adds the batch's pairs in batch order: a point adds its pairs
-// in ascending Gaussian index, in one thread.
-__device__ __forceinline__ void variance_points_block(int N, const float *__restrict__ points, int P, const float *__restrict__ means,
-                                                      const float *__restrict__ density, const float *__restrict__ scales, float mod,
-                                                      const float *__restrict__ rotations, const float *__restrict__ v_means,
-                                                      const float *__restrict__ v_density, const float *__restrict__ v_scales,
-                                                      const float *__restrict__ v_rotations, float *__restrict__ out)
+// The point-major kernel of r2_query_gaussians_variance: query_points_block's rounds (gaussian_points.hpp, on
+// gaussian_skeleton.hpp's gather_rounds) with the larger record.  One workgroup per block of QB points, one thread per point;
+// a point adds its pairs in ascending Gaussian index, in one thread.
+__device__ __forceinline__ void variance_points_block(int N, const float *__restrict__ points, const Cloud &cl,
+                                                      const float *__restrict__ v_means, const float *__restrict__ v_density,
+                                                      const float *__restrict__ v_scales, const float *__restrict__ v_rotations,
+                                                      float *__restrict__ out)
 {
     __shared__ StagedPointVar st[QB];
     __shared__ float wbox[QB / WAVE][6];
-    __shared__ int wcount[QB / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const long long n = (long long)blockIdx.x * QB + tid;   // < 2^31 + QB
+    const long long n = (long long)blockIdx.x * QB + threadIdx.x;   // < 2^31 + QB
     float x = 0.f, y = 0.f, z = 0.f;
     if (n < N) {
         x = points[3 * n]; y = points[3 * n + 1]; z = points[3 * n + 2];
@@ -92,43 +91,16 @@ __device__ __forceinline__ void variance_points_block(int N, const float *__rest
     const BlockBox box = block_box(valid, x, y, z, wbox);
     const Ray ray = point_ray(x, y, z);
     float acc = 0.0f;
-    for (int base = 0; base < P; base += QB) {
-        const int i = base + tid;
-        bool hit = false;
-        float mx = 0.f, my = 0.f, mz = 0.f, rho = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, radius = 0.f;
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < P) {
-            mx = means[3 * i]; my = means[3 * i + 1]; mz = means[3 * i + 2];
-            rho = density[i];
-            sx = scales[3 * i]; sy = scales[3 * i + 1]; sz = scales[3 * i + 2];
-            q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-            radius = gauss_radius(mx, my, mz, rho, sx, sy, sz, mod, q);
-            hit = radius >= 0.0f && box_meets_sphere(box, mx, my, mz, radius);
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (lane == 0) wcount[wave] = __popcll(mask);
-        __syncthreads();
-        int slot = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-        for (int w = 0; w < QB / WAVE; ++w) {
-            if (w < wave) slot += wcount[w];
-            total += wcount[w];
-        }
-        if (hit) {
-            stage_var(st[slot].a, mx, my, mz, rho, sx, sy, sz, mod, q, v_means, v_density, v_scales, v_rotations, i);
-            st[slot].r2 = radius * radius;
-        }
-        __syncthreads();
-        if (valid) {
-            for (int j = 0; j < total; ++j) {
-                const StagedVar &a = st[j].a;
-                GaussPair p;
-                if (!point_pair(a.g, st[j].r2, x, y, z, p)) continue;
-                acc += pair_variance(a.g, p, ray, 1.0f, a.s, make_float4(a.q[0], a.q[1], a.q[2], a.q[3]), a.v);
-            }
-        }
-        __syncthreads();   // the batch and the wave counts are rewritten by the next round
-    }
+    gather_rounds<QB>(
+        cl, st, valid, [&](const Gauss &a, float radius) { return box_meets_sphere(box, a.mx, a.my, a.mz, radius); },
+        [&](StagedPointVar &d, const Gauss &a, float radius, int i) {
+            stage_var(d.a, a, cl.mod, v_means, v_density, v_scales, v_rotations, i);
+            d.r2 = radius * radius;
+        },
+        [&](const StagedPointVar &s) {
+            GaussPair p;
+            if (point_pair(s.a.g, s.r2, x, y, z, p)) acc += staged_variance(s.a, p, ray, 1.0f);
+        });
     if (n < N) out[n] = acc;
 }
 

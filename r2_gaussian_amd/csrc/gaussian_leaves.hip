@@ -15,25 +15,22 @@ namespace {
 // One thread per Gaussian, one wave per leaf: the float4 {mean, radius} of the Gaussian, its record S^-1 R^T when it has a
 // radius, and, by a min / max butterfly over the wave, the box of the leaf's spheres (gaussian_leaves.hpp).  min and max are
 // exact, so no order matters.
-__global__ void __launch_bounds__(QB) gaussian_leaves_prepare_kernel(int P, const float *__restrict__ means,
-                                                                     const float *__restrict__ density,
-                                                                     const float *__restrict__ scales, float mod,
-                                                                     const float *__restrict__ rotations, float4 *__restrict__ cent,
-                                                                     GaussRec *__restrict__ recs, BlockBox *__restrict__ boxes)
+__global__ void __launch_bounds__(QB) gaussian_leaves_prepare_kernel(Cloud cl, float4 *__restrict__ cent, GaussRec *__restrict__ recs,
+                                                                     BlockBox *__restrict__ boxes)
 {
+    const int P = cl.P;
     const int lane = threadIdx.x & (WAVE - 1);
     const int leaf = blockIdx.x * LV + threadIdx.x / WAVE;   // wave-uniform
     const int i = leaf * LEAF + lane;                        // < 2^29 + 256
     float v[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
     if (i < P) {
-        const float m[3] = { means[3 * i], means[3 * i + 1], means[3 * i + 2] };
-        const float4 q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        const float rho = density[i], sx = scales[3 * i], sy = scales[3 * i + 1], sz = scales[3 * i + 2];
-        const float r = gauss_radius(m[0], m[1], m[2], rho, sx, sy, sz, mod, q);
+        const Gauss a = load_gauss(cl, i);
+        const float m[3] = { a.mx, a.my, a.mz };
+        const float r = gauss_radius(a, cl.mod);
         const bool live = r >= 0.0f;
         cent[i] = make_float4(m[0], m[1], m[2], live ? r : -1.0f);
         if (live) {
-            recs[i] = gauss_rec(m[0], m[1], m[2], rho, sx, sy, sz, mod, q);
+            recs[i] = gauss_rec(a, cl.mod);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 v[k] = m[k] - r;
@@ -68,11 +65,9 @@ __global__ void __launch_bounds__(QB) gaussian_leaves_kernel(int N, const float 
 
 }  // namespace
 
-void leaves_prepare(int P, const float *means, const float *density, const float *scales, float mod, const float *rotations,
-                    float4 *cent, GaussRec *recs, BlockBox *boxes, hipStream_t s)
+void leaves_prepare(const Cloud &cl, float4 *cent, GaussRec *recs, BlockBox *boxes, hipStream_t s)
 {
-    gaussian_leaves_prepare_kernel<<<dim3((leaf_count(P) + LV - 1) / LV), dim3(QB), 0, s>>>(P, means, density, scales, mod, rotations,
-                                                                                           cent, recs, boxes);
+    gaussian_leaves_prepare_kernel<<<dim3((leaf_count(cl.P) + LV - 1) / LV), dim3(QB), 0, s>>>(cl, cent, recs, boxes);
 }
 
 }  // namespace r2
@@ -86,30 +81,18 @@ extern "C" int r2_integrate_gaussians_leaves(int N, const float *rays, int half_
 {
     using namespace r2;
     static_assert(sizeof(BlockBox) == 24 && sizeof(float4) == 16 && sizeof(GaussRec) == 64, "the workspace is 80 bytes per Gaussian and 24 per leaf");
-    if (N < 0 || P < 0 || (N > 0 && (!rays || !out)) || (N > 0 && P > 0 && (!means || !density || !scales || !rotations))) {
-        set_error("r2_integrate_gaussians_leaves: invalid argument");
-        return R2_ERR_INVALID;
-    }
-    if (P > (1 << 29)) {
-        set_error("r2_integrate_gaussians_leaves: shape out of range (P %d)", P);
-        return R2_ERR_INVALID;
-    }
+    const char *entry = "r2_integrate_gaussians_leaves";
+    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    if (N < 0 || P < 0 || (N > 0 && (!rays || !out)) || (N > 0 && cl.missing())) return invalid_argument(entry);
+    if (cloud_too_large(entry, P)) return R2_ERR_INVALID;
     if (N == 0) return 0;
     const size_t need = r2_integrate_gaussians_leaves_workspace_bytes(N, P);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("r2_integrate_gaussians_leaves: workspace of %zu bytes, %zu needed (r2_integrate_gaussians_leaves_workspace_bytes)",
-                  workspace ? workspace_bytes : (size_t)0, need);
-        return R2_ERR_INVALID;
-    }
-    if (need > 0 && ((size_t)workspace & 15) != 0) {
-        set_error("r2_integrate_gaussians_leaves: the workspace must be aligned to 16 bytes");
-        return R2_ERR_INVALID;
-    }
+    if (leaves_workspace_refused(entry, workspace, workspace_bytes, need)) return R2_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     float4 *cent = (float4 *)workspace;
     GaussRec *recs = P > 0 ? leaves_recs(workspace, P) : nullptr;
     BlockBox *boxes = P > 0 ? leaves_boxes(workspace, P) : nullptr;
-    if (P > 0) leaves_prepare(P, means, density, scales, scale_modifier, rotations, cent, recs, boxes, s);
+    if (P > 0) leaves_prepare(cl, cent, recs, boxes, s);
     gaussian_leaves_kernel<<<dim3((unsigned)(((long long)N + LV - 1) / LV)), dim3(QB), 0, s>>>(N, rays, half_line, P, cent, recs, boxes, out);
     R2_STAGE_CHECK(0, s, "integrate gaussians leaves");
     return 0;

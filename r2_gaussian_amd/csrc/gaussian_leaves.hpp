@@ -54,9 +54,17 @@ __host__ __device__ __forceinline__ BlockBox *leaves_boxes(void *workspace, int 
     return (BlockBox *)((char *)workspace + (size_t)P * (sizeof(float4) + sizeof(GaussRec)));
 }
 
+// host: the workspace is absent, too small or not aligned to 16 bytes (the float4 loads); sets the error text.
+inline bool leaves_workspace_refused(const char *entry, const void *workspace, size_t workspace_bytes, size_t need)
+{
+    if (workspace_too_small(entry, "r2_integrate_gaussians_leaves_workspace_bytes", workspace, workspace_bytes, need)) return true;
+    if (need == 0 || ((size_t)workspace & 15) == 0) return false;
+    set_error("%s: the workspace must be aligned to 16 bytes", entry);
+    return true;
+}
+
 // Launches the prepare kernel (gaussian_leaves.hip): the float4 and the record of every Gaussian, the box of every leaf; P > 0.
-void leaves_prepare(int P, const float *means, const float *density, const float *scales, float mod, const float *rotations,
-                    float4 *cent, GaussRec *recs, BlockBox *boxes, hipStream_t s);
+void leaves_prepare(const Cloud &cl, float4 *cent, GaussRec *recs, BlockBox *boxes, hipStream_t s);
 
 // The ray-major skeleton of the forward (GRAD = false: out[n] = the integral along ray n) and of the ray gradient
 // (GRAD = true: out[6 n ..] = G[n] d integral / d (s, d)).  One wave per ray, LV rays per workgroup, no LDS, no barrier.  The

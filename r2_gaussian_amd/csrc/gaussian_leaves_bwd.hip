@@ -18,45 +18,36 @@ namespace {
 // What the slice keeps of a ray whose line meets the leaf's box: s, d, |d|, the unit direction, tame, G[n].
 constexpr int SLICE = 12;
 
-__global__ void __launch_bounds__(QB) gaussian_leaves_bwd_kernel(int N, const float *__restrict__ rays, int half_line, int P,
-                                                                 const float *__restrict__ means, const float *__restrict__ density,
-                                                                 const float *__restrict__ scales, float mod,
-                                                                 const float *__restrict__ rotations, const float *__restrict__ G,
-                                                                 const BlockBox *__restrict__ boxes, float *__restrict__ d_means,
-                                                                 float *__restrict__ d_density, float *__restrict__ d_scales,
-                                                                 float *__restrict__ d_rotations)
+__global__ void __launch_bounds__(QB) gaussian_leaves_bwd_kernel(int N, const float *__restrict__ rays, int half_line, Cloud cl,
+                                                                 const float *__restrict__ G, const BlockBox *__restrict__ boxes,
+                                                                 CloudOut d)
 {
     __shared__ float slice[LV][SLICE][WAVE];
+    const int P = cl.P;
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int leaf = blockIdx.x * LV + wave;   // wave-uniform
     const int i = leaf * LEAF + lane;          // < 2^29 + 256
     // A wave whose leaf does not exist (the tail workgroup) runs the rounds with no hit: the barriers below are the
     // workgroup's, and the round count is the same for every wave.
     const bool exists = leaf < leaf_count(P) && N > 0;
-    float s[3] = { 1.0f, 1.0f, 1.0f }, acc[11];
-    float4 q = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    float acc[NPAR];
+    Gauss a = { 0.0f, 0.0f, 0.0f, 0.0f, { 1.0f, 1.0f, 1.0f }, make_float4(1.0f, 0.0f, 0.0f, 0.0f) };
     GaussRec g = {};
     float radius = -1.0f;
     BlockBox box = { { INFINITY, INFINITY, INFINITY }, { -INFINITY, -INFINITY, -INFINITY } };
 #pragma unroll
-    for (int k = 0; k < 11; ++k) acc[k] = 0.0f;
+    for (int k = 0; k < NPAR; ++k) acc[k] = 0.0f;
     if (exists) box = boxes[leaf];
     if (i < P) {
-        const float mx = means[3 * i], my = means[3 * i + 1], mz = means[3 * i + 2], rho = density[i];
-        s[0] = scales[3 * i]; s[1] = scales[3 * i + 1]; s[2] = scales[3 * i + 2];
-        q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-        radius = gauss_radius(mx, my, mz, rho, s[0], s[1], s[2], mod, q);
-        if (radius >= 0.0f) g = gauss_rec(mx, my, mz, rho, s[0], s[1], s[2], mod, q);
+        a = load_gauss(cl, i);
+        radius = gauss_radius(a, cl.mod);
+        if (radius >= 0.0f) g = gauss_rec(a, cl.mod);
     }
     const bool live = radius >= 0.0f;
     float (*sl)[WAVE] = slice[wave];
     for (long long base = 0; base < N; base += WAVE) {
         const long long n = base + lane;
-        BundleRay y;
-        y.y = Ray{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        y.len = 0.0f;
-        y.valid = false;
-        if (exists && n < N) y = bundle_ray(rays, n);
+        const BundleRay y = bundle_ray(rays, n, exists ? N : 0);
         const BundleDir u = bundle_dir(y);
         float v[6];
         const bool hit = exists && bundle_ray_box(y, u, half_line, box, v);
@@ -84,21 +75,15 @@ __global__ void __launch_bounds__(QB) gaussian_leaves_bwd_kernel(int N, const fl
                 if (bundle_line_misses(r, w, g.mx, g.my, g.mz, radius)) continue;
                 GaussPair p;
                 if (!bundle_pair(g, r.y, half_line, p)) continue;
-                float o[11];
-                gauss_pair_grad(g, p, r.y, r.len, sl[11][j], s, q, o);
+                float o[NPAR];
+                gauss_pair_grad(g, p, r.y, r.len, sl[11][j], a.s, a.q, o);
 #pragma unroll
-                for (int t = 0; t < 11; ++t) acc[t] += o[t];
+                for (int t = 0; t < NPAR; ++t) acc[t] += o[t];
             }
         }
         __syncthreads();   // the slice is rewritten by the next round
     }
-    if (i < P) {
-        d_means[3 * i] = acc[0]; d_means[3 * i + 1] = acc[1]; d_means[3 * i + 2] = acc[2];
-        d_density[i] = acc[3];
-        d_scales[3 * i] = acc[4]; d_scales[3 * i + 1] = acc[5]; d_scales[3 * i + 2] = acc[6];
-        d_rotations[4 * i] = acc[7]; d_rotations[4 * i + 1] = acc[8]; d_rotations[4 * i + 2] = acc[9];
-        d_rotations[4 * i + 3] = acc[10];
-    }
+    if (i < P) store_gauss(d, i, acc);
 }
 
 __global__ void __launch_bounds__(QB) gaussian_leaves_rays_bwd_kernel(int N, const float *__restrict__ rays, int half_line, int P,
@@ -121,35 +106,20 @@ extern "C" int r2_integrate_gaussians_leaves_backward(int N, const float *rays, 
 {
     using namespace r2;
     static_assert(sizeof(BlockBox) == 24 && sizeof(float4) == 16 && sizeof(GaussRec) == 64, "the workspace is 80 bytes per Gaussian and 24 per leaf");
-    if (N < 0 || P < 0 || (N > 0 && (!rays || !dL_dout)) ||
-        (P > 0 && (!means || !density || !scales || !rotations || !dL_dmeans || !dL_ddensity || !dL_dscales || !dL_drotations))) {
-        set_error("r2_integrate_gaussians_leaves_backward: invalid argument");
-        return R2_ERR_INVALID;
-    }
-    if (P > (1 << 29)) {
-        set_error("r2_integrate_gaussians_leaves_backward: shape out of range (P %d)", P);
-        return R2_ERR_INVALID;
-    }
+    const char *entry = "r2_integrate_gaussians_leaves_backward";
+    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    const CloudOut d = { dL_dmeans, dL_ddensity, dL_dscales, dL_drotations };
+    if (N < 0 || P < 0 || (N > 0 && (!rays || !dL_dout)) || cl.missing() || d.missing(P)) return invalid_argument(entry);
+    if (cloud_too_large(entry, P)) return R2_ERR_INVALID;
     const size_t need = r2_integrate_gaussians_leaves_workspace_bytes(N, P);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        set_error("r2_integrate_gaussians_leaves_backward: workspace of %zu bytes, %zu needed "
-                  "(r2_integrate_gaussians_leaves_workspace_bytes)", workspace ? workspace_bytes : (size_t)0, need);
-        return R2_ERR_INVALID;
-    }
-    if (need > 0 && ((size_t)workspace & 15) != 0) {
-        set_error("r2_integrate_gaussians_leaves_backward: the workspace must be aligned to 16 bytes");
-        return R2_ERR_INVALID;
-    }
+    if (leaves_workspace_refused(entry, workspace, workspace_bytes, need)) return R2_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     float4 *cent = (float4 *)workspace;
     GaussRec *recs = need > 0 ? leaves_recs(workspace, P) : nullptr;     // N = 0 or P = 0: no workspace
     BlockBox *boxes = need > 0 ? leaves_boxes(workspace, P) : nullptr;
     if (P > 0) {
-        if (N > 0) leaves_prepare(P, means, density, scales, scale_modifier, rotations, cent, recs, boxes, s);
-        gaussian_leaves_bwd_kernel<<<dim3((leaf_count(P) + LV - 1) / LV), dim3(QB), 0, s>>>(N, rays, half_line, P, means, density, scales,
-                                                                                           scale_modifier, rotations, dL_dout, boxes,
-                                                                                           dL_dmeans, dL_ddensity, dL_dscales,
-                                                                                           dL_drotations);
+        if (N > 0) leaves_prepare(cl, cent, recs, boxes, s);
+        gaussian_leaves_bwd_kernel<<<dim3((leaf_count(P) + LV - 1) / LV), dim3(QB), 0, s>>>(N, rays, half_line, cl, dL_dout, boxes, d);
     }
     if (N > 0 && dL_drays)
         gaussian_leaves_rays_bwd_kernel<<<dim3((unsigned)(((long long)N + LV - 1) / LV)), dim3(QB), 0, s>>>(

@@ -22,7 +22,7 @@
 // carries 1 %), and a point in the sphere lies in its block's box, which then meets the sphere -- in float32 as well: the
 // box's distance is componentwise at most the point's, and rounding is monotone.
 #pragma once
-#include "gaussian_rays.hpp"
+#include "gaussian_skeleton.hpp"
 
 namespace r2 {
 
@@ -137,22 +137,17 @@ struct StagedPoint {
     float r2;
 };
 
-// The point-major skeleton of the forward (GRAD = false: out[n] = the field at point n) and of the point gradient
-// (GRAD = true: out[3 n ..] = G[n] d field / d x).  One workgroup per block of QB points, one thread per point.  The workgroup
-// walks the P Gaussians in index order, QB at a time: thread i tests the sphere of Gaussian base + i against the block's box,
-// the hits are compacted IN ORDER (wave ballots + the wave counts) into an LDS batch with their S^-1 R^T, and every point
-// adds the batch's pairs in batch order.  A point therefore adds its pairs in ascending Gaussian index, in one thread.
+// The point-major kernel of the forward (GRAD = false: out[n] = the field at point n) and of the point gradient
+// (GRAD = true: out[3 n ..] = G[n] d field / d x) on gaussian_skeleton.hpp's gather_rounds.  One workgroup per block of QB
+// points, one thread per point.  A Gaussian is a hit when its sphere meets the block's box; the hits are staged with their
+// S^-1 R^T, and every point adds the batch's pairs in batch order: in ascending Gaussian index, in one thread.
 template <bool GRAD>
-__device__ __forceinline__ void query_points_block(int N, const float *__restrict__ points, int P, const float *__restrict__ means,
-                                                   const float *__restrict__ density, const float *__restrict__ scales, float mod,
-                                                   const float *__restrict__ rotations, const float *__restrict__ G,
-                                                   float *__restrict__ out)
+__device__ __forceinline__ void query_points_block(int N, const float *__restrict__ points, const Cloud &cl,
+                                                   const float *__restrict__ G, float *__restrict__ out)
 {
     __shared__ StagedPoint st[QB];
     __shared__ float wbox[QB / WAVE][6];
-    __shared__ int wcount[QB / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const long long n = (long long)blockIdx.x * QB + tid;   // < 2^31 + QB
+    const long long n = (long long)blockIdx.x * QB + threadIdx.x;   // < 2^31 + QB
     float x = 0.f, y = 0.f, z = 0.f;
     if (n < N) {
         x = points[3 * n]; y = points[3 * n + 1]; z = points[3 * n + 2];
@@ -161,48 +156,23 @@ __device__ __forceinline__ void query_points_block(int N, const float *__restric
     const BlockBox box = block_box(valid, x, y, z, wbox);
     const float Gn = GRAD && valid ? G[n] : 0.0f;
     float acc[3] = { 0.0f, 0.0f, 0.0f };
-    for (int base = 0; base < P; base += QB) {
-        const int i = base + tid;
-        bool hit = false;
-        float mx = 0.f, my = 0.f, mz = 0.f, rho = 0.f, sx = 0.f, sy = 0.f, sz = 0.f, radius = 0.f;
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < P) {
-            mx = means[3 * i]; my = means[3 * i + 1]; mz = means[3 * i + 2];
-            rho = density[i];
-            sx = scales[3 * i]; sy = scales[3 * i + 1]; sz = scales[3 * i + 2];
-            q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-            radius = gauss_radius(mx, my, mz, rho, sx, sy, sz, mod, q);
-            hit = radius >= 0.0f && box_meets_sphere(box, mx, my, mz, radius);
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (lane == 0) wcount[wave] = __popcll(mask);
-        __syncthreads();
-        int slot = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-        for (int w = 0; w < QB / WAVE; ++w) {
-            if (w < wave) slot += wcount[w];
-            total += wcount[w];
-        }
-        if (hit) {
-            st[slot].g = gauss_rec(mx, my, mz, rho, sx, sy, sz, mod, q);
-            st[slot].r2 = radius * radius;
-        }
-        __syncthreads();
-        if (valid) {
-            for (int j = 0; j < total; ++j) {
-                GaussPair p;
-                if (!point_pair(st[j].g, st[j].r2, x, y, z, p)) continue;
-                if (GRAD) {
-                    float o[3];
-                    point_pair_dx(st[j].g, p, x, y, z, Gn, o);
-                    acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
-                } else {
-                    acc[0] += point_term(st[j].g, p);
-                }
+    gather_rounds<QB>(
+        cl, st, valid, [&](const Gauss &a, float radius) { return box_meets_sphere(box, a.mx, a.my, a.mz, radius); },
+        [&](StagedPoint &d, const Gauss &a, float radius, int) {
+            d.g = gauss_rec(a, cl.mod);
+            d.r2 = radius * radius;
+        },
+        [&](const StagedPoint &s) {
+            GaussPair p;
+            if (!point_pair(s.g, s.r2, x, y, z, p)) return;
+            if (GRAD) {
+                float o[3];
+                point_pair_dx(s.g, p, x, y, z, Gn, o);
+                acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
+            } else {
+                acc[0] += point_term(s.g, p);
             }
-        }
-        __syncthreads();   // the batch and the wave counts are rewritten by the next round
-    }
+        });
     if (n < N) {
         if (GRAD) {
             out[3 * n] = acc[0]; out[3 * n + 1] = acc[1]; out[3 * n + 2] = acc[2];

@@ -2,8 +2,8 @@
 // (include/r2hip.h: r2_project_gaussians_rays_backward; the per-pair arithmetic is gaussian_ray_grad.hpp's on top of
 // gaussian_rays.hpp's pair, rectangle and cone rule, so a pair is differentiated exactly when the forward summed it).
 //
-// Pixel-major, on the forward's skeleton (gaussian_project.hip): one workgroup per 16 x 16 pixel tile and view, one thread per
-// pixel; the P Gaussians are walked 256 per round, thread i tests the rectangle of Gaussian base + i against the tile, the hits
+// Pixel-major, on the forward's skeleton (gaussian_skeleton.hpp: tile_rounds): one workgroup per 16 x 16 pixel tile and view, one thread
+// per pixel; the P Gaussians are walked 256 per round, thread i tests the rectangle of Gaussian base + i against the tile, the hits
 // are compacted IN ORDER into an LDS batch, and every pixel adds the batch's pairs whose rectangle holds it to its six sums
 // g_s, g_d -- in ascending Gaussian index, in one thread.  At the end a pixel forms its twelve contributions, the workgroup adds
 // the 256 x 12 values in one fixed order (gaussian_ray_grad.hpp: block_sum12) and writes partial[view][tile][12] into the
@@ -11,86 +11,34 @@
 // in ascending order, then the same fixed-order sum -- and writes dL_drays[view].  No atomics, no allocation and no host
 // synchronisation, the same bits on every call, and nothing a view computes depends on another view.
 #include "gaussian_ray_grad.hpp"
+#include "gaussian_skeleton.hpp"
 
 namespace r2 {
 
 namespace {
 
-struct Staged {
-    GaussRec g;
-    PixRect q;
-};
-
-__global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, int W, const float *__restrict__ rays, int cone, int P,
-                                                                       const float *__restrict__ means,
-                                                                       const float *__restrict__ density,
-                                                                       const float *__restrict__ scales, float mod,
-                                                                       const float *__restrict__ rotations,
+__global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, int W, const float *__restrict__ rays, int cone, Cloud cl,
                                                                        const float *__restrict__ G, float *__restrict__ partial)
 {
     static_assert(RG == TILE2D * TILE2D, "one thread per pixel of a tile");
     __shared__ ViewGeom vg;
     __shared__ Staged st[RG];
-    __shared__ int wcount[RG / WAVE];
     __shared__ float wsum[RG / WAVE][12];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int view = blockIdx.z;
-    const int tc0 = blockIdx.x * TILE2D, tr0 = blockIdx.y * TILE2D;
-    const int tc1 = min(tc0 + TILE2D, W) - 1, tr1 = min(tr0 + TILE2D, H) - 1;
-    const int c = tc0 + (tid & (TILE2D - 1)), r = tr0 + tid / TILE2D;
-    const bool inside = c < W && r < H;
-    const float *R = rays + 12 * view;
-    if (tid == 0) vg = view_geom(R, cone);
-    __syncthreads();
-    const Ray y = pixel_ray(R, cone, r, c);
-    const float len = ray_length(y);
-    const float Gp = inside ? G[((size_t)view * H + r) * W + c] : 0.0f;
+    const PixelTile t = pixel_tile(rays, cone, H, W, vg);
+    const float Gp = t.inside ? G[((size_t)t.view * H + t.r) * W + t.c] : 0.0f;
     float gs[3] = { 0.f, 0.f, 0.f }, gd[3] = { 0.f, 0.f, 0.f };
-    for (int base = 0; base < P; base += RG) {
-        const int i = base + tid;
-        bool hit = false;
-        float mx = 0.f, my = 0.f, mz = 0.f, rho = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        PixRect rc;
-        if (i < P) {
-            mx = means[3 * i]; my = means[3 * i + 1]; mz = means[3 * i + 2];
-            rho = density[i];
-            sx = scales[3 * i]; sy = scales[3 * i + 1]; sz = scales[3 * i + 2];
-            q = make_float4(rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2], rotations[4 * i + 3]);
-            const float radius = gauss_radius(mx, my, mz, rho, sx, sy, sz, mod, q);
-            if (radius >= 0.0f && gauss_rect(vg, cone, mx, my, mz, radius, H, W, rc))
-                hit = rc.c0 <= tc1 && rc.c1 >= tc0 && rc.r0 <= tr1 && rc.r1 >= tr0;
-        }
-        const unsigned long long mask = __ballot(hit);
-        if (lane == 0) wcount[wave] = __popcll(mask);
-        __syncthreads();
-        int slot = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-#pragma unroll
-        for (int w = 0; w < RG / WAVE; ++w) {
-            if (w < wave) slot += wcount[w];
-            total += wcount[w];
-        }
-        if (hit) {
-            st[slot].g = gauss_rec(mx, my, mz, rho, sx, sy, sz, mod, q);
-            st[slot].q = rc;
-        }
-        __syncthreads();
-        if (inside) {
-            for (int j = 0; j < total; ++j) {
-                const PixRect &b = st[j].q;
-                if (c < b.c0 || c > b.c1 || r < b.r0 || r > b.r1) continue;
-                GaussPair p;
-                if (gauss_pair(st[j].g, y, cone, p)) gauss_pair_ray_grad(st[j].g, p, y, len, Gp, gs, gd);
-            }
-        }
-        __syncthreads();   // the batch and the wave counts are rewritten by the next round
-    }
+    tile_rounds(
+        cl, t, vg, cone, H, W, st, [&](Staged &d, const Gauss &a, int) { d.g = gauss_rec(a, cl.mod); },
+        [&](const Staged &s) {
+            GaussPair p;
+            if (gauss_pair(s.g, t.y, cone, p)) gauss_pair_ray_grad(s.g, p, t.y, t.len, Gp, gs, gd);
+        });
     float o[12];   // a thread outside the detector has added nothing: twelve zeros
-    pixel_ray_grad(cone, r, c, gs, gd, o);
+    pixel_ray_grad(cone, t.r, t.c, gs, gd, o);
     block_sum12(o, wsum);
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        float *dst = partial + ((size_t)view * gridDim.x * gridDim.y + tile) * 12;
+        float *dst = partial + ((size_t)t.view * gridDim.x * gridDim.y + tile) * 12;
 #pragma unroll
         for (int k = 0; k < 12; ++k) dst[k] = o[k];
     }
@@ -131,12 +79,10 @@ extern "C" int r2_project_gaussians_rays_backward(int V, int H, int W, const flo
                                                   size_t workspace_bytes, void *stream)
 {
     using namespace r2;
-    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !dL_dout || !dL_drays ||
-        (P > 0 && (!means || !density || !scales || !rotations))) {
-        set_error("r2_project_gaussians_rays_backward: invalid argument");
-        return R2_ERR_INVALID;
-    }
-    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || (long long)H * W >= (1LL << 30) || P > (1 << 29)) {
+    const char *entry = "r2_project_gaussians_rays_backward";
+    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !dL_dout || !dL_drays || cl.missing()) return invalid_argument(entry);
+    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || (long long)H * W >= (1LL << 30) || P > CLOUD_MAX_P) {
         set_error("r2_project_gaussians_rays_backward: shape out of range (V %d, H %d, W %d, P %d)", V, H, W, P);
         return R2_ERR_INVALID;
     }
@@ -146,15 +92,11 @@ extern "C" int r2_project_gaussians_rays_backward(int V, int H, int W, const flo
         return 0;
     }
     const size_t need = r2_project_gaussians_rays_backward_workspace_bytes(V, H, W);
-    if (!workspace || workspace_bytes < need) {
-        set_error("r2_project_gaussians_rays_backward: workspace of %zu bytes, %zu needed "
-                  "(r2_project_gaussians_rays_backward_workspace_bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    if (workspace_too_small(entry, "r2_project_gaussians_rays_backward_workspace_bytes", workspace, workspace_bytes, need))
         return R2_ERR_INVALID;
-    }
     const dim3 grid((W + TILE2D - 1) / TILE2D, (H + TILE2D - 1) / TILE2D, V);
     float *partial = (float *)workspace;
-    gaussian_project_rays_bwd_kernel<<<grid, dim3(RG), 0, s>>>(H, W, rays, cone, P, means, density, scales, scale_modifier,
-                                                               rotations, dL_dout, partial);
+    gaussian_project_rays_bwd_kernel<<<grid, dim3(RG), 0, s>>>(H, W, rays, cone, cl, dL_dout, partial);
     gaussian_project_rays_reduce_kernel<<<dim3(V), dim3(RG), 0, s>>>((int)tiles_of(H, W), partial, dL_drays);
     R2_STAGE_CHECK(0, s, "project gaussians rays backward");
     return 0;

@@ -11,12 +11,9 @@ namespace r2 {
 
 namespace {
 
-__global__ void __launch_bounds__(QB) gaussian_query_kernel(int N, const float *__restrict__ points, int P,
-                                                            const float *__restrict__ means, const float *__restrict__ density,
-                                                            const float *__restrict__ scales, float mod,
-                                                            const float *__restrict__ rotations, float *__restrict__ out)
+__global__ void __launch_bounds__(QB) gaussian_query_kernel(int N, const float *__restrict__ points, Cloud cl, float *__restrict__ out)
 {
-    query_points_block<false>(N, points, P, means, density, scales, mod, rotations, nullptr, out);
+    query_points_block<false>(N, points, cl, nullptr, out);
 }
 
 }  // namespace
@@ -27,18 +24,13 @@ extern "C" int r2_query_gaussians(int N, const float *points, int P, const float
                                   float scale_modifier, const float *rotations, float *out, void *stream)
 {
     using namespace r2;
-    if (N < 0 || P < 0 || (N > 0 && (!points || !out)) || (N > 0 && P > 0 && (!means || !density || !scales || !rotations))) {
-        set_error("r2_query_gaussians: invalid argument");
-        return R2_ERR_INVALID;
-    }
-    if (P > (1 << 29)) {
-        set_error("r2_query_gaussians: shape out of range (P %d)", P);
-        return R2_ERR_INVALID;
-    }
+    const char *entry = "r2_query_gaussians";
+    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    if (N < 0 || P < 0 || (N > 0 && (!points || !out)) || (N > 0 && cl.missing())) return invalid_argument(entry);
+    if (cloud_too_large(entry, P)) return R2_ERR_INVALID;
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    gaussian_query_kernel<<<dim3(query_blocks(N)), dim3(QB), 0, s>>>(N, points, P, means, density, scales, scale_modifier,
-                                                                         rotations, out);
+    gaussian_query_kernel<<<dim3(query_blocks(N)), dim3(QB), 0, s>>>(N, points, cl, out);
     R2_STAGE_CHECK(0, s, "query gaussians");
     return 0;
 }
