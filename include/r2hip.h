@@ -710,6 +710,39 @@ R2_API int r2_project_gaussians_variance(int V, int H, int W, const float *rays 
                                          const float *v_scales /* [P,3] */, const float *v_rotations /* [P,4] */,
                                          float *out /* [V,H,W] */, void *stream);
 
+/* ---- Jacobian products of the exact projector (no counterpart in the reference) ----------------------------------------------
+ * r2_project_gaussians_backward applies J^T, the transpose of the image's Jacobian in the cloud's parameters, and
+ * r2_project_gaussians_fisher the diagonal of J^T W J.  These two apply J itself, pixel-major on the forward's skeleton (one
+ * workgroup per 16 x 16 tile and view, one thread per pixel, ascending Gaussian index in one thread).
+ * r2_project_gaussians_jvp: out[v][r][c] = the sum over the pixel's pairs of
+ *     pair_tangent = tan[i][0] * o[0], then + tan[i][t] * o[t] in ascending t,
+ * o = the pair's eleven derivatives with G = 1 (csrc/gaussian_rays.hpp: gauss_pair_grad; the parameters and their order as for
+ * the Fisher entries above), tan = the tangent of Gaussian i (t_means [P,3], t_density [P], t_scales [P,3], t_rotations
+ * [P,4]): the directional derivative (J t) of r2_project_gaussians' image along t.  The pairs are exactly those the forward
+ * sums (rectangle, then the pair rule); the culling, the cone rule and the cut are piecewise constant and NOT differentiated,
+ * as in the backward.  The tangent of a Gaussian that is staged on no tile (off the detector, behind the source, a non-finite
+ * parameter or a scale <= 0) is never read.  The staged record is the projection variance's (156 bytes).  P = 0 writes zeros.
+ * Identities: <G, J t> = <J^T G, t> with r2_project_gaussians_backward's J^T G up to rounding (the same pairs added in two
+ * orders); linear in t, and exactly so for a factor 2; t = (0, density, 0, 0) gives the forward's image up to rounding.
+ * r2_project_gaussians_ray_jacobian: out[v][0..2][r][c] = d pixel / d s and out[v][3..5][r][c] = d pixel / d d, the pixel's
+ * derivative in the start s and the direction d of its own ray: the sums over the pixel's pairs of g_s and g_d of
+ * r2_project_gaussians_rays_backward with G = 1 (csrc/gaussian_ray_grad.hpp: gauss_pair_ray_grad).  Planar, so that a tile row
+ * stores 64 contiguous bytes per plane.  The pixel point is P = p00 + c pu + r pv; cone beam has s = a, d = P - a, parallel
+ * beam s = P, d = a: contracting the six planes with G by that rule (pixel_ray_grad) and adding over the pixels gives
+ * r2_project_gaussians_rays_backward's dL_drays up to rounding, and contracting them with the tangent of (s, d) gives the
+ * image's directional derivative along any change of the geometry.  P = 0 writes zeros.
+ * Both: V <= 65535, P <= 2^29; argument checks as r2_project_gaussians_variance; separately rounded float32 in the order
+ * written; no atomics, no workspace, no allocation, no host synchronisation; bit-reproducible; a view's output does not
+ * depend on the other views. */
+R2_API int r2_project_gaussians_jvp(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                    const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                    const float *t_means /* [P,3] */, const float *t_density /* [P] */,
+                                    const float *t_scales /* [P,3] */, const float *t_rotations /* [P,4] */,
+                                    float *out /* [V,H,W] */, void *stream);
+R2_API int r2_project_gaussians_ray_jacobian(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                             const float *means, const float *density, const float *scales, float scale_modifier,
+                                             const float *rotations, float *out /* [V,6,H,W] */, void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

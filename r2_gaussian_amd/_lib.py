@@ -93,6 +93,8 @@ _SIGNATURES = {
     "r2_project_gaussians_fisher": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
     "r2_query_gaussians_variance": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
     "r2_project_gaussians_variance": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
+    "r2_project_gaussians_jvp": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
+    "r2_project_gaussians_ray_jacobian": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
     "r2_tv_descent_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),

@@ -67,6 +67,8 @@ SOURCES = {
     # EXACT for the same two reasons (tests/gaussian_fisher_ref.py, gaussian_fisher.hpp on gaussian_rays.hpp / gaussian_points.hpp)
     "gaussian_fisher.hip": EXACT,
     "gaussian_variance.hip": EXACT,
+    # EXACT for the same two reasons (tests/gaussian_tangent_ref.py, gaussian_tangent.hpp on gaussian_fisher.hpp / gaussian_ray_grad.hpp)
+    "gaussian_tangent.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

@@ -12,6 +12,10 @@ camera cannot describe (shifted, tilted) can be projected with ``project_gaussia
 ``integrate_rays`` is the same line integral along rays that are no detector's: any [..., 3] starts and directions, on the
 kernels of csrc/gaussian_bundle.hip and csrc/gaussian_bundle_bwd.hip (``r2_integrate_gaussians`` and its backward), or, with
 ``method="leaves"``, of csrc/gaussian_leaves.hip and csrc/gaussian_leaves_bwd.hip (``r2_integrate_gaussians_leaves``).
+
+``project_gaussians_jvp`` / ``project_gaussians_rays_jvp`` apply the projector's Jacobian forwards, to a tangent of the cloud,
+of the rays, or both, on the kernels of csrc/gaussian_tangent.hip (``r2_project_gaussians_jvp``,
+``r2_project_gaussians_ray_jacobian``); gauss_newton.py and ``geometry.refine_geometry_lm`` build their solvers on them.
 """
 import torch
 
@@ -127,6 +131,80 @@ def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0
     views, H, W = projector.check_views(views)
     return project_gaussians_rays(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
                                   rotation, scale_modifier, out)
+
+
+def _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0):
+    """``geometry.ray_jacobian``, where its documentation is: [V,6,H,W] on ``r2_project_gaussians_ray_jacobian``."""
+    rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
+    rays = projector.device_rays(rays.detach(), dev)
+    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    out = torch.empty((V, 6, H, W), dtype=_F32, device=dev)
+    with _on_device(dev):
+        rc = _lib.lib().r2_project_gaussians_ray_jacobian(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
+                                                          s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(),
+                                                          _stream(dev))
+    _lib.check(rc, "r2_project_gaussians_ray_jacobian")
+    return out
+
+
+def contract_ray_jacobian(jac, ray_tangent, cone):
+    """The ray Jacobian ``jac`` [V,6,H,W] (``geometry.ray_jacobian``) applied to a tangent ``ray_tangent`` [V,12] of the rays
+    {a, p00, pu, pv} -> [V,H,W] float64: the pixel point is P = p00 + c pu + r pv, so t_P = t_p00 + c t_pu + r t_pv; cone beam
+    has ds = t_a, dd = t_P - t_a, parallel beam ds = t_P, dd = t_a.  Plain torch in float64 on the device of ``jac``."""
+    V, _, H, W = jac.shape
+    t = ray_tangent.to(device=jac.device, dtype=torch.float64)
+    c = torch.arange(W, dtype=torch.float64, device=jac.device)[None, None, :, None]
+    r = torch.arange(H, dtype=torch.float64, device=jac.device)[None, :, None, None]
+    tP = t[:, None, None, 3:6] + c * t[:, None, None, 6:9] + r * t[:, None, None, 9:12]
+    ta = t[:, None, None, 0:3].expand_as(tP)
+    ds, dd = (ta, tP - ta) if cone else (tP, ta)
+    j = jac.to(torch.float64)
+    return (j[:, 0:3].permute(0, 2, 3, 1) * ds).sum(-1) + (j[:, 3:6].permute(0, 2, 3, 1) * dd).sum(-1)
+
+
+@torch.no_grad()
+def project_gaussians_rays_jvp(rays, cone, H, W, xyz, density, scaling, rotation, tangents=None, ray_tangent=None,
+                               scale_modifier=1.0):
+    """The directional derivative [V,H,W] (GPU, float32) of ``project_gaussians_rays`` on the same arguments: J t for a tangent
+    of the cloud, of the rays, or of both (their sum).  ``tangents``: a 4-tuple shaped like the cloud (xyz [P,3], density
+    [P,1] or [P], scaling [P,3], rotation [P,4]), in the parameters of the projector's gradient (the scales as given, the
+    quaternion as it comes): one launch of ``r2_project_gaussians_jvp``, the cost of ``uncertainty.projection_variance``.
+    ``ray_tangent`` [V,12]: one launch of ``r2_project_gaussians_ray_jacobian`` (``geometry.ray_jacobian``), contracted in
+    torch with every pixel's (ds, dd) (``contract_ray_jacobian``).  At least one of the two must be given.  Which pairs are
+    summed is piecewise constant and not differentiated, as in the backward, whose transpose this is:
+    <G, J t> = <J^T G, t> up to rounding.  The result is not attached to autograd.  No host synchronisation."""
+    if tangents is None and ray_tangent is None:
+        raise ValueError("give tangents, ray_tangent or both")
+    rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
+    out = None
+    if tangents is not None:
+        from .uncertainty import _check_group_tuple
+        tx, td, ts, tr = _check_group_tuple(tangents, P, dev, "tangents")
+        rdev = projector.device_rays(rays.detach(), dev)
+        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+        out = torch.empty((V, H, W), dtype=_F32, device=dev)
+        with _on_device(dev):
+            rc = _lib.lib().r2_project_gaussians_jvp(V, H, W, rdev.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
+                                                     s.data_ptr(), float(scale_modifier), r.data_ptr(), tx.data_ptr(), td.data_ptr(),
+                                                     ts.data_ptr(), tr.data_ptr(), out.data_ptr(), _stream(dev))
+        _lib.check(rc, "r2_project_gaussians_jvp")
+    if ray_tangent is not None:
+        ray_tangent = torch.as_tensor(ray_tangent)
+        if tuple(ray_tangent.shape) != (V, 12):
+            raise ValueError("ray_tangent must be [%d,12], got %s" % (V, tuple(ray_tangent.shape)))
+        jac = _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
+        part = contract_ray_jacobian(jac, ray_tangent.detach(), bool(cone)).to(_F32)
+        out = part if out is None else out + part
+    return out
+
+
+def project_gaussians_jvp(views, xyz, density, scaling, rotation, tangents=None, ray_tangent=None, scale_modifier=1.0):
+    """``project_gaussians_rays_jvp`` on ``views`` (``scene.View`` list: one detector size, one beam mode)."""
+    views, H, W = projector.check_views(views)
+    return project_gaussians_rays_jvp(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
+                                      rotation, tangents, ray_tangent, scale_modifier)
 
 
 _BLOCKS = ("r2_integrate_gaussians", "r2_integrate_gaussians_backward", "r2_integrate_gaussians_workspace_bytes")
