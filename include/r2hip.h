@@ -743,6 +743,74 @@ R2_API int r2_project_gaussians_ray_jacobian(int V, int H, int W, const float *r
                                              const float *means, const float *density, const float *scales, float scale_modifier,
                                              const float *rotations, float *out /* [V,6,H,W] */, void *stream);
 
+/* ---- projection plans: per-tile Gaussian lists for the pixel-major operators of the exact projector -----------------------------
+ * r2_project_gaussians, its ray backward, the projection variance, the JVP and the ray Jacobian are pixel-major: every 16 x 16
+ * tile of every view walks all P Gaussians and tests each one's detector rectangle against the tile.  For a cloud and a geometry
+ * that are projected many times (a Gauss-Newton solve) a plan keeps the answer: with Tx = ceil(W / 16), Ty = ceil(H / 16) and
+ * T = Tx Ty, list k = view T + ty Tx + tx is ids[offsets[k] .. offsets[k + 1]), where
+ *     offsets  long long [V T + 1], offsets[0] = 0, non-decreasing; offsets[V T] is the number of instances,
+ *     ids      int [instances]: the indices of the Gaussians the unplanned kernels stage for that tile -- a radius (no
+ *              non-finite parameter, every scale > 0), a detector rectangle (csrc/gaussian_rays.hpp: gauss_radius, gauss_rect)
+ *              and the rectangle meets the tile -- ASCENDING within a list.
+ * Building (two calls, so that the caller can size ids in between):
+ * r2_project_gaussians_plan_count computes every Gaussian's rectangle once per view (V P evaluations where an unplanned call
+ * makes V T P) into a table in `workspace` (r2_project_gaussians_plan_workspace_bytes(V, H, W, P) = 8 bytes per view and
+ * Gaussian; 0 for P = 0), counts every tile's hits and scans the counts into `offsets`; the caller reads offsets[V T].
+ * r2_project_gaussians_plan_fill walks the SAME table (the workspace of the count, untouched in between, and the same
+ * arguments) and writes the ids.  It refuses nothing on the device: an id is written only below ids_capacity and below its
+ * list's end, so a capacity that is too small loses the instances beyond it and nothing else.
+ * No atomics anywhere: a tile's hits are compacted in index order by wave ballots and wave counts, so building twice gives
+ * the same bytes, and the ids of a view's lists do not depend on the other views of the call.  Cost: V P rectangles, then
+ * 2 V T P tests of four integer compares each on 8-byte entries, against V T P rectangles (about 60 float operations, a
+ * square root and two divisions each in cone beam) for ONE unplanned call.  P = 0: the offsets are zeros, no workspace.
+ * V <= 65535, Tx <= 65535, Ty <= 65535, P <= 2^29.  NULL or too small a workspace with P > 0: R2_ERR_INVALID, nothing written.
+ * Consuming: each *_planned entry takes its parent's arguments and, before the stream, offsets, ids and ids_capacity (the
+ * number of ints ids holds), and writes what its parent writes, BIT FOR BIT when the lists are a plan's: an entry is staged
+ * as the parent stages a hit (radius and rectangle are computed again, the same record is filled), the test of the pixel
+ * against the rectangle and the pair are the parent's, so a pixel adds the same pairs in the same ascending order in one
+ * thread.  THE LISTS DRIVE THE KERNEL: a Gaussian that is absent from a tile's list contributes nothing to that tile even if
+ * its rectangle meets it, so a caller may hand in lists of their own -- ascending, every id < P; an id outside [0, P) or a
+ * Gaussian without radius or rectangle is skipped.  A tile with an empty list still writes its pixels (zeros; its zero partial
+ * in the ray backward).  Reads are bounded: both ends of a list are clamped to [0, ids_capacity], so wrong offsets give a
+ * wrong image and never a read outside ids.  offsets NULL, ids NULL with ids_capacity > 0, or ids_capacity < 0 (P > 0):
+ * R2_ERR_INVALID, nothing written; every other check is the parent's.  P = 0 writes zeros and needs no lists.  The plan is
+ * valid for exactly the (V, H, W, rays, cone, cloud, scale_modifier) it was built with; the C ABI does not check that. */
+R2_API size_t r2_project_gaussians_plan_workspace_bytes(int V, int H, int W, int P);
+R2_API int r2_project_gaussians_plan_count(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                           const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                           long long *offsets /* [V T + 1] */, void *workspace, size_t workspace_bytes,
+                                           void *stream);
+R2_API int r2_project_gaussians_plan_fill(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                          const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                          const long long *offsets /* [V T + 1] */, int *ids, long long ids_capacity,
+                                          void *workspace, size_t workspace_bytes, void *stream);
+R2_API int r2_project_gaussians_planned(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                        const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                        float *out /* [V,H,W] */, const long long *offsets, const int *ids, long long ids_capacity,
+                                        void *stream);
+R2_API int r2_project_gaussians_rays_backward_planned(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                                      const float *means, const float *density, const float *scales,
+                                                      float scale_modifier, const float *rotations,
+                                                      const float *dL_dout /* [V,H,W] */, float *dL_drays /* [V,12] */,
+                                                      void *workspace, size_t workspace_bytes, const long long *offsets,
+                                                      const int *ids, long long ids_capacity, void *stream);
+R2_API int r2_project_gaussians_variance_planned(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                                 const float *means, const float *density, const float *scales,
+                                                 float scale_modifier, const float *rotations, const float *v_means,
+                                                 const float *v_density, const float *v_scales, const float *v_rotations,
+                                                 float *out /* [V,H,W] */, const long long *offsets, const int *ids,
+                                                 long long ids_capacity, void *stream);
+R2_API int r2_project_gaussians_jvp_planned(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P, const float *means,
+                                            const float *density, const float *scales, float scale_modifier, const float *rotations,
+                                            const float *t_means, const float *t_density, const float *t_scales,
+                                            const float *t_rotations, float *out /* [V,H,W] */, const long long *offsets,
+                                            const int *ids, long long ids_capacity, void *stream);
+R2_API int r2_project_gaussians_ray_jacobian_planned(int V, int H, int W, const float *rays /* [V,12] */, int cone, int P,
+                                                     const float *means, const float *density, const float *scales,
+                                                     float scale_modifier, const float *rotations, float *out /* [V,6,H,W] */,
+                                                     const long long *offsets, const int *ids, long long ids_capacity,
+                                                     void *stream);
+
 /* ---- exact adjoint of the forward projector, and TV descent (tigre.Atb and minimizeTV as the iterative reconstructions of
  * ct_utils.py:60-215 call them; r2_gaussian_amd/recon.py) ----------------------------------------------------------------
  * r2_backproject_volume: vol = A^T projs for the A of r2_project_volume with the same arguments.  For the ray rho of pixel

@@ -95,6 +95,19 @@ _SIGNATURES = {
     "r2_project_gaussians_variance": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
     "r2_project_gaussians_jvp": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
     "r2_project_gaussians_ray_jacobian": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
+    "r2_project_gaussians_plan_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "r2_project_gaussians_plan_count": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _p, _p, C.c_size_t, _p]),
+    "r2_project_gaussians_plan_fill": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _p, _p, C.c_longlong, _p,
+                                                 C.c_size_t, _p]),
+    "r2_project_gaussians_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, _p, C.c_longlong, _p]),
+    "r2_project_gaussians_rays_backward_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _p,
+                                                             C.c_size_t, _p, _p, C.c_longlong, _p]),
+    "r2_project_gaussians_variance_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                        _p, _p, C.c_longlong, _p]),
+    "r2_project_gaussians_jvp_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp,
+                                                   _p, _p, C.c_longlong, _p]),
+    "r2_project_gaussians_ray_jacobian_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, _p,
+                                                            C.c_longlong, _p]),
     "r2_tv_descent_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),

@@ -69,6 +69,9 @@ SOURCES = {
     "gaussian_variance.hip": EXACT,
     # EXACT for the same two reasons (tests/gaussian_tangent_ref.py, gaussian_tangent.hpp on gaussian_fisher.hpp / gaussian_ray_grad.hpp)
     "gaussian_tangent.hip": EXACT,
+    # EXACT for the projector's two reasons: a list holds a Gaussian exactly when the kernels above would stage it, so the
+    # radius and the rectangle must round as theirs do (tests/test_gaussian_plan_gpu.py compares bit for bit)
+    "gaussian_plan.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
 }

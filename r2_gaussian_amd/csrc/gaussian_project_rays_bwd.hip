@@ -17,8 +17,10 @@ namespace r2 {
 
 namespace {
 
-__global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, int W, const float *__restrict__ rays, int cone, Cloud cl,
-                                                                       const float *__restrict__ G, float *__restrict__ partial)
+// The first kernel's body, once: src says where the tile's Gaussians come from (WholeCloud, or the TileLists of a plan).
+template <typename Src>
+__device__ __forceinline__ void rays_bwd_tile(int H, int W, const float *__restrict__ rays, int cone, const Cloud &cl, const Src &src,
+                                              const float *__restrict__ G, float *__restrict__ partial)
 {
     static_assert(RG == TILE2D * TILE2D, "one thread per pixel of a tile");
     __shared__ ViewGeom vg;
@@ -28,7 +30,7 @@ __global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, in
     const float Gp = t.inside ? G[((size_t)t.view * H + t.r) * W + t.c] : 0.0f;
     float gs[3] = { 0.f, 0.f, 0.f }, gd[3] = { 0.f, 0.f, 0.f };
     tile_rounds(
-        cl, t, vg, cone, H, W, st, [&](Staged &d, const Gauss &a, int) { d.g = gauss_rec(a, cl.mod); },
+        src, cl, t, vg, cone, H, W, st, [&](Staged &d, const Gauss &a, int) { d.g = gauss_rec(a, cl.mod); },
         [&](const Staged &s) {
             GaussPair p;
             if (gauss_pair(s.g, t.y, cone, p)) gauss_pair_ray_grad(s.g, p, t.y, t.len, Gp, gs, gd);
@@ -42,6 +44,20 @@ __global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, in
 #pragma unroll
         for (int k = 0; k < 12; ++k) dst[k] = o[k];
     }
+}
+
+__global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_kernel(int H, int W, const float *__restrict__ rays, int cone, Cloud cl,
+                                                                       const float *__restrict__ G, float *__restrict__ partial)
+{
+    rays_bwd_tile(H, W, rays, cone, cl, WholeCloud{}, G, partial);
+}
+
+// A tile without entries runs no round and writes its zero partial.
+__global__ void __launch_bounds__(RG) gaussian_project_rays_bwd_planned_kernel(int H, int W, const float *__restrict__ rays, int cone,
+                                                                               Cloud cl, TileLists tl, const float *__restrict__ G,
+                                                                               float *__restrict__ partial)
+{
+    rays_bwd_tile(H, W, rays, cone, cl, tl, G, partial);
 }
 
 __global__ void __launch_bounds__(RG) gaussian_project_rays_reduce_kernel(int tiles, const float *__restrict__ partial,
@@ -63,6 +79,36 @@ __global__ void __launch_bounds__(RG) gaussian_project_rays_reduce_kernel(int ti
 
 size_t tiles_of(int H, int W) { return (size_t)((H + TILE2D - 1) / TILE2D) * (size_t)((W + TILE2D - 1) / TILE2D); }
 
+// Both entry points; tl: the lists of the planned one, or NULL.
+int rays_backward(const char *entry, const TileLists *tl, int V, int H, int W, const float *rays, int cone, const Cloud &cl,
+                  const float *dL_dout, float *dL_drays, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int P = cl.P;
+    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !dL_dout || !dL_drays || cl.missing() || (tl && lists_missing(P, *tl)))
+        return invalid_argument(entry);
+    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || (long long)H * W >= (1LL << 30) || P > CLOUD_MAX_P) {
+        set_error("%s: shape out of range (V %d, H %d, W %d, P %d)", entry, V, H, W, P);
+        return R2_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) {
+        R2_HIP_TRY(hipMemsetAsync(dL_drays, 0, (size_t)V * 12 * sizeof(float), s));
+        return 0;
+    }
+    const size_t need = r2_project_gaussians_rays_backward_workspace_bytes(V, H, W);
+    if (workspace_too_small(entry, "r2_project_gaussians_rays_backward_workspace_bytes", workspace, workspace_bytes, need))
+        return R2_ERR_INVALID;
+    const dim3 grid((W + TILE2D - 1) / TILE2D, (H + TILE2D - 1) / TILE2D, V);
+    float *partial = (float *)workspace;
+    if (tl)
+        gaussian_project_rays_bwd_planned_kernel<<<grid, dim3(RG), 0, s>>>(H, W, rays, cone, cl, *tl, dL_dout, partial);
+    else
+        gaussian_project_rays_bwd_kernel<<<grid, dim3(RG), 0, s>>>(H, W, rays, cone, cl, dL_dout, partial);
+    gaussian_project_rays_reduce_kernel<<<dim3(V), dim3(RG), 0, s>>>((int)tiles_of(H, W), partial, dL_drays);
+    R2_STAGE_CHECK(0, s, "project gaussians rays backward");
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace r2
@@ -78,26 +124,19 @@ extern "C" int r2_project_gaussians_rays_backward(int V, int H, int W, const flo
                                                   const float *rotations, const float *dL_dout, float *dL_drays, void *workspace,
                                                   size_t workspace_bytes, void *stream)
 {
-    using namespace r2;
-    const char *entry = "r2_project_gaussians_rays_backward";
-    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
-    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !dL_dout || !dL_drays || cl.missing()) return invalid_argument(entry);
-    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || (long long)H * W >= (1LL << 30) || P > CLOUD_MAX_P) {
-        set_error("r2_project_gaussians_rays_backward: shape out of range (V %d, H %d, W %d, P %d)", V, H, W, P);
-        return R2_ERR_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (P == 0) {
-        R2_HIP_TRY(hipMemsetAsync(dL_drays, 0, (size_t)V * 12 * sizeof(float), s));
-        return 0;
-    }
-    const size_t need = r2_project_gaussians_rays_backward_workspace_bytes(V, H, W);
-    if (workspace_too_small(entry, "r2_project_gaussians_rays_backward_workspace_bytes", workspace, workspace_bytes, need))
-        return R2_ERR_INVALID;
-    const dim3 grid((W + TILE2D - 1) / TILE2D, (H + TILE2D - 1) / TILE2D, V);
-    float *partial = (float *)workspace;
-    gaussian_project_rays_bwd_kernel<<<grid, dim3(RG), 0, s>>>(H, W, rays, cone, cl, dL_dout, partial);
-    gaussian_project_rays_reduce_kernel<<<dim3(V), dim3(RG), 0, s>>>((int)tiles_of(H, W), partial, dL_drays);
-    R2_STAGE_CHECK(0, s, "project gaussians rays backward");
-    return 0;
+    const r2::Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    return r2::rays_backward("r2_project_gaussians_rays_backward", nullptr, V, H, W, rays, cone, cl, dL_dout, dL_drays, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int r2_project_gaussians_rays_backward_planned(int V, int H, int W, const float *rays, int cone, int P, const float *means,
+                                                          const float *density, const float *scales, float scale_modifier,
+                                                          const float *rotations, const float *dL_dout, float *dL_drays,
+                                                          void *workspace, size_t workspace_bytes, const long long *offsets,
+                                                          const int *ids, long long ids_capacity, void *stream)
+{
+    const r2::Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    const r2::TileLists tl = { offsets, ids, ids_capacity };
+    return r2::rays_backward("r2_project_gaussians_rays_backward_planned", &tl, V, H, W, rays, cone, cl, dL_dout, dL_drays, workspace,
+                             workspace_bytes, stream);
 }

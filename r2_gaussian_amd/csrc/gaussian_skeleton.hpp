@@ -1,11 +1,13 @@
 // gaussian_skeleton.hpp -- the kernel skeletons of the exact operators on the Gaussian cloud, written once, on top of
 // gaussian_rays.hpp.  Every property those operators advertise -- a pair is differentiated exactly when the forward summed
-// it, a thread adds its pairs in ascending index, the same bits come out on every call -- lives in the four pieces below;
+// it, a thread adds its pairs in ascending index, the same bits come out on every call -- lives in the five pieces below;
 // the kernels hand them small callables (lambdas) for the lines in which they differ.
 //
 //   the loaded Gaussian   Cloud / CloudOut, Gauss, load_gauss, store_gauss: the only reads and writes of the parameter arrays;
 //   the gather round      gather_rounds: P Gaussians NT at a time, hit test, in-order compaction into an LDS batch, every
-//                         active thread walks the batch (the three pixel-tile kernels through pixel_tile and tile_rounds);
+//                         active thread walks the batch (the pixel-tile kernels through pixel_tile and tile_rounds);
+//   the list round        TileLists, list_rounds: the same batch and the same walk, fed from a tile's list of a projection
+//                         plan instead of the cloud (tile_rounds on TileLists): one staging per list entry, no test;
 //   the tile prologue     PixelTile, pixel_tile: the tile's bounds, the thread's pixel and its ray, the view's constants;
 //   the Gaussian wave     gauss_wave: one wave per Gaussian, eleven sums per lane, one butterfly, one store; with rect_walk
 //                         (the pixels of the Gaussian's rectangle) or hit_block_walk (the blocks whose box meets its sphere).
@@ -164,6 +166,74 @@ __device__ __forceinline__ void tile_rounds(const Cloud &cl, const PixelTile &t,
         });
 }
 
+// The per-tile lists of a projection plan (gaussian_plan.hip builds them; include/r2hip.h has the layout): list k = (view T +
+// ty Tx + tx) is ids[offsets[k] .. offsets[k + 1]), ascending Gaussian indices, and `capacity` is the number of ints `ids`
+// holds.  THE LISTS DRIVE THE KERNEL: a Gaussian that is not in a tile's list contributes nothing to that tile, whatever its
+// rectangle, so a caller may hand in lists of their own.
+struct TileLists {
+    const long long *offsets;
+    const int *ids;
+    long long capacity;
+};
+
+// Where the pixel-tile kernels take their Gaussians from: the whole cloud (gather_rounds) or the tile's list (list_rounds).
+struct WholeCloud {};
+
+// The list-driven round: entries [beg, end) of ids, NT at a time.  Thread i stages entry base + i into st[i] through
+// stage(st[i], id) -- no ballot and no compaction, every entry is a hit and the list's order is the batch's -- and every
+// thread with `active` set then calls consume(st[j]) for the batch in order.  Two barriers per round, which every thread of
+// the workgroup reaches.
+template <int NT, typename Rec, typename Stage, typename Consume>
+__device__ __forceinline__ void list_rounds(const int *__restrict__ ids, long long beg, long long end, Rec *st, bool active,
+                                            Stage stage, Consume consume)
+{
+    const int tid = threadIdx.x;
+    for (long long base = beg; base < end; base += NT) {
+        const int total = end - base < NT ? (int)(end - base) : NT;
+        if (tid < total) stage(st[tid], ids[base + tid]);
+        __syncthreads();
+        if (active)
+            for (int j = 0; j < total; ++j) consume(st[j]);
+        __syncthreads();   // the batch is rewritten by the next round
+    }
+}
+
+// tile_rounds on the whole cloud, and on the tile's list: an entry is staged as the gather round stages a hit -- its radius
+// and rectangle are computed again, by the same functions, and stage(st[i], a, id) fills the same record -- so a pixel adds
+// the pairs it adds without a plan, in the same order, and the same bits come out.  A list's ends are clamped to the
+// buffer's capacity; an entry that is no index of the cloud, or a Gaussian without radius or rectangle, is staged with an
+// empty rectangle that holds no pixel.
+template <typename Rec, typename Stage, typename Pair>
+__device__ __forceinline__ void tile_rounds(const WholeCloud &, const Cloud &cl, const PixelTile &t, const ViewGeom &vg, int cone,
+                                            int H, int W, Rec *st, Stage stage, Pair pair)
+{
+    tile_rounds(cl, t, vg, cone, H, W, st, stage, pair);
+}
+
+template <typename Rec, typename Stage, typename Pair>
+__device__ __forceinline__ void tile_rounds(const TileLists &tl, const Cloud &cl, const PixelTile &t, const ViewGeom &vg, int cone,
+                                            int H, int W, Rec *st, Stage stage, Pair pair)
+{
+    const size_t k = ((size_t)t.view * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const long long beg = min(max(tl.offsets[k], 0ll), tl.capacity), end = min(max(tl.offsets[k + 1], beg), tl.capacity);
+    list_rounds<TILE2D * TILE2D>(
+        tl.ids, beg, end, st, t.inside,
+        [&](Rec &d, int i) {
+            d.q = PixRect{ 1, 0, 1, 0 };
+            if (i < 0 || i >= cl.P) return;
+            const Gauss a = load_gauss(cl, i);
+            const float radius = gauss_radius(a, cl.mod);
+            PixRect rc;
+            if (!(radius >= 0.0f) || !gauss_rect(vg, cone, a.mx, a.my, a.mz, radius, H, W, rc)) return;
+            stage(d, a, i);
+            d.q = rc;
+        },
+        [&](const Rec &s) {
+            if (t.c < s.q.c0 || t.c > s.q.c1 || t.r < s.q.r0 || t.r > s.q.r1) return;
+            pair(s);
+        });
+}
+
 // The Gaussian-major wave: wave w of workgroup b owns Gaussian i = b NT / 64 + w.  It loads the Gaussian, and when the Gaussian
 // has a radius, walk(a, g, radius, lane, acc) adds the lane's pairs to its NPAR sums; one xor butterfly then adds the 64
 // partial sums in a fixed order and lane 0 writes row i of out.  A Gaussian without a radius, or one that the walk finds
@@ -236,6 +306,12 @@ inline int invalid_argument(const char *entry)
 {
     set_error("%s: invalid argument", entry);
     return R2_ERR_INVALID;
+}
+
+// The lists of a planned entry point: P = 0 needs none; a capacity of 0 needs no ids (every list is then empty).
+inline bool lists_missing(int P, const TileLists &tl)
+{
+    return tl.capacity < 0 || (P > 0 && (!tl.offsets || (tl.capacity > 0 && !tl.ids)));
 }
 
 constexpr int CLOUD_MAX_P = 1 << 29;

@@ -31,24 +31,70 @@ __global__ void __launch_bounds__(QB) gaussian_query_variance_kernel(int N, cons
 }
 
 // One workgroup per 16 x 16 pixel tile and view (blockIdx.z), one thread per pixel: the projector's rounds (tile_rounds).
-__global__ void __launch_bounds__(GB) gaussian_project_variance_kernel(int H, int W, const float *__restrict__ rays, int cone, Cloud cl,
-                                                                       const float *__restrict__ v_means,
-                                                                       const float *__restrict__ v_density,
-                                                                       const float *__restrict__ v_scales,
-                                                                       const float *__restrict__ v_rotations, float *__restrict__ out)
+// The body, once: src says where the tile's Gaussians come from (WholeCloud, or the TileLists of a plan).
+template <typename Src>
+__device__ __forceinline__ void variance_tile(int H, int W, const float *__restrict__ rays, int cone, const Cloud &cl, const Src &src,
+                                              const float *__restrict__ v_means, const float *__restrict__ v_density,
+                                              const float *__restrict__ v_scales, const float *__restrict__ v_rotations,
+                                              float *__restrict__ out)
 {
     __shared__ ViewGeom vg;
     __shared__ StagedPixVar st[GB];
     const PixelTile t = pixel_tile(rays, cone, H, W, vg);
     float acc = 0.0f;
     tile_rounds(
-        cl, t, vg, cone, H, W, st,
+        src, cl, t, vg, cone, H, W, st,
         [&](StagedPixVar &d, const Gauss &a, int i) { stage_var(d.a, a, cl.mod, v_means, v_density, v_scales, v_rotations, i); },
         [&](const StagedPixVar &s) {
             GaussPair p;
             if (gauss_pair(s.a.g, t.y, cone, p)) acc += staged_variance(s.a, p, t.y, t.len);
         });
     if (t.inside) out[((size_t)t.view * H + t.r) * W + t.c] = acc;
+}
+
+__global__ void __launch_bounds__(GB) gaussian_project_variance_kernel(int H, int W, const float *__restrict__ rays, int cone, Cloud cl,
+                                                                       const float *__restrict__ v_means,
+                                                                       const float *__restrict__ v_density,
+                                                                       const float *__restrict__ v_scales,
+                                                                       const float *__restrict__ v_rotations, float *__restrict__ out)
+{
+    variance_tile(H, W, rays, cone, cl, WholeCloud{}, v_means, v_density, v_scales, v_rotations, out);
+}
+
+__global__ void __launch_bounds__(GB) gaussian_project_variance_planned_kernel(int H, int W, const float *__restrict__ rays, int cone,
+                                                                               Cloud cl, TileLists tl,
+                                                                               const float *__restrict__ v_means,
+                                                                               const float *__restrict__ v_density,
+                                                                               const float *__restrict__ v_scales,
+                                                                               const float *__restrict__ v_rotations,
+                                                                               float *__restrict__ out)
+{
+    variance_tile(H, W, rays, cone, cl, tl, v_means, v_density, v_scales, v_rotations, out);
+}
+
+// Both entry points of the projection variance; tl: the lists of the planned one, or NULL.
+int project_variance(const char *entry, const TileLists *tl, int V, int H, int W, const float *rays, int cone, const Cloud &cl,
+                     const float *v_means, const float *v_density, const float *v_scales, const float *v_rotations, float *out,
+                     void *stream)
+{
+    const int P = cl.P;
+    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !out ||
+        (P > 0 && (cl.missing() || !v_means || !v_density || !v_scales || !v_rotations)) || (tl && lists_missing(P, *tl)))
+        return invalid_argument(entry);
+    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || P > CLOUD_MAX_P) {
+        set_error("%s: shape out of range (V %d, H %d, P %d)", entry, V, H, P);
+        return R2_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((W + TILE2D - 1) / TILE2D, (H + TILE2D - 1) / TILE2D, V);
+    if (tl && P > 0)   // P = 0 needs no lists: the unplanned kernel runs no round and writes the zeros
+        gaussian_project_variance_planned_kernel<<<grid, dim3(GB), 0, s>>>(H, W, rays, cone, cl, *tl, v_means, v_density, v_scales,
+                                                                           v_rotations, out);
+    else
+        gaussian_project_variance_kernel<<<grid, dim3(GB), 0, s>>>(H, W, rays, cone, cl, v_means, v_density, v_scales, v_rotations,
+                                                                   out);
+    R2_STAGE_CHECK(0, s, "project gaussians variance");
+    return 0;
 }
 
 }  // namespace
@@ -80,18 +126,19 @@ extern "C" int r2_project_gaussians_variance(int V, int H, int W, const float *r
                                              const float *rotations, const float *v_means, const float *v_density,
                                              const float *v_scales, const float *v_rotations, float *out, void *stream)
 {
-    using namespace r2;
-    const Cloud cl = { P, means, density, scales, scale_modifier, rotations };
-    if (V <= 0 || H <= 0 || W <= 0 || P < 0 || !rays || !out ||
-        (P > 0 && (cl.missing() || !v_means || !v_density || !v_scales || !v_rotations)))
-        return invalid_argument("r2_project_gaussians_variance");
-    if (V > 65535 || (H + TILE2D - 1) / TILE2D > 65535 || P > CLOUD_MAX_P) {
-        set_error("r2_project_gaussians_variance: shape out of range (V %d, H %d, P %d)", V, H, P);
-        return R2_ERR_INVALID;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((W + TILE2D - 1) / TILE2D, (H + TILE2D - 1) / TILE2D, V);
-    gaussian_project_variance_kernel<<<grid, dim3(GB), 0, s>>>(H, W, rays, cone, cl, v_means, v_density, v_scales, v_rotations, out);
-    R2_STAGE_CHECK(0, s, "project gaussians variance");
-    return 0;
+    const r2::Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    return r2::project_variance("r2_project_gaussians_variance", nullptr, V, H, W, rays, cone, cl, v_means, v_density, v_scales,
+                                v_rotations, out, stream);
+}
+
+extern "C" int r2_project_gaussians_variance_planned(int V, int H, int W, const float *rays, int cone, int P, const float *means,
+                                                     const float *density, const float *scales, float scale_modifier,
+                                                     const float *rotations, const float *v_means, const float *v_density,
+                                                     const float *v_scales, const float *v_rotations, float *out,
+                                                     const long long *offsets, const int *ids, long long ids_capacity, void *stream)
+{
+    const r2::Cloud cl = { P, means, density, scales, scale_modifier, rotations };
+    const r2::TileLists tl = { offsets, ids, ids_capacity };
+    return r2::project_variance("r2_project_gaussians_variance_planned", &tl, V, H, W, rays, cone, cl, v_means, v_density, v_scales,
+                                v_rotations, out, stream);
 }

@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from . import projector
 from ._C import _on_device, _stream
-from .gaussian_projector import check_projection_arguments, project_gaussians_rays, project_gaussians_rays_jvp, world_ray_params
+from .gaussian_projector import (check_projection_arguments, plan_projection_rays, project_gaussians_rays, project_gaussians_rays_jvp,
+                                 world_ray_params)
 from .uncertainty import CloudTuple, _check_group_tuple, _cloud, fisher_diagonal_rays
 
 _F32, _F64 = torch.float32, torch.float64
@@ -57,20 +58,23 @@ def _check_weights(weights, V, H, W, dev):
 
 
 @torch.no_grad()
-def normal_matvec(rays, cone, H, W, cloud, tangents, weights=None, damping=0.0, fisher=None, scale_modifier=1.0):
+def normal_matvec(rays, cone, H, W, cloud, tangents, weights=None, damping=0.0, fisher=None, scale_modifier=1.0, planned=False):
     """``J^T W J t + damping * F * t`` as a ``CloudTuple``: the normal-equations operator of the weighted least-squares fit of
     ``project_gaussians_rays`` on (``rays``, ``cone``, ``H``, ``W``, ``cloud``), applied to ``tangents`` (a 4-tuple shaped like
     the cloud).  One ``r2_project_gaussians_jvp`` launch and one ``r2_project_gaussians_backward`` launch; J is never formed.
     ``weights`` [V,H,W] (GPU, >= 0; None: 1).  ``fisher``: F, a 4-tuple (``uncertainty.fisher_diagonal_rays`` with the same
     weights); it is read only when ``damping`` is not 0, and computed when it is needed and not given.  float32; no host
-    synchronisation."""
+    synchronisation.  ``planned``: build a ``ProjectionPlan`` of (rays, cloud) and let the JVP walk its lists -- the same bits,
+    and ONE host read for the plan (``gaussian_projector.plan_projection_rays``); a single product does not repay the build,
+    the solvers below share one plan among a cloud's launches."""
     cloud = tuple(cloud)
     rays, H, W = check_projection_arguments(rays, H, W, *cloud)
     V, P, dev = rays.shape[0], cloud[0].shape[0], cloud[0].device
     weights = _check_weights(weights, V, H, W, dev)
     t = _check_group_tuple(tangents, P, dev, "tangents")
     rays = projector.device_rays(rays.detach(), dev)
-    jt = project_gaussians_rays_jvp(rays, cone, H, W, *cloud, tangents=t, scale_modifier=scale_modifier)
+    plan = plan_projection_rays(rays, cone, H, W, *cloud, scale_modifier=scale_modifier) if planned else None
+    jt = project_gaussians_rays_jvp(rays, cone, H, W, *cloud, tangents=t, scale_modifier=scale_modifier, plan=plan)
     if weights is not None:
         jt = jt * weights
     out = _backward(rays, cone, H, W, cloud, jt, scale_modifier)
@@ -99,9 +103,9 @@ def _log_factors(cloud, log_density, log_scaling):
                       s if log_scaling else torch.ones_like(s), torch.ones_like(r)], 1)
 
 
-def _loss(rays, cone, H, W, cloud, target, weights, scale_modifier):
+def _loss(rays, cone, H, W, cloud, target, weights, scale_modifier, plan=None):
     """-> (residual [V,H,W] float32, the mean weighted squared error: a float64 scalar on the device)."""
-    res = project_gaussians_rays(rays, cone, H, W, *cloud, scale_modifier=scale_modifier) - target
+    res = project_gaussians_rays(rays, cone, H, W, *cloud, scale_modifier=scale_modifier, plan=plan) - target
     sq = res.to(_F64) ** 2
     return res, (sq if weights is None else sq * weights.to(_F64)).mean()
 
@@ -127,12 +131,14 @@ def _linearise(rays, cone, H, W, cloud, res, weights, log_density, log_scaling, 
 
 
 @torch.no_grad()
-def _solve_and_move(rays, cone, H, W, cloud, lin, cg_iters, lam, weights, log_density, log_scaling, scale_modifier, max_log_step):
-    """``cg_iters`` CG iterations on (J^T W J + lam diag F) delta = b from delta = 0, and the cloud moved by delta."""
+def _solve_and_move(rays, cone, H, W, cloud, lin, cg_iters, lam, weights, log_density, log_scaling, scale_modifier, max_log_step,
+                    plan=None):
+    """``cg_iters`` CG iterations on (J^T W J + lam diag F) delta = b from delta = 0, and the cloud moved by delta; ``plan``:
+    the ``ProjectionPlan`` of (rays, cloud) every JVP walks, or None."""
     f, F, b = lin
 
     def matvec(t):
-        jt = project_gaussians_rays_jvp(rays, cone, H, W, *cloud, tangents=_split(t * f), scale_modifier=scale_modifier)
+        jt = project_gaussians_rays_jvp(rays, cone, H, W, *cloud, tangents=_split(t * f), scale_modifier=scale_modifier, plan=plan)
         if weights is not None:
             jt = jt * weights
         return _flat(_backward(rays, cone, H, W, cloud, jt, scale_modifier)) * f + lam * F * t
@@ -172,7 +178,7 @@ def _kernel_cloud(cloud):
 
 @torch.no_grad()
 def gauss_newton_step(rays, cone, H, W, cloud, projs, cg_iters, damping, weights=None, log_density=True, log_scaling=True,
-                      scale_modifier=1.0, max_log_step=MAX_LOG_STEP):
+                      scale_modifier=1.0, max_log_step=MAX_LOG_STEP, planned=False):
     """One damped Gauss-Newton step of the weighted least-squares fit of the cloud to ``projs`` [V,H,W] (GPU): solves
     ``(J^T W J + damping diag F) delta = -J^T W r``, r = image - projs, F = diag(J^T W J), by ``cg_iters`` iterations of
     conjugate gradients from delta = 0 -- a fixed count, so nothing waits for the device -- preconditioned by Jacobi,
@@ -183,6 +189,9 @@ def gauss_newton_step(rays, cone, H, W, cloud, projs, cg_iters, damping, weights
     renormalised (the projector uses it as it comes).
     Launches: one forward, one Fisher, one backward, then one JVP and one backward per CG iteration.  The CG vectors are
     float32, its scalars float64 on the device; an iteration whose curvature is not positive changes nothing.
+    ``planned``: one ``ProjectionPlan`` of (rays, cloud) is built first and serves the forward and every JVP of the CG, which
+    then walk per-tile lists instead of the whole cloud: the same bits, fewer tests, and ONE host read, of the plan's instance
+    count (``gaussian_projector.plan_projection_rays``).  The Fisher and the backward launches are Gaussian-major and unchanged.
     -> (the moved cloud: a ``CloudTuple`` of float32 tensors, the loss BEFORE the step: the mean weighted squared error, a
     float64 scalar on the device)."""
     cloud = tuple(cloud)
@@ -194,14 +203,15 @@ def gauss_newton_step(rays, cone, H, W, cloud, projs, cg_iters, damping, weights
     weights = _check_weights(weights, V, H, W, dev)
     rays = projector.device_rays(rays.detach(), dev)
     cloud = _kernel_cloud(cloud)
-    res, loss = _loss(rays, cone, H, W, cloud, projs.detach().to(_F32), weights, scale_modifier)
+    plan = plan_projection_rays(rays, cone, H, W, *cloud, scale_modifier=scale_modifier) if planned else None
+    res, loss = _loss(rays, cone, H, W, cloud, projs.detach().to(_F32), weights, scale_modifier, plan)
     lin = _linearise(rays, cone, H, W, cloud, res, weights, log_density, log_scaling, scale_modifier)
     return _solve_and_move(rays, cone, H, W, cloud, lin, cg_iters, float(damping), weights, log_density, log_scaling, scale_modifier,
-                           max_log_step), loss
+                           max_log_step, plan), loss
 
 
 def refine_cloud(views, projs, cloud, steps, cg_iters, damping=1e-3, cone=True, weights=None, log_density=True, log_scaling=True,
-                 scale_modifier=1.0, callback=None, max_log_step=MAX_LOG_STEP):
+                 scale_modifier=1.0, callback=None, max_log_step=MAX_LOG_STEP, planned=False):
     """Levenberg-Marquardt fit of the cloud to ``projs`` [V,H,W] (GPU) on the exact projector: ``steps`` steps of
     ``gauss_newton_step``'s solve with the accept / reject rule of ``geometry.refine_geometry_lm`` -- the candidate is taken
     when the mean weighted squared error falls, ``damping`` is divided by 10 then and multiplied by 10 otherwise (the cloud
@@ -210,6 +220,9 @@ def refine_cloud(views, projs, cloud, steps, cg_iters, damping=1e-3, cone=True, 
     Gaussians does not change.  Per step: the CG's launches and ONE forward, of the candidate, whose residual serves the
     next step when it is taken; the Fisher diagonal and the right-hand side are computed once per accepted cloud and kept
     across rejected steps.  One host read per step, of the comparison that decides it.
+    ``planned``: every cloud that is projected gets a ``ProjectionPlan`` -- the start, then each candidate -- which serves its
+    forward and, when the candidate is taken, every JVP of the next steps' CG until another candidate is; the same bits, and
+    one more host read per plan (``gaussian_projector.plan_projection_rays``), so two per step.
     -> (the refined cloud: a ``CloudTuple`` of float32 tensors, loss history: a float64 tensor [steps] on the device, the loss
     BEFORE each step).  ``callback(step, loss, cloud)``, when given, runs after every step."""
     if isinstance(views, (list, tuple)) and views and hasattr(views[0], "world_view_transform"):
@@ -232,17 +245,20 @@ def refine_cloud(views, projs, cloud, steps, cg_iters, damping=1e-3, cone=True, 
     cloud = _kernel_cloud(cloud)
     lam = float(damping)
     history = torch.zeros((int(steps),), dtype=_F64, device=projs.device)
-    res, loss = _loss(rays, cone, H, W, cloud, target, weights, scale_modifier)
+    make_plan = lambda c: plan_projection_rays(rays, cone, H, W, *c, scale_modifier=scale_modifier) if planned else None
+    plan = make_plan(cloud)
+    res, loss = _loss(rays, cone, H, W, cloud, target, weights, scale_modifier, plan)
     lin = None
     for it in range(int(steps)):
         history[it] = loss
         if lin is None:   # a new cloud: its Fisher diagonal and right-hand side
             lin = _linearise(rays, cone, H, W, cloud, res, weights, log_density, log_scaling, scale_modifier)
         cand = _solve_and_move(rays, cone, H, W, cloud, lin, cg_iters, lam, weights, log_density, log_scaling, scale_modifier,
-                               max_log_step)
-        res_c, loss_c = _loss(rays, cone, H, W, cand, target, weights, scale_modifier)
+                               max_log_step, plan)
+        plan_c = make_plan(cand)
+        res_c, loss_c = _loss(rays, cone, H, W, cand, target, weights, scale_modifier, plan_c)
         if bool(loss_c < loss):   # the one host read of the step
-            cloud, res, loss, lin, lam = cand, res_c, loss_c, None, lam / 10.0
+            cloud, res, loss, lin, lam, plan = cand, res_c, loss_c, None, lam / 10.0, plan_c
         else:
             lam = lam * 10.0
         if callback is not None:

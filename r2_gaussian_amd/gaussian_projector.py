@@ -16,6 +16,9 @@ kernels of csrc/gaussian_bundle.hip and csrc/gaussian_bundle_bwd.hip (``r2_integ
 ``project_gaussians_jvp`` / ``project_gaussians_rays_jvp`` apply the projector's Jacobian forwards, to a tangent of the cloud,
 of the rays, or both, on the kernels of csrc/gaussian_tangent.hip (``r2_project_gaussians_jvp``,
 ``r2_project_gaussians_ray_jacobian``); gauss_newton.py and ``geometry.refine_geometry_lm`` build their solvers on them.
+
+``plan_projection`` / ``plan_projection_rays`` build a ``ProjectionPlan``, the per-tile Gaussian lists of one (rays, cloud), on
+the kernels of csrc/gaussian_plan.hip; the pixel-major operators take it as ``plan=`` and write the same bits sooner.
 """
 import torch
 
@@ -36,18 +39,152 @@ def _f32c(t):
     return t if t.dtype == _F32 and t.is_contiguous() else t.to(_F32).contiguous()
 
 
+_PLAN_SOURCES = ("rays", "xyz", "density", "scaling", "rotation")
+
+
+class ProjectionPlan:
+    """The per-tile Gaussian lists of one (rays, detector, cloud): what ``plan_projection_rays`` returns and the ``plan=``
+    keyword of the pixel-major operators takes (include/r2hip.h, "projection plans", has the layout).
+
+    ``offsets`` int64 [V T + 1] and ``ids`` int32 [instances], both on the GPU (``lists()`` returns the two); ``instances``,
+    ``V``, ``H``, ``W``, ``cone``, ``P``, ``scale_modifier`` as it was built.  The plan keeps references to the rays tensor
+    and the four cloud tensors it was built from and records their shapes and ``_version`` counters: a consumer that is handed
+    other tensors, tensors that were written in place since, or another detector, beam or scale modifier raises ValueError
+    (``check``) instead of projecting with stale lists."""
+
+    def __init__(self, offsets, ids, instances, V, H, W, cone, P, scale_modifier, sources):
+        self.offsets, self.ids, self.instances = offsets, ids, int(instances)
+        self.V, self.H, self.W, self.cone, self.P, self.scale_modifier = V, H, W, bool(cone), P, float(scale_modifier)
+        self._sources = tuple((t, tuple(t.shape), t._version) for t in sources)
+        self._view_params = None   # plan_projection: the [V,12] host parameters of the views it was built from
+
+    def lists(self):
+        """-> (offsets, ids)."""
+        return self.offsets, self.ids
+
+    def check(self, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier):
+        """ValueError, naming what changed, unless the arguments are the ones the plan was built from."""
+        changed = [n for n, a, b in (("H", int(H), self.H), ("W", int(W), self.W), ("cone", bool(cone), self.cone),
+                                     ("scale_modifier", float(scale_modifier), self.scale_modifier)) if a != b]
+        for name, t, (src, shape, version) in zip(_PLAN_SOURCES, (rays, xyz, density, scaling, rotation), self._sources):
+            if t is not src:
+                changed.append("%s (another tensor)" % name)
+            elif tuple(t.shape) != shape:
+                changed.append("%s (shape %s, planned with %s)" % (name, tuple(t.shape), shape))
+            elif t._version != version:
+                changed.append("%s (written in place since)" % name)
+        if changed:
+            raise ValueError("the projection plan is stale or belongs to other arguments: %s changed; build a new plan"
+                             % ", ".join(changed))
+
+    def _args(self):
+        return self.offsets.data_ptr(), self.ids.data_ptr(), self.ids.numel()
+
+
+def _plan_count(rays, cone, H, W, x, d, s, r, scale_modifier):
+    """``r2_project_gaussians_plan_count`` on kernel-ready tensors -> (offsets, the workspace that holds the table)."""
+    V, P, dev = rays.shape[0], x.shape[0], x.device
+    L = _lib.lib()
+    T = ((H + 15) // 16) * ((W + 15) // 16)
+    offsets = torch.empty((V * T + 1,), dtype=torch.int64, device=dev)
+    ws = torch.empty((max(int(L.r2_project_gaussians_plan_workspace_bytes(V, H, W, P)), 1),), dtype=torch.uint8, device=dev)
+    with _on_device(dev):
+        rc = L.r2_project_gaussians_plan_count(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                               float(scale_modifier), r.data_ptr(), offsets.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               _stream(dev))
+    _lib.check(rc, "r2_project_gaussians_plan_count")
+    return offsets, ws
+
+
+def _plan_fill(rays, cone, H, W, x, d, s, r, scale_modifier, offsets, ws, instances):
+    """``r2_project_gaussians_plan_fill`` after ``_plan_count`` -> ids [instances]."""
+    V, P, dev = rays.shape[0], x.shape[0], x.device
+    ids = torch.empty((instances,), dtype=torch.int32, device=dev)
+    with _on_device(dev):
+        rc = _lib.lib().r2_project_gaussians_plan_fill(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                                       float(scale_modifier), r.data_ptr(), offsets.data_ptr(),
+                                                       ids.data_ptr() if instances else None, instances, ws.data_ptr(), ws.numel(),
+                                                       _stream(dev))
+    _lib.check(rc, "r2_project_gaussians_plan_fill")
+    return ids
+
+
+@torch.no_grad()
+def plan_projection_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0):
+    """The ``ProjectionPlan`` of ``project_gaussians_rays`` on the same arguments: for every 16 x 16 tile of every view the
+    ascending list of the Gaussians whose detector rectangle meets it.  Hand it to the pixel-major operators (``plan=``):
+    ``project_gaussians_rays`` (the forward and its ray backward), ``project_gaussians_rays_jvp``, ``geometry.ray_jacobian``,
+    ``uncertainty.projection_variance_rays``; they then walk a tile's list where they otherwise test all P Gaussians per tile,
+    and write the same bits.  Worth it when the same cloud is projected on the same rays more than once
+    (``gauss_newton.gauss_newton_step(planned=True)``); DESIGN.md section 4, "Projection plans", has the break-even.
+
+    Building costs two groups of launches and ONE host read between them, of the instance count that sizes ``ids``: unlike
+    the operators themselves, this function synchronises with the device.  ``rays`` should be a tensor (the plan records its
+    identity; an array is converted anew on every call and can never match).  Deterministic: building twice gives equal
+    tensors, and a view's lists do not depend on the other views."""
+    rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
+    rdev = projector.device_rays(rays.detach(), dev)
+    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    c = int(bool(cone))
+    offsets, ws = _plan_count(rdev, c, H, W, x, d, s, r, scale_modifier)
+    instances = int(offsets[-1])   # the one host read
+    ids = _plan_fill(rdev, c, H, W, x, d, s, r, scale_modifier, offsets, ws, instances)
+    return ProjectionPlan(offsets, ids, instances, V, H, W, cone, P, scale_modifier, (rays, xyz, density, scaling, rotation))
+
+
+def plan_projection(views, xyz, density, scaling, rotation, scale_modifier=1.0):
+    """``plan_projection_rays`` on ``views`` (``scene.View`` list: one detector size, one beam mode), for the operators that
+    take views.  Those check that the views they are given have the ray parameters the plan was built from."""
+    views, H, W = projector.check_views(views)
+    params = world_ray_params(views)
+    plan = plan_projection_rays(torch.from_numpy(params), views[0].mode == 1, H, W, xyz, density, scaling, rotation, scale_modifier)
+    plan._view_params = params.copy()
+    return plan
+
+
+def _view_rays(views, plan):
+    """The rays tensor of ``views``: a new one without a plan, else the plan's own, after the views were compared with it."""
+    params = world_ray_params(views)
+    if plan is None:
+        return torch.from_numpy(params)
+    if not isinstance(plan, ProjectionPlan):
+        raise ValueError("plan must be a ProjectionPlan, got %r" % type(plan).__name__)
+    if plan._view_params is None:
+        raise ValueError("the projection plan was built from rays (plan_projection_rays): use the operator that takes rays")
+    if plan._view_params.shape != params.shape or not (plan._view_params == params).all():
+        raise ValueError("the projection plan is stale or belongs to other arguments: views changed; build a new plan")
+    return plan._sources[0][0]
+
+
+def _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier):
+    """None, or ``plan`` after its staleness check against the caller's own tensors."""
+    if plan is None:
+        return None
+    if not isinstance(plan, ProjectionPlan):
+        raise ValueError("plan must be a ProjectionPlan, got %r" % type(plan).__name__)
+    plan.check(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
+    return plan
+
+
 class _ProjectGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz, density, scaling, rotation, rays, cone, H, W, scale_modifier, out):
+    def forward(ctx, xyz, density, scaling, rotation, rays, cone, H, W, scale_modifier, out, plan=None):
         V, P = rays.shape[0], xyz.shape[0]
         x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
         rays = rays.detach()
         with _on_device(x.device):
-            rc = _lib.lib().r2_project_gaussians(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                 float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(x.device))
-        _lib.check(rc, "r2_project_gaussians")
+            if plan is None:
+                rc = _lib.lib().r2_project_gaussians(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
+                                                     float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(x.device))
+            else:
+                rc = _lib.lib().r2_project_gaussians_planned(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
+                                                             s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(),
+                                                             *plan._args(), _stream(x.device))
+        _lib.check(rc, "r2_project_gaussians" if plan is None else "r2_project_gaussians_planned")
         ctx.save_for_backward(x, d, s, r, rays)
         ctx.args = (cone, H, W, float(scale_modifier))
+        ctx.plan = plan
         ctx.mark_dirty(out)
         return out
 
@@ -71,11 +208,17 @@ class _ProjectGaussians(torch.autograd.Function):
             ws = torch.empty((max(int(L.r2_project_gaussians_rays_backward_workspace_bytes(V, H, W)), 1),), dtype=torch.uint8,
                              device=x.device)
             with _on_device(x.device):
-                rc = L.r2_project_gaussians_rays_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
-                                                          s.data_ptr(), mod, r.data_ptr(), G.data_ptr(), grays.data_ptr(),
-                                                          ws.data_ptr(), ws.numel(), _stream(x.device))
-            _lib.check(rc, "r2_project_gaussians_rays_backward")
-        return gx, gd, gs, gr, grays, None, None, None, None, None
+                if ctx.plan is None:
+                    rc = L.r2_project_gaussians_rays_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
+                                                              s.data_ptr(), mod, r.data_ptr(), G.data_ptr(), grays.data_ptr(),
+                                                              ws.data_ptr(), ws.numel(), _stream(x.device))
+                else:
+                    rc = L.r2_project_gaussians_rays_backward_planned(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
+                                                                      s.data_ptr(), mod, r.data_ptr(), G.data_ptr(),
+                                                                      grays.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                      *ctx.plan._args(), _stream(x.device))
+            _lib.check(rc, "r2_project_gaussians_rays_backward" if ctx.plan is None else "r2_project_gaussians_rays_backward_planned")
+        return gx, gd, gs, gr, grays, None, None, None, None, None, None
 
 
 def check_projection_arguments(rays, H, W, xyz, density, scaling, rotation):
@@ -103,15 +246,19 @@ def check_projection_arguments(rays, H, W, xyz, density, scaling, rotation):
     return rays, H, W
 
 
-def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
+def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, out=None, plan=None):
     """Exact projections [V,H,W] (GPU, float32) of the cloud ``xyz`` [P,3], ``density`` [P,1] or [P], ``scaling`` [P,3],
     ``rotation`` [P,4] (activated values; the quaternion is used as it comes) along caller-supplied rays: ``rays`` [V,12]
     {a, p00, pu, pv} in world coordinates (include/r2hip.h), ``cone`` the beam (True: from the source a through the pixel
     points; False: through the pixel points along a).  Differentiable in the four parameter tensors, and in ``rays`` when they
     require grad (``r2_project_gaussians_rays_backward``, launched only then): a ``rays`` tensor on the device or on the host,
     of any float dtype, receives its gradient where and as it is.  No host synchronisation (host rays that require grad are
-    copied synchronously); ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W]."""
+    copied synchronously); ``out`` may be a preallocated contiguous float32 GPU tensor [V,H,W].
+    ``plan``: a ``ProjectionPlan`` built from these very tensors (``plan_projection_rays``); the forward and the ray backward
+    then walk the plan's lists (``r2_project_gaussians_planned``, ``r2_project_gaussians_rays_backward_planned``), the
+    parameter backward is unchanged, and every result is the same bits.  A stale plan raises ValueError."""
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V = rays.shape[0]
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != _F32 or not out.is_cuda or not out.is_contiguous()
                             or tuple(out.shape) != (V, H, W) or out.device != xyz.device):
@@ -122,29 +269,36 @@ def project_gaussians_rays(rays, cone, H, W, xyz, density, scaling, rotation, sc
         rays = projector.device_rays(rays, xyz.device)
     if out is None:
         out = torch.empty((V, H, W), dtype=_F32, device=xyz.device)
-    return _ProjectGaussians.apply(xyz, density, scaling, rotation, rays, int(bool(cone)), H, W, float(scale_modifier), out)
+    return _ProjectGaussians.apply(xyz, density, scaling, rotation, rays, int(bool(cone)), H, W, float(scale_modifier), out, plan)
 
 
-def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0, out=None):
+def project_gaussians(views, xyz, density, scaling, rotation, scale_modifier=1.0, out=None, plan=None):
     """Exact projections [V,H,W] of the cloud on ``views`` (``scene.View`` list: one detector size, one beam mode), registered
-    to the rasterizer's image of the same view.  See ``project_gaussians_rays``."""
+    to the rasterizer's image of the same view.  See ``project_gaussians_rays``; ``plan``: from ``plan_projection``."""
     views, H, W = projector.check_views(views)
-    return project_gaussians_rays(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
-                                  rotation, scale_modifier, out)
+    return project_gaussians_rays(_view_rays(views, plan), views[0].mode == 1, H, W, xyz, density, scaling, rotation,
+                                  scale_modifier, out, plan)
 
 
-def _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0):
-    """``geometry.ray_jacobian``, where its documentation is: [V,6,H,W] on ``r2_project_gaussians_ray_jacobian``."""
+def _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, plan=None):
+    """``geometry.ray_jacobian``, where its documentation is: [V,6,H,W] on ``r2_project_gaussians_ray_jacobian``, or, with a
+    plan, on ``r2_project_gaussians_ray_jacobian_planned``."""
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
     rays = projector.device_rays(rays.detach(), dev)
     x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
     out = torch.empty((V, 6, H, W), dtype=_F32, device=dev)
+    L = _lib.lib()
     with _on_device(dev):
-        rc = _lib.lib().r2_project_gaussians_ray_jacobian(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                          s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(),
-                                                          _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_ray_jacobian")
+        if plan is None:
+            rc = L.r2_project_gaussians_ray_jacobian(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
+                                                     s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(dev))
+        else:
+            rc = L.r2_project_gaussians_ray_jacobian_planned(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(),
+                                                             d.data_ptr(), s.data_ptr(), float(scale_modifier), r.data_ptr(),
+                                                             out.data_ptr(), *plan._args(), _stream(dev))
+    _lib.check(rc, "r2_project_gaussians_ray_jacobian" if plan is None else "r2_project_gaussians_ray_jacobian_planned")
     return out
 
 
@@ -165,7 +319,7 @@ def contract_ray_jacobian(jac, ray_tangent, cone):
 
 @torch.no_grad()
 def project_gaussians_rays_jvp(rays, cone, H, W, xyz, density, scaling, rotation, tangents=None, ray_tangent=None,
-                               scale_modifier=1.0):
+                               scale_modifier=1.0, plan=None):
     """The directional derivative [V,H,W] (GPU, float32) of ``project_gaussians_rays`` on the same arguments: J t for a tangent
     of the cloud, of the rays, or of both (their sum).  ``tangents``: a 4-tuple shaped like the cloud (xyz [P,3], density
     [P,1] or [P], scaling [P,3], rotation [P,4]), in the parameters of the projector's gradient (the scales as given, the
@@ -173,10 +327,13 @@ def project_gaussians_rays_jvp(rays, cone, H, W, xyz, density, scaling, rotation
     ``ray_tangent`` [V,12]: one launch of ``r2_project_gaussians_ray_jacobian`` (``geometry.ray_jacobian``), contracted in
     torch with every pixel's (ds, dd) (``contract_ray_jacobian``).  At least one of the two must be given.  Which pairs are
     summed is piecewise constant and not differentiated, as in the backward, whose transpose this is:
-    <G, J t> = <J^T G, t> up to rounding.  The result is not attached to autograd.  No host synchronisation."""
+    <G, J t> = <J^T G, t> up to rounding.  The result is not attached to autograd.  No host synchronisation.
+    ``plan``: a ``ProjectionPlan`` built from these very tensors; both launches then walk its lists
+    (``r2_project_gaussians_jvp_planned``, ``r2_project_gaussians_ray_jacobian_planned``) and give the same bits."""
     if tangents is None and ray_tangent is None:
         raise ValueError("give tangents, ray_tangent or both")
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
     out = None
     if tangents is not None:
@@ -185,26 +342,30 @@ def project_gaussians_rays_jvp(rays, cone, H, W, xyz, density, scaling, rotation
         rdev = projector.device_rays(rays.detach(), dev)
         x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
         out = torch.empty((V, H, W), dtype=_F32, device=dev)
+        args = (V, H, W, rdev.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(), s.data_ptr(), float(scale_modifier),
+                r.data_ptr(), tx.data_ptr(), td.data_ptr(), ts.data_ptr(), tr.data_ptr(), out.data_ptr())
         with _on_device(dev):
-            rc = _lib.lib().r2_project_gaussians_jvp(V, H, W, rdev.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                     s.data_ptr(), float(scale_modifier), r.data_ptr(), tx.data_ptr(), td.data_ptr(),
-                                                     ts.data_ptr(), tr.data_ptr(), out.data_ptr(), _stream(dev))
-        _lib.check(rc, "r2_project_gaussians_jvp")
+            if plan is None:
+                rc = _lib.lib().r2_project_gaussians_jvp(*args, _stream(dev))
+            else:
+                rc = _lib.lib().r2_project_gaussians_jvp_planned(*args, *plan._args(), _stream(dev))
+        _lib.check(rc, "r2_project_gaussians_jvp" if plan is None else "r2_project_gaussians_jvp_planned")
     if ray_tangent is not None:
         ray_tangent = torch.as_tensor(ray_tangent)
         if tuple(ray_tangent.shape) != (V, 12):
             raise ValueError("ray_tangent must be [%d,12], got %s" % (V, tuple(ray_tangent.shape)))
-        jac = _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
+        jac = _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier, plan)
         part = contract_ray_jacobian(jac, ray_tangent.detach(), bool(cone)).to(_F32)
         out = part if out is None else out + part
     return out
 
 
-def project_gaussians_jvp(views, xyz, density, scaling, rotation, tangents=None, ray_tangent=None, scale_modifier=1.0):
-    """``project_gaussians_rays_jvp`` on ``views`` (``scene.View`` list: one detector size, one beam mode)."""
+def project_gaussians_jvp(views, xyz, density, scaling, rotation, tangents=None, ray_tangent=None, scale_modifier=1.0, plan=None):
+    """``project_gaussians_rays_jvp`` on ``views`` (``scene.View`` list: one detector size, one beam mode); ``plan``: from
+    ``plan_projection``."""
     views, H, W = projector.check_views(views)
-    return project_gaussians_rays_jvp(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
-                                      rotation, tangents, ray_tangent, scale_modifier)
+    return project_gaussians_rays_jvp(_view_rays(views, plan), views[0].mode == 1, H, W, xyz, density, scaling, rotation, tangents,
+                                      ray_tangent, scale_modifier, plan)
 
 
 _BLOCKS = ("r2_integrate_gaussians", "r2_integrate_gaussians_backward", "r2_integrate_gaussians_workspace_bytes")

@@ -253,14 +253,16 @@ def refine_geometry(projs, cloud, rays_fn, params, iters, lr, loss="l2", cone=Tr
     return {k: v.detach() for k, v in p.items()}, history
 
 
-def ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0):
+def ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier=1.0, plan=None):
     """Every pixel's derivative in its own ray, [V,6,H,W] (GPU, float32): planes 0..2 hold d pixel / d s, planes 3..5
     d pixel / d d, for the start s and the direction d ``pixel_rays`` gives the pixel, of ``project_gaussians_rays`` on the
     same arguments (``r2_project_gaussians_ray_jacobian``: one launch, pixel-major, no workspace, no host synchronisation).
     Six numbers per pixel are the whole ray Jacobian: any number of geometry parameters chains through them in torch
-    (``gaussian_projector.contract_ray_jacobian``), which is what ``refine_geometry_lm`` does.  Not differentiable."""
+    (``gaussian_projector.contract_ray_jacobian``), which is what ``refine_geometry_lm`` does.  Not differentiable.
+    ``plan``: a ``gaussian_projector.ProjectionPlan`` built from these very tensors; the launch then walks its lists and gives
+    the same bits.  (``refine_geometry`` and ``refine_geometry_lm`` move the rays every iteration and take no plan.)"""
     from .gaussian_projector import _ray_jacobian
-    return _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
+    return _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier, plan)
 
 
 def refine_geometry_lm(projs, cloud, rays_fn, params, iters, damping=1e-3, cone=True, weights=None, callback=None):

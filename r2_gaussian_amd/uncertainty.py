@@ -139,28 +139,37 @@ def field_variance(points, xyz, density, scaling, rotation, variance, scale_modi
 
 
 @torch.no_grad()
-def projection_variance_rays(rays, cone, H, W, xyz, density, scaling, rotation, variance, scale_modifier=1.0):
+def projection_variance_rays(rays, cone, H, W, xyz, density, scaling, rotation, variance, scale_modifier=1.0, plan=None):
     """The predictive variance [V,H,W] (GPU, float32) of every pixel of ``project_gaussians_rays`` on the same arguments, under
-    independent parameter variances ``variance``.  Not differentiable.  No host synchronisation."""
+    independent parameter variances ``variance``.  Not differentiable.  No host synchronisation.  ``plan``: a
+    ``gaussian_projector.ProjectionPlan`` built from these very tensors; the launch then walks its lists
+    (``r2_project_gaussians_variance_planned``) and gives the same bits."""
+    from .gaussian_projector import _checked_plan
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
+    plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
     vx, vd, vs, vr = _check_group_tuple(variance, P, dev, "variance")
     rays = projector.device_rays(rays.detach(), dev)
     x, d, s, r = _cloud(xyz, density, scaling, rotation)
     out = torch.empty((V, H, W), dtype=_F32, device=dev)
+    args = (V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(), s.data_ptr(), float(scale_modifier),
+            r.data_ptr(), vx.data_ptr(), vd.data_ptr(), vs.data_ptr(), vr.data_ptr(), out.data_ptr())
     with _on_device(dev):
-        rc = _lib.lib().r2_project_gaussians_variance(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                      s.data_ptr(), float(scale_modifier), r.data_ptr(), vx.data_ptr(),
-                                                      vd.data_ptr(), vs.data_ptr(), vr.data_ptr(), out.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_variance")
+        if plan is None:
+            rc = _lib.lib().r2_project_gaussians_variance(*args, _stream(dev))
+        else:
+            rc = _lib.lib().r2_project_gaussians_variance_planned(*args, *plan._args(), _stream(dev))
+    _lib.check(rc, "r2_project_gaussians_variance" if plan is None else "r2_project_gaussians_variance_planned")
     return out
 
 
-def projection_variance(views, xyz, density, scaling, rotation, variance, scale_modifier=1.0):
-    """``projection_variance_rays`` on ``views`` (``scene.View`` list) -> [V,H,W]."""
+def projection_variance(views, xyz, density, scaling, rotation, variance, scale_modifier=1.0, plan=None):
+    """``projection_variance_rays`` on ``views`` (``scene.View`` list) -> [V,H,W]; ``plan``: from
+    ``gaussian_projector.plan_projection``."""
+    from .gaussian_projector import _view_rays
     views, H, W = projector.check_views(views)
-    return projection_variance_rays(torch.from_numpy(world_ray_params(views)), views[0].mode == 1, H, W, xyz, density, scaling,
-                                    rotation, variance, scale_modifier)
+    return projection_variance_rays(_view_rays(views, plan), views[0].mode == 1, H, W, xyz, density, scaling, rotation, variance,
+                                    scale_modifier, plan)
 
 
 def view_information(views, xyz, density, scaling, rotation, variance, weights=None, scale_modifier=1.0):
