@@ -572,13 +572,23 @@ __global__ void __launch_bounds__(EMIT_THREADS) raster_emit_hist_kernel(
 //   2. turn the moments into dL/dmean2D, dL/dconic, dL/dopacity, dL/dmu (the 7 sums of the reference);
 //   3. computeCov2DCUDA (RAS/backward.cu:145-330) + preprocessCUDA backward (RAS/backward.cu:402-444).
 // Outputs are ASSIGNED; the caller's zero-initialisation covers the rows of culled Gaussians.
-constexpr int GB_ROWS = 256;   // moment rows a wave streams per pass (4 per lane)
-// (Measured and left out, round 5: __launch_bounds__(256, 4) makes hipcc allocate 94 instead of 98 VGPRs, i.e. five waves per SIMD by
-// registers -- the grid of 1172 workgroups is 1.14 rounds of the 1024 slots that four allow, and the stamps show the second round
-// starting 12 us after the first.  26.2 us against 25.2: the LDS (32 KB per workgroup) still stops at four per CU, and with 192 or 128
-// rows per pass -- 24 / 16 KB, six or more per CU -- the kernel takes 27.7 us: the row passes get shorter, the round trips do not.)
+constexpr int GB_ROWS = 320;   // moment rows a wave streams per pass (5 per lane)
+// Residency and pass length, 300k Gaussians on 512^2 (1172 workgroups; a wave owns 247 +- 12 rows, at most 298):
+//   - round 5, rows parked as 32 bytes: __launch_bounds__(256, 4) gave 94 VGPRs but the LDS (32 KB per workgroup) still stopped at
+//     four workgroups per CU, 1.14 rounds of 1024 slots, the second starting 12 us after the first: 26.2 us against 25.2.  192 or
+//     128 rows per pass (24 / 16 KB, six or more per CU) took 27.7 us: those passes were SHORTER, every wave paid a second gather
+//     round trip for them.
+//   - rows parked as 24 bytes, 256 rows per pass (24 KB), bounded to five waves per SIMD: all 1172 workgroups start within
+//     0.8 us of each other (stamp 6), and the kernel takes 23.4 us against 23.5 -- one resident round alone buys nothing, the
+//     last workgroup still ends 20.4 us after the first starts.  At 256 rows a fifth of the waves, in 59 % of the workgroups,
+//     go round a second time for their last few rows.
+//   - the same with 320 rows per pass (30 KB, five per CU are 150 of the 160 KB): no wave of this scene needs a second pass,
+//     21.9 us against 23.6 (profiles/r07a_summary.md).  384 rows would be 36 KB, four per CU, and 98 VGPRs.
+// hipcc -Rpass-analysis=kernel-resource-usage, gfx950: <false> 94 VGPRs (98 without the bound), no spills, no scratch, 5 waves per
+// SIMD, 30720 B of LDS; <true> 148 VGPRs (140 with 32-byte rows), 3 waves per SIMD as before, 4 SGPRs spilled to lanes as before,
+// no scratch.  Bounding <true> to five spills 38 registers: it keeps its three.
 template <bool MV>
-__global__ void __launch_bounds__(256) raster_geom_backward_kernel(
+__global__ void __launch_bounds__(256, MV ? 3 : 5) raster_geom_backward_kernel(
     int P, int Vn, const float *__restrict__ means3D, const int *__restrict__ radii, const float *__restrict__ cov3Ds,
     int cov_per_view, const float *__restrict__ scales, const float *__restrict__ rotations, float scale_modifier,
     float h_x, float h_y, float tan_fovx, float tan_fovy, const float *__restrict__ views,
@@ -598,8 +608,12 @@ __global__ void __launch_bounds__(256) raster_geom_backward_kernel(
     const bool in_range = idx_raw < P;
     const int idx = in_range ? idx_raw : P - 1;
     const int lane = threadIdx.x & 63;
-    __shared__ float4 s_rows[256 / 64][GB_ROWS * 2];   // per wave: one pass of moment rows (32 bytes each)
-    float4 *const wrows = s_rows[threadIdx.x >> 6];
+    // per wave: one pass of moment rows, parked as 24 bytes each (S0..S3 | S4, S5; the two pad floats of the 32-byte global row
+    // are never read) in two planes: 7.5 KB per wave, 30 KB per workgroup
+    __shared__ float4 s_rows_a[256 / 64][GB_ROWS];
+    __shared__ float2 s_rows_b[256 / 64][GB_ROWS];
+    float4 *const wrows_a = s_rows_a[threadIdx.x >> 6];
+    float2 *const wrows_b = s_rows_b[threadIdx.x >> 6];
     R2_TS_AT(geom, 6);
     const int V = MV ? Vn : 1;   // single view: a compile-time trip count (the loop folds away)
     const float3 mean = make_float3(means3D[3 * idx], means3D[3 * idx + 1], means3D[3 * idx + 2]);
@@ -635,10 +649,10 @@ __global__ void __launch_bounds__(256) raster_geom_backward_kernel(
     // This Gaussian's rows are contiguous (the render backward stores each instance's row at its EMISSION index), but a lane
     // that walks its own run makes its wave wait one gather round trip per step of its WIDEST Gaussian: stamped inside the
     // kernel, that loop was 11 of the 16 us a workgroup lives.  So the wave streams the rows of its 64 Gaussians together:
-    // the concatenated runs are dealt out 64 * 4 rows at a time, one row per lane and load (owner = last lane whose exclusive
+    // the concatenated runs are dealt out GB_ROWS rows at a time, one row per lane and load (owner = last lane whose exclusive
     // offset is <= k, found like in the duplicate kernel), parked in LDS, and every lane then adds ITS rows from LDS in row
     // order -- the same sums in the same order as before (bit-reproducible, bit-identical to the per-lane walk), one gather
-    // round trip per 256 rows instead of one per 4 rows of the widest lane.
+    // round trip per GB_ROWS rows instead of one per 4 rows of the widest lane.
     {
         uint32_t incl = ninst;
 #pragma unroll
@@ -649,7 +663,8 @@ __global__ void __launch_bounds__(256) raster_geom_backward_kernel(
         const uint32_t excl = incl - ninst;
         const uint32_t total = __shfl(incl, 63);
         for (uint32_t base = 0; base < total; base += GB_ROWS) {   // wave-uniform
-            float4 m0[GB_ROWS / 64], m1[GB_ROWS / 64];
+            float4 m0[GB_ROWS / 64];
+            float2 m1[GB_ROWS / 64];
 #pragma unroll
             for (int u = 0; u < GB_ROWS / 64; ++u) {
                 const uint32_t k = min(base + (uint32_t)(u * 64 + lane), total - 1u);   // clamped: branch-free loads
@@ -662,19 +677,20 @@ __global__ void __launch_bounds__(256) raster_geom_backward_kernel(
                 }
                 const size_t row = (size_t)__shfl(first, lo) + (k - __shfl(excl, lo));
                 m0[u] = part[2 * row];
-                m1[u] = part[2 * row + 1];
+                m1[u] = *reinterpret_cast<const float2 *>(part + 2 * row + 1);   // S4, S5; the rest of the row is padding
             }
             __builtin_amdgcn_wave_barrier();   // the previous pass has been read
 #pragma unroll
             for (int u = 0; u < GB_ROWS / 64; ++u) {
-                wrows[2 * (u * 64 + lane)] = m0[u];
-                wrows[2 * (u * 64 + lane) + 1] = m1[u];
+                wrows_a[u * 64 + lane] = m0[u];
+                wrows_b[u * 64 + lane] = m1[u];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             const uint32_t r0 = max(excl, base), r1 = min(excl + ninst, base + (uint32_t)GB_ROWS);
             for (uint32_t r = r0; r < r1; ++r) {
-                const float4 a0 = wrows[2 * (r - base)], a1 = wrows[2 * (r - base) + 1];
+                const float4 a0 = wrows_a[r - base];
+                const float2 a1 = wrows_b[r - base];
                 S0 += a0.x; S1 += a0.y; S2 += a0.z; S3 += a0.w; S4 += a1.x; S5 += a1.y;
             }
         }
