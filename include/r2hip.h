@@ -388,7 +388,7 @@ R2_API int r2_profile_host(double *pre_sync_us, double *post_sync_us, long long 
  * r2_fdk_filter: cosine pre-weight (cone != 0: DSD / sqrt(DSD^2 + u^2 + v^2) at the pixel centres, pixel size du x dv) and
  *   ramp filter along detector rows: out[v][i] = scale * sum_j w(j,v) projs[v][j] * taps[i - j + W - 1], taps = the 2W-1
  *   spatial taps of the (windowed) ramp (host side: r2_gaussian_amd/fdk.py:ramp_taps), scale = (DSD/DSO)(2 pi/V)/(4 du).
- *   The result is stored transposed: filtered_t[V][W][H].
+ *   The result is stored transposed: filtered_t[V][W][H].  W <= 4096 and V <= 65535, else R2_ERR_INVALID.
  * r2_fdk_backproject: vol[nx][ny][nz] = sum over the views (in order) of the bilinear sample (zero outside the detector) of
  *   filtered_t at the projection of the voxel centre, times (DSO / U)^2 for cone beams (U = p_hom.w, the depth along the
  *   central ray).  projmatrices [V,16] are the full_proj_transform matrices the rasterizer takes (same memory layout), voxel

@@ -86,25 +86,31 @@ def ndc2pix(v, S):
     return ((v + 1.0) * S - 1.0) * 0.5
 
 
+def voxel_footprints(full_proj, H, W, nVoxel, sVoxel, center):
+    """Per view: (fx, fy, inv), each [nx,ny,nz] float64 -- the detector pixel coordinates every voxel centre projects to on
+    an H x W detector, and 1 / its homogeneous w (the view-space depth U for a cone beam)."""
+    nx, ny, nz = [int(n) for n in nVoxel]
+    d = [float(s) / n for s, n in zip(sVoxel, (nx, ny, nz))]
+    ax = [center[k] - sVoxel[k] / 2.0 + (np.arange(n) + 0.5) * d[k] for k, n in enumerate((nx, ny, nz))]
+    X, Y, Z = np.meshgrid(ax[0], ax[1], ax[2], indexing="ij")
+    for Mv in full_proj:
+        M = np.asarray(Mv, dtype=np.float64)
+        hx = X * M[0, 0] + Y * M[1, 0] + Z * M[2, 0] + M[3, 0]
+        hy = X * M[0, 1] + Y * M[1, 1] + Z * M[2, 1] + M[3, 1]
+        hw = X * M[0, 3] + Y * M[1, 3] + Z * M[2, 3] + M[3, 3]
+        inv = 1.0 / (hw + 1e-7)
+        yield ndc2pix(hx * inv, W), ndc2pix(hy * inv, H), inv
+
+
 def fdk_backproject(filtered, full_proj, DSO, nVoxel, sVoxel, center, cone=True, return_abs=False):
     """filtered [V,H,W]; full_proj [V,4,4] as the rasterizer takes it (row-vector convention: p_hom = [x,y,z,1] @ M).
     -> vol [nx,ny,nz] float64 (and the sum of |terms| per voxel when return_abs)."""
     q = np.asarray(filtered, dtype=np.float64)
     V, H, W = q.shape
     nx, ny, nz = [int(n) for n in nVoxel]
-    d = [float(s) / n for s, n in zip(sVoxel, (nx, ny, nz))]
-    ax = [center[k] - sVoxel[k] / 2.0 + (np.arange(n) + 0.5) * d[k] for k, n in enumerate((nx, ny, nz))]
-    X, Y, Z = np.meshgrid(ax[0], ax[1], ax[2], indexing="ij")
     vol = np.zeros((nx, ny, nz))
     absum = np.zeros((nx, ny, nz))
-    for v in range(V):
-        M = np.asarray(full_proj[v], dtype=np.float64)
-        hx = X * M[0, 0] + Y * M[1, 0] + Z * M[2, 0] + M[3, 0]
-        hy = X * M[0, 1] + Y * M[1, 1] + Z * M[2, 1] + M[3, 1]
-        hw = X * M[0, 3] + Y * M[1, 3] + Z * M[2, 3] + M[3, 3]
-        inv = 1.0 / (hw + 1e-7)
-        fx = ndc2pix(hx * inv, W)
-        fy = ndc2pix(hy * inv, H)
+    for v, (fx, fy, inv) in enumerate(voxel_footprints(full_proj[:V], H, W, nVoxel, sVoxel, center)):
         x0 = np.floor(fx)
         y0 = np.floor(fy)
         ax_, ay_ = fx - x0, fy - y0

@@ -158,6 +158,10 @@ extern "C" int r2_fdk_filter(int V, int H, int W, const float *projs, const floa
         set_error("r2_fdk_filter: detector rows longer than 4096 pixels are not supported (W = %d)", W);
         return R2_ERR_INVALID;
     }
+    if (V > 65535) {
+        set_error("r2_fdk_filter: more than 65535 views do not fit one launch (V = %d)", V);
+        return R2_ERR_INVALID;
+    }
     const int Wp = (W + 7) & ~7, PAD = 8 + ((4 - (W & 3)) & 3);
     const int RB = W <= 1024 ? 16 : (W <= 2048 ? 8 : 4);
     const size_t lds = ((size_t)RB * (Wp + 4) + (size_t)(Wp + W + PAD)) * sizeof(float);
