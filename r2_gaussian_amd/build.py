@@ -74,6 +74,7 @@ SOURCES = {
     "gaussian_plan.hip": EXACT,
     "tv_descent.hip": FAST,
     "dispatch.hip": FAST,
+    "host_runtime.hip": FAST,
 }
 
 

@@ -13,8 +13,8 @@
 // is raised and the caller re-sorts with the radix sort; the flag is read at the host synchronisation the forward
 // pass has anyway.
 #include "r2_common.hpp"
+#include "host_tables.hpp"
 #include <algorithm>
-#include <atomic>
 #include <cstddef>
 #include <cstdlib>
 #include <cmath>
@@ -514,21 +514,8 @@ struct HintEntry {
 };
 thread_local HintEntry g_hints[2][4];
 thread_local unsigned g_hint_clock[2] = { 0, 0 };
-std::atomic<int> g_hint_mode{-1};   // -1: read R2_DEPTH_HINT from the environment on first use; 0 off; 1 on
+EnvSwitch g_hint_switch("R2_DEPTH_HINT", true);
 
-bool hints_enabled()
-{
-    int m = g_hint_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char *e = getenv("R2_DEPTH_HINT");
-        int want = (e && e[0] == '0') ? 0 : 1;
-        // several threads may get here at once: the first to install its (identical) answer wins
-        int expected = -1;
-        g_hint_mode.compare_exchange_strong(expected, want, std::memory_order_relaxed);
-        m = g_hint_mode.load(std::memory_order_relaxed);
-    }
-    return m == 1;
-}
 HintEntry *find_hint(int which, size_t P)
 {
     for (auto &h : g_hints[which])
@@ -539,7 +526,7 @@ HintEntry *find_hint(int which, size_t P)
 
 bool depth_hint_lookup(int which, size_t P, DepthHint *out)
 {
-    if (!hints_enabled() || which < 0 || which > 1) return false;
+    if (!g_hint_switch.on() || which < 0 || which > 1) return false;
     const HintEntry *h = find_hint(which, P);
     if (!h || (!h->has_pos && !h->has_neg)) return false;
     const uint32_t nb = 1u << log_buckets(P);
@@ -598,7 +585,7 @@ void depth_hint_update(int which, size_t P, const uint32_t w[DW_COUNT], bool ove
 // 2: forget the hint history.  Results never depend on this: it only selects between two exact sorting paths.
 extern "C" void r2_depth_hint_control(int mode)
 {
-    if (mode == 0 || mode == 1) r2::g_hint_mode.store(mode, std::memory_order_relaxed);
+    r2::g_hint_switch.set(mode);
     if (mode == 2)
         for (auto &tab : r2::g_hints)
             for (auto &e : tab) e = r2::HintEntry();

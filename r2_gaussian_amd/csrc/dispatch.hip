@@ -1,8 +1,7 @@
 // dispatch.hip -- the chain rules of dispatch.hpp and their counters (r2_path_stats / r2_path_stat_name in r2hip.h).
 #include "dispatch.hpp"
 #include "voxel_state.hpp"
-
-#include <atomic>
+#include "host_tables.hpp"
 
 namespace r2 {
 
@@ -64,9 +63,6 @@ extern "C" int r2_path_stat_count(void) { return (int)r2::PS_COUNT; }
 extern "C" const char *r2_path_stat_name(int i) { return (i >= 0 && i < (int)r2::PS_COUNT) ? r2::PATH_NAMES[i] : nullptr; }
 extern "C" int r2_path_stats(long long *out, int n, int reset)
 {
-    for (int i = 0; i < (int)r2::PS_COUNT; ++i) {
-        if (out && i < n) out[i] = r2::g_path[i].load(std::memory_order_relaxed);
-        if (reset) r2::g_path[i].store(0, std::memory_order_relaxed);
-    }
+    r2::stats_read(r2::g_path, (int)r2::PS_COUNT, out, n, reset);
     return (int)r2::PS_COUNT;
 }

@@ -14,6 +14,12 @@
 //                      general      everything (debug, x-slabs of <= 64 tiles, larger grids)
 //   render kernels     one-wave forward / four-wave forward (ids >= 2^28) / debug (n_contrib)
 // Results never depend on the chain: point_list, ranges, images / volumes and gradients are identical (tests/test_*_gpu.py compare them).
+//
+// This file is the RULE.  The general chain's SEQUENCE (depth order, num_rendered check, state, duplicate, tile sort, ranges + work
+// list) is chain_general.hpp, shared by raster_api.hip and voxel_api.hip; the per-thread TABLES of the fast chains (LRU table, the
+// environment-then-control-call switch, the statistics read-out) are host_tables.hpp, and their per-(thread, device, stream) counter
+// block is device_blocks.hpp; the host RUNTIME every chain leans on (error text, stage timers, pinned words, mailbox, defer slots,
+// per-device queries) is host_runtime.hip.
 #pragma once
 #include "r2_common.hpp"
 

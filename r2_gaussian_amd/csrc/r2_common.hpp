@@ -14,7 +14,7 @@ constexpr int WAVE = 64;         // CDNA4 wavefront
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
-void set_error(const char *fmt, ...);
+void set_error(const char *fmt, ...);   // host_runtime.hip: the calling thread's text for r2_last_error()
 
 #define R2_HIP_TRY(expr)                                                                         \
     do {                                                                                          \
@@ -67,7 +67,7 @@ void set_error(const char *fmt, ...);
 #define R2_TS_AT8(unit, ph)
 #endif
 
-// ---- optional per-stage timing with HIP events on the caller's stream (r2_profile_* in r2hip.h)
+// ---- host_runtime.hip: optional per-stage timing with HIP events on the caller's stream (r2_profile_* in r2hip.h)
 enum Stage {
     ST_RAS_PREPROCESS = 0, ST_RAS_SCAN, ST_RAS_DUPLICATE, ST_RAS_SORT, ST_RAS_RANGES, ST_RAS_RENDER_FWD,
     ST_RAS_RENDER_BWD, ST_RAS_GEOM_BWD,
@@ -265,9 +265,10 @@ int fill_tiles_from_ranges(const uint2 *ranges, size_t T, uint32_t *tiles, hipSt
 size_t scan_gather_temp_bytes(int P);
 int inclusive_scan_gather_u32(void *temp, size_t temp_bytes, const uint32_t *in, const uint32_t *order, uint32_t *out,
                               int P, hipStream_t s, uint32_t *total_out = nullptr /* device word receiving out[P-1] */);
+// ---- host_runtime.hip: per-device queries, the pinned read-back words, the mailbox, the defer slot pool
 // one small device->host read (n <= 16 words) through pinned memory + busy-wait on an event.  begin enqueues the copy on the
 // stream, wait spins until it has landed: work enqueued between the two keeps the GPU busy while the host waits.
-int current_device_slot();   // index of the current HIP device into small per-device host tables (binning.hip)
+int current_device_slot();   // index of the current HIP device into small per-device host tables
 int device_cu_count();       // compute units of the current device (cached per device)
 constexpr int R2_MAX_DEVICES = 64;
 // > 64 KB of dynamic LDS for `kernel` on the current device, asked for once per device; state = the call site's
@@ -286,13 +287,14 @@ void host_mark_forward_end();
 int host_mailbox_arm(uint32_t **mailbox /* device-visible pinned host memory, 16 words */, uint32_t *seq);
 int host_mailbox_wait(uint32_t seq, uint32_t *out, int n, hipStream_t s);
 void host_words_release();   // the calling thread's pinned words (r2_thread_release; also at thread exit)
-// deferred num_rendered (binning.hip): a forward that does not wait posts its control words to a pool slot and returns a token
+// deferred num_rendered: a forward that does not wait posts its control words to a pool slot and returns a token
 // (>= DEFER_TOKEN_FLAG, still a non-negative int); the backward resolves it.  -1 from acquire: no slot, wait as usual
 constexpr int DEFER_TOKEN_FLAG = 0x40000000;
 int defer_acquire(uint32_t **mailbox, uint32_t *seq, uint32_t cap);
 int defer_resolve(int token, uint32_t *out, int n, uint32_t *cap, hipStream_t s, bool release);
 bool defer_peek(int token, uint32_t *out, int n, uint32_t *cap);
 bool defer_first_short(int token);
+// ---- binning.hip again
 // tile ranges of the sorted list + point_list[k] = vals_unsorted[perm[k]] in the same pass
 int tile_ranges(const uint32_t *tiles_sorted, const uint32_t *perm, const uint32_t *vals_unsorted, uint32_t *point_list,
                 size_t R, uint2 *ranges, size_t T, hipStream_t s, bool ranges_zeroed = false);

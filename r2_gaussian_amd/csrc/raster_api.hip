@@ -3,8 +3,12 @@
 #include "raster_state.hpp"
 #include "voxel_state.hpp"
 #include "dispatch.hpp"
+#include "chain_general.hpp"
+#include "host_tables.hpp"
 
 using namespace r2;
+
+static EnvSwitch g_sorted_records("R2_SORTED_RECORDS", true), g_emit_hist("R2_EMIT_HIST", true);
 
 // Forward of V views of the same Gaussians (V = 1: the reference's call).  viewmatrices / projmatrices: [V,16]; out_color
 // [V,H,W]; radii [V,P].  See raster_state.hpp (tile_decode) for how the views share one pipeline.
@@ -64,143 +68,58 @@ static int raster_forward_impl(
     }
     const RasterGeom geom = RasterGeom::carve(gchunk, PV);
 
-    // Binning, first half: view instances in (depth, id) order + their instance offsets in that order.
-    //   hinted path (depth range known from the previous call with this size): preprocess registers every key in its bucket,
-    //   one dual scan + place + rank finish the job, and the host's read-back overlaps place + rank;
-    //   un-hinted path: min/max, count, scan, place, rank, then the offsets scan;
-    //   either may overflow a bucket (many identical depths / a stale hint): general radix sort + scan instead.
-    int rc = depth_order_prepare(geom.dorder_temp, geom.dorder_bytes, (size_t)PV, s);   // zeroes counters + the host-read words
-    if (rc) return rc;
-    uint32_t *host_words = geom.host_words;
-    DepthHint hint;
-    const bool hinted = depth_hint_lookup(0, (size_t)PV, &hint);
-    const uint32_t pre_wgs = (uint32_t)((PV + 255) / 256);
-    DepthReg reg{};
+    // Binning, first half (chain_general.hpp): view instances in (depth, id) order + their instance offsets in that order.
     // sorted records for the emission kernel: the preprocess hands each key's tile rectangle (one word) to the depth order
-    static const bool rects_on = [] { const char *e = getenv("R2_SORTED_RECORDS"); return !(e && e[0] == '0'); }();
-    const bool rects = hinted && rects_on && gx <= 256 && gy <= 256;
-    if (hinted) reg = depth_order_reg(geom.dorder_temp, (size_t)PV, hint, rects);
-    { StageScope t(ST_RAS_PREPROCESS, s);
-    launch_raster_preprocess(geom, P, V, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, viewmatrices,
-                             projmatrices, width, height, tan_fovx, tan_fovy, mode, radii, host_words + DW_USER, reg, true, s); }
-    R2_STAGE_CHECK(debug, s, "preprocess");
-    uint32_t hw[DW_COUNT] = { 0 };
-    if (hinted) {
-        uint32_t *mailbox = nullptr, mailbox_seq = 0;
-        rc = host_mailbox_arm(&mailbox, &mailbox_seq);
-        if (rc) return rc;
-        { StageScope t(ST_RAS_SCAN, s);
-        rc = depth_order_fast_scan(geom.dorder_temp, (size_t)PV, pre_wgs, mailbox, mailbox_seq, s); }
-        if (rc) return rc;
-        { StageScope t(ST_RAS_DEPTHSORT, s);
-        rc = depth_order_fast_finish(geom.dorder_temp, (size_t)PV, geom.depth_key, geom.tiles_touched, geom.order, geom.offsets, s, rects); }
-        if (rc) return rc;
-        rc = host_mailbox_wait(mailbox_seq, hw, DW_COUNT, s);   // the GPU places + ranks while the host waits for the words
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "depth order (hinted)");
-    } else {
-        { StageScope t(ST_RAS_DEPTHSORT, s);
-        rc = depth_order_buckets(geom.dorder_temp, geom.dorder_bytes, geom.depth_key, geom.order, (size_t)PV, s); }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "depth order");
-        // (fusing the scan's per-group reduction into the depth order's last kernel with per-wave atomics was measured
-        // 4x slower than this separate 5 us kernel: ~5k atomics on ~75 addresses serialise at the memory side)
-        { StageScope t(ST_RAS_SCAN, s);
-        rc = inclusive_scan_gather_u32(geom.scan_temp, geom.scan_bytes, geom.tiles_touched, geom.order, geom.offsets, PV, s,
-                                       host_words + DW_TOTAL); }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "scan");
-        // total number of (tile, Gaussian) instances: sizes the binning state (the reference's D2H, RAS/rasterizer_impl.cu:279)
-        rc = read_host_words(host_words, hw, DW_COUNT, s);
-        if (rc) return rc;
-    }
-    uint32_t num_rendered = hw[DW_TOTAL];
-    const bool overflow = hw[DW_OVERFLOW] != 0;
-    bool full_order = !hinted;   // order / offsets cover all view instances (else only the visible prefix)
-    if (overflow) {   // general radix sort instead
-        rc = sort_pairs_ex(geom.psort_temp, geom.psort_bytes, geom.depth_key, geom.depth_sorted, nullptr /* values = indices */, geom.order, nullptr,
-                           nullptr, (size_t)PV, 32, /*allow_skip=*/true, nullptr, s);
-        if (!rc) rc = inclusive_scan_gather_u32(geom.scan_temp, geom.scan_bytes, geom.tiles_touched, geom.order, geom.offsets, PV,
-                                                s, host_words + DW_TOTAL);
-        uint32_t total = 0;
-        if (!rc) rc = read_host_words(host_words + DW_TOTAL, &total, 1, s);
-        if (rc) return rc;
-        num_rendered = total;
-        full_order = true;
-    }
-    depth_hint_update(0, (size_t)PV, hw, overflow);
-    if (num_rendered > 0x7FFFFFFFu) {   // the API returns it as a non-negative int (like the reference's int num_rendered)
-        set_error("%s: more than 2147483647 (tile, Gaussian) instances: they do not fit the 31-bit num_rendered", what);
-        return R2_ERR_INVALID;
-    }
-    const size_t R = num_rendered;
+    uint32_t *host_words = geom.host_words;
+    ChainOrder ord;
+    int rc = chain_depth_order(
+        CHAIN_RASTER, what, geom, PV, RASTER_STAGES,
+        [&](const DepthReg &reg) {
+            launch_raster_preprocess(geom, P, V, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, viewmatrices,
+                                     projmatrices, width, height, tan_fovx, tan_fovy, mode, radii, host_words + DW_USER, reg, true, s);
+        },
+        /*skip_preprocess=*/false, /*rects_allowed=*/g_sorted_records.on() && gx <= 256 && gy <= 256, /*reset_nvis_on_overflow=*/false, debug, s, &ord);
+    if (rc) return rc;
+    const size_t R = ord.num_rendered;
 
-    // both remaining state buffers are sized by R: the sorted lists (+ backward scratch) and the
-    // forward work list / per-chunk partial images
-    char *bchunk = binningBuffer(RasterBinning::carve(nullptr, R).bytes, binning_user);
-    char *ichunk = imageBuffer(RasterImage::carve(nullptr, T, N, R, debug != 0).bytes, image_user);
-    if (!bchunk || !ichunk) {
-        set_error("%s: binning/image allocation callback returned NULL", what);
-        return R2_ERR_ALLOC;
-    }
-    const RasterBinning bin = RasterBinning::carve(bchunk, R);
-    const RasterImage img = RasterImage::carve(ichunk, T, N, R, debug != 0);
+    RasterBinning bin{};
+    RasterImage img{};
+    rc = chain_state(what, binningBuffer, binning_user, imageBuffer, image_user, R,
+                     [&](char *chunk) { return RasterImage::carve(chunk, T, N, R, debug != 0); }, &bin, &img);
+    if (rc) return rc;
 
-    const uint32_t *tile_counts = nullptr;
-    bool work_built = false;   // ranges + work list already produced by the sort's last kernel
-    if (R > 0) {
-        const int bit = (int)higher_msb((uint32_t)(T > 1 ? T - 1 : 1));   // bits of the largest tile id (the reference
-                                                                     // sorts getHigherMsb(T) bits: one more for T = 2^k)
-        bool hist_ready = false;   // the emission kernel built the tile sort's histograms as well
-        { StageScope t(ST_RAS_DUPLICATE, s);
-        if (rects && !full_order) {
-            static const bool fuse_on = [] { const char *e = getenv("R2_EMIT_HIST"); return !(e && e[0] == '0'); }();
-            TileSortPlan plan;
-            if (fuse_on && !debug && tile_sort_plan(bin.sort_temp, bin.sort_bytes, R, bit, &plan))
-                hist_ready = launch_raster_emit_hist(geom, bin, P, V, width, height, host_words + DW_NVIS, R, plan, s);
-            if (!hist_ready) launch_raster_duplicate_sorted(geom, bin, P, V, width, height, host_words + DW_NVIS, s);
-        } else {
-            launch_raster_duplicate(geom, bin, P, V, radii, width, height, full_order ? nullptr : host_words + DW_NVIS, s);
-        } }
-        R2_STAGE_CHECK(debug, s, "duplicateWithKeys");
-        // stable sort by tile id; payloads: the emission index (-> perm, the backward's scratch row) and the Gaussian
-        // id (-> point_list)
-        { StageScope t(ST_RAS_SORT, s);
-        if (sort_is_single_pass(bit)) {
-            const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, FWD_CHUNK,
-                                 debug ? nullptr : img.tile_done, 0u, 0u,
-                                 raster_ids_leave_room_for_masks((size_t)PV) ? 1u : 0u};
-            rc = sort_by_tile_single_pass(bin.sort_temp, bin.sort_bytes, bin.tiles_unsorted, bin.vals_unsorted, bin.point_list,
-                                          debug ? bin.inv : nullptr, R, bit, &tile_counts, s, &wo, hist_ready);   // inv: introspection only
-            work_built = true;
-        } else {   // > 4096 tiles: general multi-pass sort, then invert its permutation (the scratch is free until backward)
-            uint32_t *perm = reinterpret_cast<uint32_t *>(bin.part);   // scratch for the intermediate pass (free until backward)
-            rc = sort_pairs_ex(bin.sort_temp, bin.sort_bytes, bin.tiles_unsorted, bin.tiles, nullptr, perm, bin.vals_unsorted,
-                               bin.point_list, R, bit, false, nullptr, s, bin.inv);
-        } }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "sort");
-    }
-    { StageScope t(ST_RAS_RANGES, s);
-    if (work_built) {
-        // nothing to do
-    } else if (tile_counts) {   // single-pass sort: per-tile counts are a by-product
-        launch_ranges_and_work(tile_counts, (uint32_t)T, FWD_CHUNK, img.ranges, img.chunk_base, img.work_tile, s);
-    } else {
-        rc = tile_ranges(bin.tiles, nullptr, nullptr, nullptr, R, img.ranges, T, s);
-        if (rc) return rc;
-        launch_build_work(img.ranges, (uint32_t)T, FWD_CHUNK, img.chunk_base, img.work_tile, img.work_temp, s);
-    } }
-    R2_STAGE_CHECK(debug, s, "identifyTileRanges");
+    // second half: stable sort by tile id; payloads: the emission index (-> perm, the backward's scratch row) and the Gaussian
+    // id (-> point_list)
+    const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, FWD_CHUNK, debug ? nullptr : img.tile_done, 0u, 0u,
+                         raster_ids_leave_room_for_masks((size_t)PV) ? 1u : 0u};
+    // > 4096 tiles: general multi-pass sort, then invert its permutation (perm: the backward's scratch, free until then)
+    const ChainMultiPass mp{nullptr, reinterpret_cast<uint32_t *>(bin.part), bin.vals_unsorted, bin.point_list, bin.inv};
+    ChainLists lists;
+    rc = chain_tile_lists(
+        bin, img, R, T, RASTER_STAGES,
+        [&](int bit, bool) {
+            bool hist_ready = false;   // the emission kernel built the tile sort's histograms as well
+            if (ord.rects && !ord.full_order) {
+                TileSortPlan plan;
+                if (g_emit_hist.on() && !debug && tile_sort_plan(bin.sort_temp, bin.sort_bytes, R, bit, &plan))
+                    hist_ready = launch_raster_emit_hist(geom, bin, P, V, width, height, host_words + DW_NVIS, R, plan, s);
+                if (!hist_ready) launch_raster_duplicate_sorted(geom, bin, P, V, width, height, host_words + DW_NVIS, s);
+            } else {
+                launch_raster_duplicate(geom, bin, P, V, radii, width, height, ord.full_order ? nullptr : host_words + DW_NVIS, s);
+            }
+            return hist_ready;
+        },
+        wo, mp, /*zero_ranges_in_duplicate=*/false, debug, s, &lists);
+    if (rc) return rc;
     { StageScope t(ST_RAS_RENDER_FWD, s);
     // single-pass sort: the tile's last work item (or the combine kernel) also writes tiles[k] for the backward
-    launch_raster_render_forward(geom, bin, img, width, height, V, out_color, debug != 0, tile_counts ? bin.tiles : nullptr,
-                                 /*fused_combine=*/work_built && debug == 0, s, nullptr, nullptr, (size_t)PV); }
+    launch_raster_render_forward(geom, bin, img, width, height, V, out_color, debug != 0, lists.tile_counts ? bin.tiles : nullptr,
+                                 /*fused_combine=*/lists.work_built && debug == 0, s, nullptr, nullptr, (size_t)PV); }
     R2_STAGE_CHECK(debug, s, "render");
     // the next call's prediction (visible keys are positive floats: their range is the P class of the host words)
-    raster_tilefirst_note(P, V, width, height, num_rendered, hw[DW_USER] != 0, hw[DW_PMAX], ~hw[DW_PNMAX]);
+    raster_tilefirst_note(P, V, width, height, ord.num_rendered, ord.hw[DW_USER] != 0, ord.hw[DW_PMAX], ~ord.hw[DW_PNMAX]);
     host_mark_forward_end();
-    return (int)num_rendered;
+    return (int)ord.num_rendered;
 }
 
 static int raster_backward_impl(

@@ -34,8 +34,11 @@
 // What must survive from forward to backward sits at prediction-independent offsets (RasterBinning::carve).
 #include "raster_state.hpp"
 #include "dispatch.hpp"
+#include "chain_general.hpp"
+#include "device_blocks.hpp"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdlib>
 #include <vector>
@@ -627,119 +630,52 @@ __global__ void __launch_bounds__(TFK_THREADS, 8) raster_tf_sort_kernel(
 }
 
 // ---- host side
-// Counters that several workgroups bump with atomics live in a small persistent allocation per (host thread, device, stream):
-// self-resetting, so no zero-fill launch precedes the forward.  Owned by the thread: freed when it exits (or on
-// r2_thread_release()); a thread that cycles through more streams than the table holds evicts the least recently used entry
-// (round 4: never freed, and the fast path silently switched itself off after 64 streams -- ADVICE r4).
+// Counters that several workgroups bump with atomics live in the thread's block for (device, stream) -- device_blocks.hpp: TFCounters,
+// then 64 bytes for nparts -- self-resetting, so no zero-fill launch precedes the forward.
 // (a deferred forward whose prediction fell short gets no second pass: its sort kernel clears the counters it leaves behind --
 // the host may not know of the short count before the next forward on the stream is enqueued)
-struct TFWorkspace { int dev; hipStream_t stream; TFCounters *ctr; uint32_t *nparts; bool dirty; unsigned long long used; };
-struct TFWorkspaces {
-    std::vector<TFWorkspace> v;
-    unsigned long long tick = 0;
-    static void free_one(const TFWorkspace &w)
-    {
-        int cur = 0;
-        if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (cur != w.dev && hipSetDevice(w.dev) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (hipFree(w.ctr) != hipSuccess) (void)hipGetLastError();   // (its last forward may still run: hipFree waits for the device)
-        if (cur != w.dev) (void)hipSetDevice(cur);
-    }
-    void release()
-    {
-        for (const TFWorkspace &w : v) free_one(w);
-        v.clear();
-    }
-    ~TFWorkspaces() { release(); }
-};
-thread_local TFWorkspaces g_tf_ws;
-constexpr size_t TF_MAX_WORKSPACES = 16;
-
-TFWorkspace *tf_workspace(int dev, hipStream_t s)
-{
-    TFWorkspaces &t = g_tf_ws;
-    ++t.tick;
-    for (TFWorkspace &w : t.v)
-        if (w.dev == dev && w.stream == s) { w.used = t.tick; return &w; }
-    if (t.v.size() >= TF_MAX_WORKSPACES) {
-        size_t lru = 0;
-        for (size_t i = 1; i < t.v.size(); ++i)
-            if (t.v[i].used < t.v[lru].used) lru = i;
-        TFWorkspaces::free_one(t.v[lru]);
-        t.v.erase(t.v.begin() + (long)lru);
-    }
-    char *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), sizeof(TFCounters) + 64) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    t.v.push_back(TFWorkspace{dev, s, reinterpret_cast<TFCounters *>(p), reinterpret_cast<uint32_t *>(p + sizeof(TFCounters)), true, t.tick});
-    return &t.v.back();
-}
+thread_local DeviceBlocks g_tf_blocks;
 
 // the thread's recent instance counts per problem size: what the prediction is made of
+using TFSize = std::array<int, 4>;   // {P, V, W, H}: Gaussians, stacked views, detector
 struct TFHint {
-    int P, V, W, H;   // Gaussians, stacked views, detector
     uint32_t recent[8], n;
     bool thin;
     uint32_t kmax, kmin;    // depth-key range of the last call (the next call's slabs are laid over it)
-    unsigned long long used;
 };
-thread_local std::vector<TFHint> g_tf_hints;
-thread_local unsigned long long g_tf_hint_tick = 0;
-
-TFHint *tf_hint(int P, int V, int W, int H, bool create)
-{
-    for (TFHint &h : g_tf_hints)
-        if (h.P == P && h.V == V && h.W == W && h.H == H) { h.used = ++g_tf_hint_tick; return &h; }
-    if (!create) return nullptr;
-    if (g_tf_hints.size() >= 16) {
-        size_t lru = 0;
-        for (size_t i = 1; i < g_tf_hints.size(); ++i)
-            if (g_tf_hints[i].used < g_tf_hints[lru].used) lru = i;
-        g_tf_hints.erase(g_tf_hints.begin() + (long)lru);
-    }
-    g_tf_hints.push_back(TFHint{P, V, W, H, {0}, 0u, false, 0u, 0u, ++g_tf_hint_tick});
-    return &g_tf_hints.back();
-}
+using TFHints = LruTable<TFSize, TFHint, 16>;
+thread_local TFHints g_tf_hints;
 
 // no call with this P yet -- every densification changes it (train.py:155-168) --: the thread's most recent call on the same
 // detector, scaled by the ratio of the Gaussian counts
-const TFHint *tf_hint_nearby(int V, int W, int H)
+const TFHints::Entry *tf_hint_nearby(int V, int W, int H)
 {
-    const TFHint *best = nullptr;
-    for (const TFHint &h : g_tf_hints)
-        if (h.V == V && h.W == W && h.H == H && h.n != 0u && h.P > 0 && (!best || h.used > best->used)) best = &h;
+    const TFHints::Entry *best = nullptr;
+    for (const TFHints::Entry &e : g_tf_hints)
+        if (e.key[1] == V && e.key[2] == W && e.key[3] == H && e.value.n != 0u && e.key[0] > 0 && (!best || e.used > best->used)) best = &e;
     return best;
 }
 
 // what the chain did, process-wide (r2_tile_first_stats): forwards that took it, forwards it declined (no prediction / limits),
 // chains run a second time because the prediction fell short, renders repeated for the thin-Gaussian variant, forwards whose
 // prediction was seeded from another P (the call after a densification)
-std::atomic<long long> g_tf_taken{0}, g_tf_declined{0}, g_tf_rerun{0}, g_tf_rerender{0}, g_tf_seeded{0};
+enum { TF_TAKEN = 0, TF_DECLINED, TF_RERUN, TF_RERENDER, TF_SEEDED, TF_STATS };
+std::atomic<long long> g_tf_stats[TF_STATS];
+// ... and of the deferred num_rendered (r2_defer_count_stats)
+enum { DEFER_TAKEN = 0, DEFER_NO_SLOT, DEFER_SHORT, DEFER_STATS };
+std::atomic<long long> g_defer_stats[DEFER_STATS];
+void count(std::atomic<long long> &c) { c.fetch_add(1, std::memory_order_relaxed); }
 
-std::atomic<int> g_tf_mode{-1};   // -1: not decided yet (environment), 0: off, 1: on
-std::atomic<int> g_defer_mode{-1};   // deferred num_rendered (r2_defer_count_control): -1 environment, 0 off (default), 1 on
-std::atomic<long long> g_defer_taken{0}, g_defer_no_slot{0}, g_defer_short{0};
+EnvSwitch g_tf_switch("R2_TILE_FIRST", true);
+EnvSwitch g_defer_switch("R2_DEFER_COUNT", false);   // deferred num_rendered (r2_defer_count_control): off by default
 
 // the one comparison of a deferred forward's true count with the capacity it was launched with: the forward thread's pending
 // poll, r2_defer_count_resolve and the backward all come here, and a short forward is counted once, whoever finds it first
-bool defer_count_short(int token, uint32_t count, uint32_t cap)
+bool defer_count_short(int token, uint32_t count_, uint32_t cap)
 {
-    if (count <= cap) return false;
-    if (defer_first_short(token)) g_defer_short.fetch_add(1, std::memory_order_relaxed);
+    if (count_ <= cap) return false;
+    if (defer_first_short(token)) count(g_defer_stats[DEFER_SHORT]);
     return true;
-}
-
-bool defer_enabled()
-{
-    int on = g_defer_mode.load(std::memory_order_relaxed);
-    if (on < 0) {
-        const char *e = getenv("R2_DEFER_COUNT");
-        on = (e && e[0] == '1') ? 1 : 0;
-        g_defer_mode.store(on, std::memory_order_relaxed);
-    }
-    return on != 0;
 }
 
 // deferred forwards of this thread whose instance count it has not seen yet: polled (non-blocking) at its next forward, so that its
@@ -747,16 +683,6 @@ bool defer_enabled()
 struct TFPending { int token, P, V, W, H; };
 thread_local std::vector<TFPending> g_tf_pending;
 
-bool tf_switched_on()
-{
-    int on = g_tf_mode.load(std::memory_order_relaxed);
-    if (on < 0) {
-        const char *e = getenv("R2_TILE_FIRST");
-        on = (e && e[0] == '0') ? 0 : 1;
-        g_tf_mode.store(on, std::memory_order_relaxed);
-    }
-    return on != 0;
-}
 bool tf_lds_ok()
 {
     static signed char lds_state[R2_MAX_DEVICES] = {};
@@ -768,7 +694,7 @@ bool tf_lds_ok()
 
 void raster_tilefirst_note(int P, int V, int W, int H, uint32_t num_rendered, bool thin, uint32_t kmax, uint32_t kmin)
 {
-    TFHint *h = tf_hint(P, V, W, H, true);
+    TFHint *h = g_tf_hints.find_or_insert({P, V, W, H});
     h->recent[h->n++ & 7u] = num_rendered;
     h->thin = thin;
     h->kmax = kmax;
@@ -791,11 +717,11 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     const TFGrid grid = tf_grid((int)std::min<size_t>(PVs, (size_t)1 << 24), device_cu_count());
     const size_t wgs = grid.wgs;
     // the static rule: dispatch.hpp (debug calls never get here)
-    const bool on = tf_switched_on();
+    const bool on = g_tf_switch.on();
     const RasterChoice choice = raster_forward_choice((size_t)P, (size_t)V, width, height, false, on, on && tf_lds_ok(), wgs);
     if (!choice.tile_first) {
         path_count(choice.why);
-        g_tf_declined.fetch_add(1, std::memory_order_relaxed);
+        count(g_tf_stats[TF_DECLINED]);
         return TF_NOT_TAKEN;
     }
     const int PV = (int)PVs;
@@ -815,35 +741,39 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     // ---- the prediction: the largest count of the thread's recent calls with this P and detector; for a P it has not rendered
     // yet (the call after a densification) the most recent call on the same detector, scaled -- same scene, more Gaussians
     uint32_t rmax = 0, kmax = 0, kmin = 0;
-    if (const TFHint *hint = tf_hint(P, V, width, height, false); hint && hint->n != 0u) {
+    if (const TFHint *hint = g_tf_hints.find({P, V, width, height}); hint && hint->n != 0u) {
         for (uint32_t i = 0; i < std::min(hint->n, 8u); ++i) rmax = std::max(rmax, hint->recent[i]);
         kmax = hint->kmax; kmin = hint->kmin;
-    } else if (const TFHint *near = tf_hint_nearby(V, width, height)) {
+    } else if (const TFHints::Entry *e = tf_hint_nearby(V, width, height)) {
+        const TFHint *near = &e->value;
         uint32_t r0 = 0;
         for (uint32_t i = 0; i < std::min(near->n, 8u); ++i) r0 = std::max(r0, near->recent[i]);
-        const double f = (double)P / (double)near->P;
+        const double f = (double)P / (double)e->key[0];
         rmax = (uint32_t)std::min<double>((double)r0 * f * 1.1, 2.0e9);
         kmax = near->kmax; kmin = near->kmin;
-        g_tf_seeded.fetch_add(1, std::memory_order_relaxed);
+        count(g_tf_stats[TF_SEEDED]);
         path_count(PS_RAS_EVENT_SEEDED);
     } else {
         path_count(PS_RAS_GENERAL_NO_PREDICTION);
-        g_tf_declined.fetch_add(1, std::memory_order_relaxed);
+        count(g_tf_stats[TF_DECLINED]);
         return TF_NOT_TAKEN;   // no prediction yet: the general path, which leaves one behind
     }
     // (deferred forwards of this thread that have completed meanwhile: their counts into the history -- done above the prediction)
     int dev = 0;
     R2_HIP_TRY(hipGetDevice(&dev));
-    TFWorkspace *ws = tf_workspace(dev, s);
-    if (!ws) {
+    // (zero-filled here, ahead of the chain's first kernel, when it is new or a call that failed half way left it dirty)
+    char *const block = static_cast<char *>(g_tf_blocks.acquire(dev, s, sizeof(TFCounters) + 64));
+    if (!block) {
         path_count(PS_RAS_GENERAL_NO_WORKSPACE);
-        g_tf_declined.fetch_add(1, std::memory_order_relaxed);
+        count(g_tf_stats[TF_DECLINED]);
         return TF_NOT_TAKEN;
     }
+    TFCounters *const ctr = reinterpret_cast<TFCounters *>(block);
+    uint32_t *const nparts = reinterpret_cast<uint32_t *>(block + sizeof(TFCounters));
     path_count(PS_RAS_TILE_FIRST);
     // + 25 %, in steps of 64 K instances (the allocator behind the callbacks then sees few distinct sizes); a deferred forward,
     // which cannot repeat itself when the prediction falls short, takes + 50 %
-    const bool defer = defer_enabled();
+    const bool defer = g_defer_switch.on();
     size_t cap = (((size_t)rmax + (defer ? rmax / 2 : rmax / 4) + 16384) + 65535) & ~(size_t)65535;
 
     // depth slabs per tile, from an ESTIMATE of the longest tile list: a dense tile holds ~8x the mean on every scene seen so far
@@ -869,20 +799,17 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
         return R2_ERR_ALLOC;
     }
     const RasterGeom geom = RasterGeom::carve(gchunk, PV, TL, wgs);
-    if (ws->dirty)   // first use, or a call that failed half way
-        R2_HIP_TRY(hipMemsetAsync(ws->ctr, 0, sizeof(TFCounters) + 64, s));
-    ws->dirty = true;
     uint32_t *mailbox = nullptr, mailbox_seq = 0;
     int rc = 0, token = -1;
     if (defer && cap < (size_t)DEFER_TOKEN_FLAG) {
         token = defer_acquire(&mailbox, &mailbox_seq, (uint32_t)cap);
-        if (token < 0) g_defer_no_slot.fetch_add(1, std::memory_order_relaxed);
+        if (token < 0) count(g_defer_stats[DEFER_NO_SLOT]);
     }
     if (token < 0) rc = host_mailbox_arm(&mailbox, &mailbox_seq);
     if (rc) return rc;
     { StageScope t(ST_RAS_PREPROCESS, s);
     launch_raster_preprocess_tf(geom, P, V, grid, slabs, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, viewmatrix,
-                                projmatrix, width, height, tan_fovx, tan_fovy, mode, radii, ws->ctr, s); }
+                                projmatrix, width, height, tan_fovx, tan_fovy, mode, radii, ctr, s); }
     R2_HIP_TRY(hipGetLastError());
 
     RasterBinning bin{};
@@ -892,14 +819,9 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     bool post_mailbox = true;
     auto enqueue = [&](size_t capacity, bool render_only) -> int {
         if (!render_only) {
-            char *bchunk = binningBuffer(RasterBinning::carve(nullptr, capacity).bytes, binning_user);
-            char *ichunk = imageBuffer(RasterImage::carve(nullptr, T, N, capacity, false, TL).bytes, image_user);
-            if (!bchunk || !ichunk) {
-                set_error("%s: binning/image allocation callback returned NULL", what);
-                return R2_ERR_ALLOC;
-            }
-            bin = RasterBinning::carve(bchunk, capacity);
-            img = RasterImage::carve(ichunk, T, N, capacity, false, TL);
+            const int arc = chain_state(what, binningBuffer, binning_user, imageBuffer, image_user, capacity,
+                                        [&](char *chunk) { return RasterImage::carve(chunk, T, N, capacity, false, TL); }, &bin, &img);
+            if (arc) return arc;
             uint2 *pairs = reinterpret_cast<uint2 *>(bin.part);   // backward scratch (32 bytes per instance), free until then
             { StageScope t(ST_RAS_DUPLICATE, s);
             const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, FWD_CHUNK, img.tile_done, 0u, (uint32_t)img.NW,
@@ -907,9 +829,9 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
 #define R2_TF_SCATTER(SLB)                                                                                                        \
             raster_tf_scatter_kernel<SLB><<<dim3((unsigned)wgs + TFS_SERVICE), dim3(TFS_THREADS), TL * sizeof(uint32_t), s>>>(         \
                 PV, P, gy, grid.per_wg, grid.threads, gx, (uint32_t)TL, slabs, geom.tf_rect, geom.rec, geom.depth_key, geom.tiles_touched, geom.tf_wgoff, \
-                geom.tf_wgmm, (uint32_t)wgs, ws->ctr, geom.host_words, post_mailbox ? mailbox : nullptr, mailbox_seq,                   \
+                geom.tf_wgmm, (uint32_t)wgs, ctr, geom.host_words, post_mailbox ? mailbox : nullptr, mailbox_seq,                   \
                 (uint32_t)std::min<size_t>(capacity, 0x7FFFFFFFu), pairs, wo, img.tf_parts, (uint32_t)img.NP, img.tf_parts + img.NP,   \
-                ws->nparts)
+                nparts)
             if (slabs.n > 1u) R2_TF_SCATTER(true);
             else R2_TF_SCATTER(false);
 #undef R2_TF_SCATTER
@@ -917,7 +839,7 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
             R2_HIP_TRY(hipGetLastError());
             { StageScope t(ST_RAS_SORT, s);
             raster_tf_sort_kernel<<<dim3((unsigned)(img.NP + (TL + TFK_GROUPS - 1) / TFK_GROUPS)), dim3(TFK_THREADS), TFK_LDS, s>>>(
-                img.tf_parts, (uint32_t)img.NP, img.tf_parts + img.NP, ws->nparts, pairs, bin.point_list, ws->ctr, geom.host_words,
+                img.tf_parts, (uint32_t)img.NP, img.tf_parts + img.NP, nparts, pairs, bin.point_list, ctr, geom.host_words,
                 (uint32_t)std::min<size_t>(capacity, 0x7FFFFFFFu), token >= 0 ? (uint32_t)TL : 0u); }
             R2_HIP_TRY(hipGetLastError());
         } else {
@@ -934,9 +856,9 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     if (rc) return rc;
     if (token >= 0) {
         // ---- deferred: no wait.  The token goes back as num_rendered; the backward resolves it (raster_backward_impl)
-        ws->dirty = false;   // (a count beyond the capacity: the sort kernel has cleared the counters -- clear_lists)
-        g_tf_taken.fetch_add(1, std::memory_order_relaxed);
-        g_defer_taken.fetch_add(1, std::memory_order_relaxed);
+        g_tf_blocks.clean(dev, s);   // (a count beyond the capacity: the sort kernel has cleared the counters -- clear_lists)
+        count(g_tf_stats[TF_TAKEN]);
+        count(g_defer_stats[DEFER_TAKEN]);
         path_count(PS_RAS_EVENT_DEFERRED);
         g_tf_pending.push_back(TFPending{token, P, V, width, height});
         host_mark_wait_begin();   // (r2_profile_host: a wait of zero length)
@@ -948,24 +870,22 @@ int raster_forward_tilefirst(const char *what, r2_alloc_fn geometryBuffer, void 
     if (rc) return rc;
     const uint32_t num_rendered = hw[DW_TOTAL];
     const bool thin = hw[DW_USER] != 0u;
-    if (num_rendered > 0x7FFFFFFFu) {
-        set_error("%s: more than 2147483647 (tile, Gaussian) instances: they do not fit the 31-bit num_rendered", what);
-        return R2_ERR_INVALID;
-    }
+    rc = check_num_rendered(CHAIN_RASTER, what, num_rendered);
+    if (rc) return rc;
     post_mailbox = false;
     if ((size_t)num_rendered > cap) {
-        g_tf_rerun.fetch_add(1, std::memory_order_relaxed);
+        count(g_tf_stats[TF_RERUN]);
         path_count(PS_RAS_EVENT_SECOND_PASS);
         rc = enqueue(num_rendered, false);      // the prediction fell short: exact sizes, same kernels
         if (rc) return rc;
     }
-    ws->dirty = false;
-    g_tf_taken.fetch_add(1, std::memory_order_relaxed);
+    g_tf_blocks.clean(dev, s);
+    count(g_tf_stats[TF_TAKEN]);
     raster_tilefirst_note(P, V, width, height, num_rendered, thin, hw[DW_NMAX], ~hw[DW_NNMAX]);
     return (int)num_rendered;
 }
 
-void raster_tilefirst_release() { g_tf_ws.release(); g_tf_hints.clear(); g_tf_pending.clear(); }
+void raster_tilefirst_release() { g_tf_blocks.release(); g_tf_hints.clear(); g_tf_pending.clear(); }
 
 // the backward's side of a deferred forward (and r2_defer_count_resolve's, which keeps the slot: release = false): token -> the
 // true instance count (waits for the control words, which the forward's second kernel posted long ago); a count beyond the
@@ -989,16 +909,12 @@ int raster_resolve_deferred(const char *what, int token, hipStream_t s, uint32_t
 
 extern "C" void r2_tile_first_stats(long long *out, int reset)
 {
-    std::atomic<long long> *c[5] = {&r2::g_tf_taken, &r2::g_tf_declined, &r2::g_tf_rerun, &r2::g_tf_rerender, &r2::g_tf_seeded};
-    for (int i = 0; i < 5; ++i) {
-        if (out) out[i] = c[i]->load(std::memory_order_relaxed);
-        if (reset) c[i]->store(0, std::memory_order_relaxed);
-    }
+    r2::stats_read(r2::g_tf_stats, r2::TF_STATS, out, r2::TF_STATS, reset);
 }
 
 extern "C" void r2_defer_count_control(int mode)
 {
-    if (mode == 0 || mode == 1) r2::g_defer_mode.store(mode, std::memory_order_relaxed);
+    r2::g_defer_switch.set(mode);
 }
 
 extern "C" int r2_defer_count_resolve(int token, int *num_rendered, void *stream)
@@ -1016,15 +932,11 @@ extern "C" int r2_defer_count_resolve(int token, int *num_rendered, void *stream
 
 extern "C" void r2_defer_count_stats(long long *out, int reset)
 {
-    std::atomic<long long> *c[3] = {&r2::g_defer_taken, &r2::g_defer_no_slot, &r2::g_defer_short};
-    for (int i = 0; i < 3; ++i) {
-        if (out) out[i] = c[i]->load(std::memory_order_relaxed);
-        if (reset) c[i]->store(0, std::memory_order_relaxed);
-    }
+    r2::stats_read(r2::g_defer_stats, r2::DEFER_STATS, out, r2::DEFER_STATS, reset);
 }
 
 extern "C" void r2_tile_first_control(int mode)
 {
-    if (mode == 0 || mode == 1) r2::g_tf_mode.store(mode, std::memory_order_relaxed);
+    r2::g_tf_switch.set(mode);
     if (mode == 2) r2::g_tf_hints.clear();   // the calling thread's predictions
 }

@@ -2,6 +2,7 @@
 // Host orchestration of Voxelizer::forward / backward (VOX/voxelizer_impl.cu:171-389).
 #include "voxel_state.hpp"
 #include "dispatch.hpp"
+#include "chain_general.hpp"
 
 using namespace r2;
 
@@ -105,129 +106,47 @@ extern "C" int r2_voxel_forward_slab(
         path_count(choice.why);
     }
 
-    // binning, first half (see raster_api.hip): order of the Gaussians by the bits of world z (the reference's low sort
+    // binning, first half (chain_general.hpp): order of the Gaussians by the bits of world z (the reference's low sort
     // word, Q10) + instance offsets in that order; hinted / un-hinted bucket sort, radix fallback
-    int rc = depth_order_prepare(geom.dorder_temp, geom.dorder_bytes, (size_t)P, s);
-    if (rc) return rc;
     uint32_t *host_words = geom.host_words;
-    DepthHint hint;
-    const bool hinted = !preprocessed && depth_hint_lookup(1, (size_t)P, &hint);
-    const uint32_t pre_wgs = (uint32_t)((P + 255) / 256);
-    DepthReg reg{};
-    if (hinted) reg = depth_order_reg(geom.dorder_temp, (size_t)P, hint);
-    if (!preprocessed) {
-        StageScope t(ST_VOX_PREPROCESS, s);
-        launch_voxel_preprocess(geom, v, P, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, radii_x,
-                                radii_y, radii_z, reg, true, s);
-    }
-    R2_STAGE_CHECK(debug, s, "preprocess");
-    uint32_t hw[DW_COUNT] = { 0 };
-    if (hinted) {
-        uint32_t *mailbox = nullptr, mailbox_seq = 0;
-        rc = host_mailbox_arm(&mailbox, &mailbox_seq);
-        if (rc) return rc;
-        { StageScope t(ST_VOX_SCAN, s);
-        rc = depth_order_fast_scan(geom.dorder_temp, (size_t)P, pre_wgs, mailbox, mailbox_seq, s); }
-        if (rc) return rc;
-        { StageScope t(ST_VOX_DEPTHSORT, s);
-        rc = depth_order_fast_finish(geom.dorder_temp, (size_t)P, geom.depth_key, geom.tiles_touched, geom.order, geom.offsets, s); }
-        if (rc) return rc;
-        rc = host_mailbox_wait(mailbox_seq, hw, DW_COUNT, s);   // the GPU places + ranks while the host waits for the words
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "depth order (hinted)");
-    } else {
-        { StageScope t(ST_VOX_DEPTHSORT, s);
-        rc = depth_order_buckets(geom.dorder_temp, geom.dorder_bytes, geom.depth_key, geom.order, (size_t)P, s); }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "depth order");
-        { StageScope t(ST_VOX_SCAN, s);
-        rc = inclusive_scan_gather_u32(geom.scan_temp, geom.scan_bytes, geom.tiles_touched, geom.order, geom.offsets, P, s,
-                                       host_words + DW_TOTAL); }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "scan");
-        // total number of (tile, Gaussian) instances: sizes the binning state (the reference's D2H, VOX/voxelizer_impl.cu:248)
-        rc = read_host_words(host_words, hw, DW_COUNT, s);
-        if (rc) return rc;
-    }
-    uint32_t num_rendered = hw[DW_TOTAL];
-    const bool overflow = hw[DW_OVERFLOW] != 0;
-    bool full_order = !hinted;   // order / offsets cover all P Gaussians (else only the visible prefix)
-    if (overflow) {   // general radix sort instead
-        rc = sort_pairs_ex(geom.psort_temp, geom.psort_bytes, geom.depth_key, geom.depth_sorted, nullptr /* values = indices */, geom.order, nullptr,
-                           nullptr, (size_t)P, 32, /*allow_skip=*/true, nullptr, s);
-        if (!rc) rc = inclusive_scan_gather_u32(geom.scan_temp, geom.scan_bytes, geom.tiles_touched, geom.order, geom.offsets, P,
-                                                s, host_words + DW_TOTAL);
-        uint32_t total = 0;
-        if (!rc) rc = read_host_words(host_words + DW_TOTAL, &total, 1, s);
-        if (rc) return rc;
-        num_rendered = total;
-        full_order = true;
-        // `order` is now a permutation of ALL P ids (culled ones interleaved: their depth_key is bits(z), not a sentinel),
-        // but the dual scan left its visible count in the device word: the geometry backward would walk only that prefix
-        // and skip visible Gaussians sorted behind it.  0 = "walk all of it" (voxel_geom_backward_kernel).
-        R2_HIP_TRY(hipMemsetAsync(host_words + DW_NVIS, 0, sizeof(uint32_t), s));
-    }
-    depth_hint_update(1, (size_t)P, hw, overflow);
-    if (num_rendered > 0x7FFFFFFFu) {   // the API returns it as a non-negative int (like the reference's int num_rendered)
-        set_error("r2_voxel_forward: %u (tile, Gaussian) instances do not fit the 31-bit num_rendered", num_rendered);
-        return R2_ERR_INVALID;
-    }
-    const size_t R = num_rendered;
+    ChainOrder ord;
+    int rc = chain_depth_order(
+        CHAIN_VOXEL, "r2_voxel_forward", geom, P, VOXEL_STAGES,
+        [&](const DepthReg &reg) {
+            launch_voxel_preprocess(geom, v, P, means3D, scales, scale_modifier, rotations, opacities, cov3D_precomp, radii_x,
+                                    radii_y, radii_z, reg, true, s);
+        },
+        /*skip_preprocess=*/preprocessed, /*rects_allowed=*/false, /*reset_nvis_on_overflow=*/true, debug, s, &ord);
+    if (rc) return rc;
+    const size_t R = ord.num_rendered;
 
-    char *bchunk = binningBuffer(VoxelBinning::carve(nullptr, R).bytes, binning_user);
-    char *ichunk = imageBuffer(VoxelImage::carve(nullptr, T, V, R, debug != 0, vox_chunk_for(v.gy, v.gz)).bytes, image_user);
-    if (!bchunk || !ichunk) {
-        set_error("r2_voxel_forward: binning/image allocation callback returned NULL");
-        return R2_ERR_ALLOC;
-    }
-    const VoxelBinning bin = VoxelBinning::carve(bchunk, R);
-    const VoxelImage img = VoxelImage::carve(ichunk, T, V, R, debug != 0, vox_chunk_for(v.gy, v.gz));
-    const uint32_t *tile_counts = nullptr;
-    bool work_built = false;   // ranges + work list already produced by the sort's last kernel
-    bool ranges_zeroed = false;   // img.ranges zero-filled by the duplicate kernel
-    if (R > 0) {
-        { StageScope t(ST_VOX_DUPLICATE, s);
-        const int bit0 = (int)higher_msb((uint32_t)(T > 1 ? T - 1 : 1));
-        ranges_zeroed = !sort_is_single_pass(bit0);   // the multi-pass path below builds the ranges with tile_ranges()
-        launch_voxel_duplicate(geom, bin, v, P, radii_x, radii_y, radii_z, full_order ? nullptr : host_words + DW_NVIS, s,
-                               ranges_zeroed ? img.ranges : nullptr, T); }
-        R2_STAGE_CHECK(debug, s, "duplicateWithKeys");
-        const int bit = (int)higher_msb((uint32_t)(T > 1 ? T - 1 : 1));   // bits of the largest tile id (the reference
-                                                                     // sorts getHigherMsb(T) bits: one more for T = 2^k)
-        { StageScope t(ST_VOX_SORT, s);
-        if (sort_is_single_pass(bit)) {   // block 0 of the sort's last kernel also builds tile ranges + work list
-            const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, vox_work_chunk(v.gy, v.gz), nullptr,
-                                 voxel_short_list_min(debug != 0)};
-            rc = sort_by_tile_single_pass(bin.sort_temp, bin.sort_bytes, bin.tiles_unsorted, bin.vals_unsorted, bin.point_list,
-                                          debug ? bin.inv : nullptr, R, bit, &tile_counts, s, &wo);   // inv: introspection only
-            work_built = true;
-        } else {   // > 4096 tiles (e.g. 256^3): general multi-pass sort of (tile, Gaussian id) pairs -- no permutation is
-                   // carried along: the backward recomputes an instance's emission index from the Gaussian's tile cube
-            rc = sort_pairs_ex(bin.sort_temp, bin.sort_bytes, bin.tiles_unsorted, bin.tiles, bin.vals_unsorted, bin.point_list,
-                               nullptr, nullptr, R, bit, false, nullptr, s);
-        } }
-        if (rc) return rc;
-        R2_STAGE_CHECK(debug, s, "sort");
-    }
-    { StageScope t(ST_VOX_RANGES, s);
-    if (work_built) {
-        // nothing to do
-    } else if (tile_counts) {
-        launch_ranges_and_work(tile_counts, (uint32_t)T, vox_work_chunk(v.gy, v.gz), img.ranges, img.chunk_base, img.work_tile, s,
-                               voxel_short_list_min(debug != 0));
-    } else {
-        rc = tile_ranges(bin.tiles, nullptr, nullptr, nullptr, R, img.ranges, T, s, ranges_zeroed);
-        if (rc) return rc;
-        launch_build_work(img.ranges, (uint32_t)T, vox_work_chunk(v.gy, v.gz), img.chunk_base, img.work_tile, img.work_temp, s,
-                          voxel_short_list_min(debug != 0));
-    } }
-    R2_STAGE_CHECK(debug, s, "identifyTileRanges");
+    VoxelBinning bin{};
+    VoxelImage img{};
+    rc = chain_state("r2_voxel_forward", binningBuffer, binning_user, imageBuffer, image_user, R,
+                     [&](char *chunk) { return VoxelImage::carve(chunk, T, V, R, debug != 0, vox_chunk_for(v.gy, v.gz)); }, &bin, &img);
+    if (rc) return rc;
+    // second half; single-pass sort: block 0 of its last kernel also builds tile ranges + work list
+    const WorkListOut wo{img.ranges, img.chunk_base, img.work_tile, (uint32_t)T, vox_work_chunk(v.gy, v.gz), nullptr,
+                         voxel_short_list_min(debug != 0)};
+    // > 4096 tiles (e.g. 256^3): general multi-pass sort of (tile, Gaussian id) pairs -- no permutation is carried along: the
+    // backward recomputes an instance's emission index from the Gaussian's tile cube
+    const ChainMultiPass mp{bin.vals_unsorted, bin.point_list, nullptr, nullptr, nullptr};
+    ChainLists lists;
+    rc = chain_tile_lists(
+        bin, img, R, T, VOXEL_STAGES,
+        [&](int, bool ranges_zeroed) {
+            launch_voxel_duplicate(geom, bin, v, P, radii_x, radii_y, radii_z, ord.full_order ? nullptr : host_words + DW_NVIS, s,
+                                   ranges_zeroed ? img.ranges : nullptr, T);
+            return false;
+        },
+        wo, mp, /*zero_ranges_in_duplicate=*/true, debug, s, &lists);
+    if (rc) return rc;
     { StageScope t(ST_VOX_RENDER_FWD, s);
     launch_voxel_render_forward(geom, bin, img, v, out_volume, debug != 0, s); }
     R2_STAGE_CHECK(debug, s, "render");
     if (R > 0 && voxel_forward_fills_tiles(T)) fill_tiles_from_ranges(img.ranges, T, bin.tiles, s);   // see voxel_state.hpp
     host_mark_forward_end();
-    return (int)num_rendered;
+    return (int)ord.num_rendered;
 }
 
 extern "C" int r2_voxel_backward(

@@ -18,6 +18,8 @@
 // temp sizes) send the call back to the general path.
 #include "voxel_state.hpp"
 #include "dispatch.hpp"
+#include "chain_general.hpp"
+#include "device_blocks.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -238,86 +240,22 @@ __global__ void __launch_bounds__(SL_THREADS) voxel_small_lists_kernel(
                                                             tmp.cap_work});
 }
 
-// one 64-byte device word per host thread: the survivor / row counter of the small-grid preprocess, zero between calls
 // The two persistent counters of the path ({done | survivors | rows} of the preprocess, `arrivals` of the lists kernel) are
-// self-resetting, so they must not be shared by two calls in flight: one 64-byte block per (host thread, device, stream), kept
-// for the life of the thread (a thread that alternates devices or streams finds its block again instead of allocating).
-// one 64-byte counter block per (host thread, device, stream), owned by the thread: freed when it exits or on
-// r2_thread_release(); a thread that cycles through more streams than the table holds evicts the least recently used entry
-// (round 4: never freed, and the path switched itself off for the thread after 256 streams -- ADVICE r4)
-// dirty: a chain armed the block's counters and has not yet seen them reset by its own kernels (set before the first kernel that
-// bumps them, cleared after the host has read the totals): found dirty by the next call -- one that aborted half way -- the block is
-// zero-filled first (the stick chain's counters had no such recovery)
-struct SmallCounter { int dev; hipStream_t stream; unsigned long long *ptr; unsigned long long used; bool dirty; };
-struct SmallCounters {
-    std::vector<SmallCounter> v;
-    unsigned long long tick = 0;
-    static void free_one(const SmallCounter &c)
-    {
-        int cur = 0;
-        if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (cur != c.dev && hipSetDevice(c.dev) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (hipFree(c.ptr) != hipSuccess) (void)hipGetLastError();   // (waits for the device: its last call may still run)
-        if (cur != c.dev) (void)hipSetDevice(cur);
-    }
-    void release()
-    {
-        for (const SmallCounter &c : v) free_one(c);
-        v.clear();
-    }
-    ~SmallCounters() { release(); }
-};
-thread_local SmallCounters g_small_counters;
-constexpr size_t SMALL_MAX_COUNTERS = 16;
-
-unsigned long long *small_counter_for(int dev, hipStream_t s)
-{
-    SmallCounters &t = g_small_counters;
-    ++t.tick;
-    for (SmallCounter &c : t.v)
-        if (c.dev == dev && c.stream == s) {
-            c.used = t.tick;
-            if (c.dirty) {
-                if (hipMemsetAsync(c.ptr, 0, 64, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            }
-            c.dirty = true;   // until voxel_counter_block_clean()
-            return c.ptr;
-        }
-    if (t.v.size() >= SMALL_MAX_COUNTERS) {
-        size_t lru = 0;
-        for (size_t i = 1; i < t.v.size(); ++i)
-            if (t.v[i].used < t.v[lru].used) lru = i;
-        SmallCounters::free_one(t.v[lru]);
-        t.v.erase(t.v.begin() + (long)lru);
-    }
-    unsigned long long *p = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&p), 64) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (hipMemsetAsync(p, 0, 64, s) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(p);
-        return nullptr;
-    }
-    t.v.push_back(SmallCounter{dev, s, p, t.tick, true});
-    return p;
-}
+// self-resetting, so they must not be shared by two calls in flight: one 64-byte block per (host thread, device, stream) --
+// device_blocks.hpp -- shared with the stick-first chain (voxel_sticks.hip: VSCounters).  Dirty from the first kernel that bumps the
+// counters until the host has read the totals.
+thread_local DeviceBlocks g_voxel_blocks;
+EnvSwitch g_small_switch("R2_VOXEL_SMALL", true);   // R2_VOXEL_SMALL=0: off
 
 }  // namespace
 
-// the calling thread's block for (dev, s) has been through a whole call: its kernels have put the zeros back
-void voxel_counter_block_clean(int dev, hipStream_t s)
+unsigned long long *voxel_small_counter_block(int dev, hipStream_t s)
 {
-    for (SmallCounter &c : g_small_counters.v)
-        if (c.dev == dev && c.stream == s) c.dirty = false;
+    return static_cast<unsigned long long *>(g_voxel_blocks.acquire(dev, s, 64));
 }
+void voxel_counter_block_clean(int dev, hipStream_t s) { g_voxel_blocks.clean(dev, s); }
 
-bool voxel_small_switched_on()
-{
-    static const bool on = [] { const char *e = getenv("R2_VOXEL_SMALL"); return !(e && e[0] == '0'); }();   // R2_VOXEL_SMALL=0: off
-    return on;
-}
+bool voxel_small_switched_on() { return g_small_switch.on(); }
 bool voxel_small_lds_ok()
 {
     // more than 64 KB of LDS per workgroup (gfx950: 160 KB per CU) has to be asked for
@@ -339,7 +277,7 @@ int voxel_forward_small(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc_
     // (whether a call comes here at all: voxel_forward_choice, dispatch.hpp)
     int dev = 0;
     R2_HIP_TRY(hipGetDevice(&dev));
-    unsigned long long *const g_small_counter = small_counter_for(dev, s);
+    unsigned long long *const g_small_counter = voxel_small_counter_block(dev, s);
     if (!g_small_counter) {
         path_count(PS_VOX_GENERAL_NO_WORKSPACE);
         return VOX_SMALL_NOT_TAKEN;
@@ -363,10 +301,8 @@ int voxel_forward_small(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc_
     if (rc) return rc;
     const uint32_t num_rendered = hw[DW_TOTAL], nsurv = hw[DW_NVIS];
     const size_t R = num_rendered;
-    if (num_rendered > 0x7FFFFFFFu) {
-        set_error("r2_voxel_forward: %u (tile, Gaussian) instances do not fit the 31-bit num_rendered", num_rendered);
-        return R2_ERR_INVALID;
-    }
+    rc = check_num_rendered(CHAIN_VOXEL, "r2_voxel_forward", num_rendered);
+    if (rc) return rc;
     const size_t NW = R / vox_chunk_for(v.gy, v.gz) + T;
     // rare (a patch that most Gaussians reach): the general path; the kernel above has seen the same totals and done nothing
     voxel_counter_block_clean(dev, s);   // (the preprocess's last workgroup has reset the counter; the lists kernel resets its own)
@@ -375,14 +311,11 @@ int voxel_forward_small(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc_
         return VOX_SMALL_NOT_TAKEN;
     }
     path_count(PS_VOX_SMALL_GRID);
-    char *bchunk = binningBuffer(VoxelBinning::carve(nullptr, R).bytes, binning_user);
-    char *ichunk = imageBuffer(VoxelImage::carve(nullptr, T, V, R, false, vox_chunk_for(v.gy, v.gz)).bytes, image_user);
-    if (!bchunk || !ichunk) {
-        set_error("r2_voxel_forward: binning/image allocation callback returned NULL");
-        return R2_ERR_ALLOC;
-    }
-    const VoxelBinning bin = VoxelBinning::carve(bchunk, R);
-    const VoxelImage img = VoxelImage::carve(ichunk, T, V, R, false, vox_chunk_for(v.gy, v.gz));
+    VoxelBinning bin{};
+    VoxelImage img{};
+    rc = chain_state("r2_voxel_forward", binningBuffer, binning_user, imageBuffer, image_user, R,
+                     [&](char *chunk) { return VoxelImage::carve(chunk, T, V, R, false, vox_chunk_for(v.gy, v.gz)); }, &bin, &img);
+    if (rc) return rc;
     { StageScope t(ST_VOX_RENDER_FWD, s);
     VoxelBinning b2 = bin;          // the render kernels read the lists where they were built ...
     VoxelImage i2 = img;
@@ -399,8 +332,6 @@ int voxel_forward_small(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc_
     return (int)num_rendered;
 }
 
-void voxel_small_release() { g_small_counters.release(); }
-
-unsigned long long *voxel_small_counter_block(int dev, hipStream_t s) { return small_counter_for(dev, s); }
+void voxel_small_release() { g_voxel_blocks.release(); }
 
 }  // namespace r2

@@ -37,8 +37,11 @@
 //     6. launch_build_work (binning.hip)             the render kernel's work list from the ranges, as in the general chain
 #include "voxel_state.hpp"
 #include "dispatch.hpp"
+#include "chain_general.hpp"
+#include "host_tables.hpp"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstdlib>
 #include <vector>
@@ -710,9 +713,9 @@ __global__ void __launch_bounds__(VSK_THREADS, 8) vox_stick_sort_kernel(
 // what the thread has learnt about a (P, grid): a stick list too long for the sort kernel -> the general chain from then on
 // The note ages: after VS_NOTE_RETRY declined calls the chain is tried again -- the cloud behind a (P, grid) changes
 // while it trains -- and r2_voxel_sticks_limits drops every thread's notes (a process-wide epoch).
-struct VSNote { int P, nx, ny, nz; bool bad; unsigned long long used; uint32_t declined; };
-thread_local std::vector<VSNote> g_vs_notes;
-thread_local unsigned long long g_vs_tick = 0;
+struct VSNote { bool bad; uint32_t declined; };
+using VSNotes = LruTable<std::array<int, 4>, VSNote, 32>;   // by {P, nx, ny, nz}
+thread_local VSNotes g_vs_notes;
 thread_local int g_vs_notes_epoch = 0;
 std::atomic<int> g_vs_epoch{0};
 constexpr uint32_t VS_NOTE_RETRY = 64;
@@ -723,41 +726,22 @@ VSNote *vs_note(int P, const VoxelGrid &v, bool create)
         g_vs_notes.clear();
         g_vs_notes_epoch = e;
     }
-    for (VSNote &n : g_vs_notes)
-        if (n.P == P && n.nx == v.nx && n.ny == v.ny && n.nz == v.nz) { n.used = ++g_vs_tick; return &n; }
-    if (!create) return nullptr;
-    if (g_vs_notes.size() >= 32) {
-        size_t lru = 0;
-        for (size_t i = 1; i < g_vs_notes.size(); ++i)
-            if (g_vs_notes[i].used < g_vs_notes[lru].used) lru = i;
-        g_vs_notes.erase(g_vs_notes.begin() + (long)lru);
-    }
-    g_vs_notes.push_back(VSNote{P, v.nx, v.ny, v.nz, false, ++g_vs_tick, 0u});
-    return &g_vs_notes.back();
+    const std::array<int, 4> key{P, v.nx, v.ny, v.nz};
+    return create ? g_vs_notes.find_or_insert(key) : g_vs_notes.find(key);
 }
 
 // forwards that took the chain, forwards that left it after the scan (a list too long), forwards it declined
-std::atomic<long long> g_vs_taken{0}, g_vs_fallback{0}, g_vs_declined{0};
+enum { VS_TAKEN = 0, VS_FALLBACK, VS_DECLINED, VS_STATS };
+std::atomic<long long> g_vs_stats[VS_STATS];
 // a call whose longest list exceeds the first AND whose instances exceed the second goes to the general chain (r2_voxel_sticks_limits)
 constexpr long long VS_LONG_LIST = 4 * 5120, VS_LONG_SCENE = 8ll << 20;
 std::atomic<long long> g_vs_long_list{VS_LONG_LIST}, g_vs_long_scene{VS_LONG_SCENE};
 std::atomic<int> g_vs_no_parts{0};   // tests: treat a list beyond one workgroup's capacity as unsupported (the fallback's path)
-std::atomic<int> g_vs_mode{-1};   // -1: not decided yet (environment), 0: off, 1: every grid it can serve
-
-int vs_mode()
-{
-    int m = g_vs_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char *e = getenv("R2_VOXEL_STICKS");
-        m = (e && e[0] == '0') ? 0 : 1;
-        g_vs_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+EnvSwitch g_vs_switch("R2_VOXEL_STICKS", true);   // on: every grid the chain can serve
 
 }  // namespace
 
-bool voxel_sticks_switched_on() { return vs_mode() != 0; }
+bool voxel_sticks_switched_on() { return g_vs_switch.on(); }
 
 // The sort kernel needs VSK_LDS = 77.8 KB of dynamic LDS per workgroup: a device whose opt-in limit is below that (64 KB parts)
 // cannot run the chain -- voxel_forward_choice then reports voxel.general.device_lds (r2_path_stats) and the general chain serves.
@@ -783,7 +767,7 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
     if (VSNote *n = vs_note(P, v, false); n && n->bad) {
         if (++n->declined < VS_NOTE_RETRY) {
             path_count(PS_VOX_GENERAL_REMEMBERED);
-            g_vs_declined.fetch_add(1, std::memory_order_relaxed);
+            g_vs_stats[VS_DECLINED].fetch_add(1, std::memory_order_relaxed);
             return VOX_STICKS_NOT_TAKEN;
         }
         n->bad = false;   // try again: the cloud behind this (P, grid) may have changed
@@ -800,7 +784,7 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
     VSCounters *ctr = reinterpret_cast<VSCounters *>(voxel_small_counter_block(dev, s));   // (zero-filled first if a call left it dirty)
     if (!ctr) {
         path_count(PS_VOX_GENERAL_NO_WORKSPACE);
-        g_vs_declined.fetch_add(1, std::memory_order_relaxed);
+        g_vs_stats[VS_DECLINED].fetch_add(1, std::memory_order_relaxed);
         return VOX_STICKS_NOT_TAKEN;
     }
     uint32_t *nparts = st.ctr;
@@ -827,10 +811,8 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
     if (rc) return rc;
     voxel_counter_block_clean(dev, s);   // the scan's last workgroup has posted the totals and put the zeros back
     const uint32_t num_rendered = hw[DW_TOTAL], longest = hw[DW_PMAX];
-    if (num_rendered > 0x7FFFFFFFu) {
-        set_error("r2_voxel_forward: %u (tile, Gaussian) instances do not fit the 31-bit num_rendered", num_rendered);
-        return R2_ERR_INVALID;
-    }
+    rc = check_num_rendered(CHAIN_VOXEL, "r2_voxel_forward", num_rendered);
+    if (rc) return rc;
     // lists beyond one workgroup's capacity are sorted in parts: at most NL + R / VSK_BIG_TARGET descriptors of long lists.  More
     // than the state holds (Gaussians of hundreds of tiles each): the general chain, from here and from now on
     const size_t parts_bound = (size_t)NL + (size_t)num_rendered / VSK_BIG_TARGET + 1;
@@ -848,18 +830,15 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
         n->bad = true;
         n->declined = 0u;
         path_count(PS_VOX_GENERAL_LONG_LISTS);
-        g_vs_fallback.fetch_add(1, std::memory_order_relaxed);
+        g_vs_stats[VS_FALLBACK].fetch_add(1, std::memory_order_relaxed);
         return VOX_STICKS_FALLBACK;
     }
     const size_t R = num_rendered;
-    char *bchunk = binningBuffer(VoxelBinning::carve(nullptr, R).bytes, binning_user);
-    char *ichunk = imageBuffer(VoxelImage::carve(nullptr, T, V, R, false, vox_chunk_for(v.gy, v.gz)).bytes, image_user);
-    if (!bchunk || !ichunk) {
-        set_error("r2_voxel_forward: binning/image allocation callback returned NULL");
-        return R2_ERR_ALLOC;
-    }
-    const VoxelBinning bin = VoxelBinning::carve(bchunk, R);
-    const VoxelImage img = VoxelImage::carve(ichunk, T, V, R, false, vox_chunk_for(v.gy, v.gz));
+    VoxelBinning bin{};
+    VoxelImage img{};
+    rc = chain_state("r2_voxel_forward", binningBuffer, binning_user, imageBuffer, image_user, R,
+                     [&](char *chunk) { return VoxelImage::carve(chunk, T, V, R, false, vox_chunk_for(v.gy, v.gz)); }, &bin, &img);
+    if (rc) return rc;
     uint2 *pairs = reinterpret_cast<uint2 *>(bin.part);   // the backward's moment scratch (48 bytes per instance), free until then
     // the render kernel's work list: for more than 4096 tiles the sort kernel leaves the work items per block of tiles behind
     // (one launch of the construction instead of two)
@@ -894,7 +873,7 @@ int voxel_forward_sticks(r2_alloc_fn binningBuffer, void *binning_user, r2_alloc
     { StageScope t(ST_VOX_RENDER_FWD, s);
     launch_voxel_render_forward(geom, bin, img, v, out_volume, false, s); }
     R2_HIP_TRY(hipGetLastError());
-    g_vs_taken.fetch_add(1, std::memory_order_relaxed);
+    g_vs_stats[VS_TAKEN].fetch_add(1, std::memory_order_relaxed);
     path_count(PS_VOX_STICK_FIRST);
     return (int)num_rendered;
 }
@@ -905,11 +884,7 @@ void voxel_sticks_release() { g_vs_notes.clear(); }
 
 extern "C" void r2_voxel_sticks_stats(long long *out, int reset)
 {
-    std::atomic<long long> *c[3] = {&r2::g_vs_taken, &r2::g_vs_fallback, &r2::g_vs_declined};
-    for (int i = 0; i < 3; ++i) {
-        if (out) out[i] = c[i]->load(std::memory_order_relaxed);
-        if (reset) c[i]->store(0, std::memory_order_relaxed);
-    }
+    r2::stats_read(r2::g_vs_stats, r2::VS_STATS, out, r2::VS_STATS, reset);
 }
 
 extern "C" void r2_voxel_sticks_limits(long long longest_list, long long instances)
@@ -921,7 +896,7 @@ extern "C" void r2_voxel_sticks_limits(long long longest_list, long long instanc
 
 extern "C" void r2_voxel_sticks_control(int mode)
 {
-    if (mode == 0 || mode == 1) r2::g_vs_mode.store(mode, std::memory_order_relaxed);
+    r2::g_vs_switch.set(mode);
     if (mode == 3) r2::g_vs_notes.clear();   // the calling thread's notes
     if (mode == 4 || mode == 5) r2::g_vs_no_parts.store(mode == 4 ? 1 : 0, std::memory_order_relaxed);   // tests
 }
