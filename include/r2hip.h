@@ -366,6 +366,68 @@ R2_API int r2_knn_dist2_ws(int P, const float *points /* [P,3] */, float *out /*
  * point of the library that allocates; callers with an allocator use the two above */
 R2_API int r2_knn_dist2(int P, const float *points /* [P,3] */, float *out /* [P] */, void *stream);
 
+/* ---- neighbour graphs and the smoothness loss (no counterpart in the reference) -------------- */
+/* r2_knn_graph: the K nearest neighbours of every point, with their indices.
+ *   Distance: formed as r2_knn_dist2 forms it, in float32 without contraction: d = other - self per axis, then
+ *     (dx*dx + dy*dy) + dz*dz, every operation rounded.
+ *   Neighbours of i: all j != i (self excluded by INDEX; a duplicate of i at distance 0 counts), ordered by the pair
+ *     (dist2 ascending, j ascending).  Row i of idx / dist2 holds the first K of that order, dist2 next to idx.
+ *   The pair is a total order, so the rows do not depend on the order the search visits candidates in: the grid search, the
+ *     exhaustive search and every hand-over between them (small P, degenerate or clustered clouds) produce the same bits.
+ *   Short rows: where P - 1 < K the missing slots are idx = -1, dist2 = +inf.
+ *   Arguments: 1 <= K <= R2_KNN_GRAPH_MAX_K, anything else is R2_ERR_INVALID (checked first); P = 0 is a no-op returning 0;
+ *     P < 0, a NULL points / idx / dist2 or P * K >= 2^31: R2_ERR_INVALID.  The workspace rule is r2_knn_dist2_ws's: with
+ *     r2_knn_graph_workspace_bytes(P, K) bytes (alignment >= 256 B) the grid search may run (P >= 4096), with NULL or fewer
+ *     bytes the exhaustive kernel runs, which needs none.  With a workspace the call synchronises the stream twice.
+ *   Non-finite coordinates: a cloud with a NaN or infinite coordinate takes the exhaustive search.  Guaranteed then: nothing
+ *     outside the inputs is read, every idx is in [-1, P), rows are ascending in (dist2, idx) and the same on every call.  A
+ *     NaN distance is never listed (its slot stays -1 / +inf); a distance that overflowed to +inf is listed like any other.
+ * r2_graph_transpose: the incoming edges of every node in a fixed order.  An edge is e = i * K + k with target idx[e]; a
+ *   target outside [0, P) (-1 included) makes the edge invalid.  in_edges[in_offsets[j] .. in_offsets[j + 1]) are the valid
+ *   edges whose target is j, in ascending e; in_offsets[P] is the number of valid edges; the tail of in_edges [P * K] beyond
+ *   that is unspecified.  Any idx is accepted, not only one from r2_knn_graph.  A stable radix sort of the edge ids by target
+ *   and a binary search per node: no host read, no atomic.  P = 0 writes in_offsets[0] = 0.  P > 0 needs
+ *   r2_graph_transpose_workspace_bytes(P, K) bytes (alignment >= 256 B), else R2_ERR_INVALID; K >= 1, P * K < 2^31.
+ * r2_graph_loss: for per-node scalars v [P] and optional edge weights w [P,K] (NULL = 1),
+ *     loss[0] = scale * sum over valid edges e = (i, k), j = idx[e], of w[e] * phi(v[i] - v[j]),
+ *   phi(x) = |x| (R2_GRAPH_KIND_L1), x * x (R2_GRAPH_KIND_L2) or Huber with delta > 0 (R2_GRAPH_KIND_HUBER):
+ *   0.5 * (x * x) for |x| <= delta, else delta * (|x| - 0.5 * delta).  Per term, in float32 without contraction:
+ *   x = v[i] - v[j]; phi as written; then w[e] * phi when w is given.  The reduction has a fixed shape whatever P and K:
+ *   workgroup b of 256 threads owns edges [2048 b, 2048 b + 2048), thread t adds its terms 2048 b + 256 k + t, k = 0 .. 7,
+ *   in that order, a wave folds by xor butterfly (offsets 32 .. 1), the four waves combine as (s0 + s1) + (s2 + s3); the
+ *   workgroups' partials (scratch: r2_graph_loss_scratch_floats(P, K) floats) are summed in double in a fixed order,
+ *   multiplied by scale and rounded to float once.  R2_GRAPH_LOSS_CHAIN = 8 + 6 + 2 + 1 is the longest chain of float
+ *   roundings between a term and the result; the same bits on every call.
+ * r2_graph_loss_backward: with in_offsets / in_edges of r2_graph_transpose on the same idx and the upstream scalar g[0] (a
+ *   device pointer),
+ *     grad[i] = (g * scale) * ( sum_k w[i,k] phi'(v[i] - v[idx[i,k]])  -  sum over incoming e = (s, k) of w[e] phi'(v[s] - v[i]) ),
+ *   phi'(x) = sign(x) with phi'(0) = 0, taken from the comparison of the two values (L1); 2 * x (L2); x for |x| <= delta,
+ *   else delta with the sign of x (Huber).  One accumulator per node, starting at 0: the own row added in ascending k, then
+ *   the incoming terms subtracted in list order; g * scale is formed first and multiplies the sum.  A node with more than
+ *   R2_GRAPH_LOSS_HUB incoming edges has its list summed by its wave instead: lane l adds entries l, l + 64, ... of the list
+ *   in that order, the 64 sums fold by xor butterfly (offsets 32 .. 1) and the result is subtracted from the own-row sum.
+ *   Either order is a function of the lists alone: no atomics, bit-reproducible.  A node without valid edges gets +0.
+ *   Differentiable in v only: the graph and the weights are structure.  kind outside 0..2, Huber with delta <= 0 (or NaN),
+ *   K < 1, P < 0, P * K >= 2^31 or a NULL array with P > 0: R2_ERR_INVALID.  Targets outside [0, P) are skipped. */
+#define R2_KNN_GRAPH_MAX_K 16
+#define R2_GRAPH_KIND_L1 0
+#define R2_GRAPH_KIND_L2 1
+#define R2_GRAPH_KIND_HUBER 2
+#define R2_GRAPH_LOSS_CHAIN 17
+#define R2_GRAPH_LOSS_HUB 64
+R2_API size_t r2_knn_graph_workspace_bytes(int P, int K);
+R2_API int r2_knn_graph(int P, const float *points /* [P,3] */, int K, int *idx /* [P,K] */, float *dist2 /* [P,K] */,
+                        void *workspace, size_t workspace_bytes, void *stream);
+R2_API size_t r2_graph_transpose_workspace_bytes(int P, int K);
+R2_API int r2_graph_transpose(int P, int K, const int *idx /* [P,K] */, int *in_offsets /* [P+1] */, int *in_edges /* [P*K] */,
+                              void *workspace, size_t workspace_bytes, void *stream);
+R2_API size_t r2_graph_loss_scratch_floats(int P, int K);
+R2_API int r2_graph_loss(int P, int K, const float *v /* [P] */, const int *idx /* [P,K] */, const float *w /* [P,K] or NULL */,
+                         int kind, float delta, float scale, float *scratch, float *loss /* [1] */, void *stream);
+R2_API int r2_graph_loss_backward(int P, int K, const float *v, const int *idx, const float *w, const int *in_offsets,
+                                  const int *in_edges, int kind, float delta, float scale, const float *g /* device scalar */,
+                                  float *grad /* [P] */, void *stream);
+
 /* ---- measurement: per-stage HIP-event timing on the caller's stream ---------------------------- */
 /* bit i of stage_mask enables stage i (0 = off, the default: no events are recorded).  Enabled stages are
  * bracketed by hipEventRecord on the stream they are launched on; r2_profile_read synchronises the recorded

@@ -18,6 +18,10 @@ R2_ERR_ALLOC = -10002
 R2_METRIC_SSIM = 1
 R2_METRIC_NORMALIZE = 2
 R2_LOSS_BATCH_CHUNK = 16
+R2_KNN_GRAPH_MAX_K = 16
+R2_GRAPH_KIND_L1, R2_GRAPH_KIND_L2, R2_GRAPH_KIND_HUBER = 0, 1, 2
+R2_GRAPH_LOSS_CHAIN = 17   # longest chain of float roundings in r2_graph_loss's reduction (include/r2hip.h)
+R2_GRAPH_LOSS_HUB = 64     # incoming lists longer than this are summed by a whole wave in r2_graph_loss_backward
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -44,6 +48,13 @@ _SIGNATURES = {
     "r2_knn_dist2": (C.c_int, [_i, _fp, _fp, _p]),
     "r2_knn_workspace_bytes": (C.c_size_t, [_i]),
     "r2_knn_dist2_ws": (C.c_int, [_i, _fp, _fp, _p, C.c_size_t, _p]),
+    "r2_knn_graph_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "r2_knn_graph": (C.c_int, [_i, _fp, _i, _p, _fp, _p, C.c_size_t, _p]),
+    "r2_graph_transpose_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "r2_graph_transpose": (C.c_int, [_i, _i, _p, _p, _p, _p, C.c_size_t, _p]),
+    "r2_graph_loss_scratch_floats": (C.c_size_t, [_i, _i]),
+    "r2_graph_loss": (C.c_int, [_i, _i, _fp, _p, _fp, _i, _f, _f, _fp, _fp, _p]),
+    "r2_graph_loss_backward": (C.c_int, [_i, _i, _fp, _p, _fp, _p, _p, _i, _f, _f, _fp, _fp, _p]),
     "r2_tile_first_stats": (None, [C.POINTER(C.c_longlong), _i]),
     "r2_defer_count_control": (None, [_i]),
     "r2_defer_count_resolve": (C.c_int, [_i, C.POINTER(C.c_int), _p]),

@@ -40,6 +40,8 @@ SOURCES = {
     "voxel_small.hip": FAST,
     "voxel_sticks.hip": FAST,
     "knn.hip": EXACT,
+    # EXACT: the per-term operation order is the one include/r2hip.h states and tests/graph_ref.py bounds
+    "graph_loss.hip": EXACT,
     "loss_ops.hip": FAST,
     "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,

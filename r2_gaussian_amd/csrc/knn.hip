@@ -9,6 +9,7 @@
 // LDS broadcast reads), 3-best kept in registers.  It runs once per training run (P = 50k: 2.5e9 pairs).
 // Compiled with -ffp-contract=off so dx*dx+dy*dy+dz*dz rounds exactly like the oracle; the 3-best
 // multiset does not depend on the visiting order, so the result is bit-exact.
+// r2_knn_graph (further down) runs the same two searches and keeps the K nearest WITH their indices.
 #include "r2_common.hpp"
 #include <float.h>
 
@@ -215,6 +216,156 @@ __global__ void __launch_bounds__(256) knn_query_kernel(int P, KnnGrid g, const 
     out[self] = (b0 + b1 + b2) / 3.0f;
 }
 
+
+// ---- k-NN graph (r2_knn_graph): the K nearest neighbours of every point WITH their indices.  Same two searches, same
+// distance; what changes is the list.  Neighbours are ordered by the pair (dist2, index), a total order, so the K first of
+// them do not depend on the order the candidates are visited in: grid search, exhaustive search and the hand-over between
+// them give the same bits (tests/test_knn_graph_gpu.py).  The list lives in registers, KB = 4 / 8 / 16 slots (template
+// parameter) kept ascending; a call with K < KB fills the FIRST KB - K slots with a pair smaller than every candidate
+// (-1, 0: distances are >= 0 or NaN), which never moves, so that the K-th best always is slot KB - 1 -- no register array
+// is indexed by a run-time value.  Free slots hold (+inf, 0xFFFFFFFF): indices compare as unsigned, so a candidate at
+// distance +inf (overflow) still enters, and a slot nobody claimed is written out as idx = -1, dist2 = +inf.  A NaN distance
+// compares false both ways and is never listed.
+__device__ __forceinline__ bool knn_pair_less(float d, uint32_t j, float bd, uint32_t bj) { return d < bd || (d == bd && j < bj); }
+
+template <int KB>
+__device__ __forceinline__ void knn_list_init(float (&bd)[KB], uint32_t (&bj)[KB], int K)
+{
+#pragma unroll
+    for (int s = 0; s < KB; ++s) {
+        const bool pad = s < KB - K;
+        bd[s] = pad ? -1.0f : INFINITY;
+        bj[s] = pad ? 0u : 0xFFFFFFFFu;
+    }
+}
+
+template <int KB>
+__device__ __forceinline__ void knn_list_insert(float (&bd)[KB], uint32_t (&bj)[KB], float d, uint32_t j)
+{
+    if (!knn_pair_less(d, j, bd[KB - 1], bj[KB - 1])) return;   // (almost every candidate once the list has warmed up)
+    // top down, so that slot s - 1 still holds its old pair when slot s takes it
+#pragma unroll
+    for (int s = KB - 1; s >= 1; --s) {
+        const bool below = knn_pair_less(d, j, bd[s - 1], bj[s - 1]), here = knn_pair_less(d, j, bd[s], bj[s]);
+        bd[s] = below ? bd[s - 1] : (here ? d : bd[s]);
+        bj[s] = below ? bj[s - 1] : (here ? j : bj[s]);
+    }
+    const bool first = knn_pair_less(d, j, bd[0], bj[0]);
+    bd[0] = first ? d : bd[0];
+    bj[0] = first ? j : bj[0];
+}
+
+template <int KB>
+__device__ __forceinline__ void knn_list_store(const float (&bd)[KB], const uint32_t (&bj)[KB], int K, size_t row,
+                                               int *__restrict__ idx, float *__restrict__ dist2)
+{
+#pragma unroll
+    for (int s = 0; s < KB; ++s) {
+        const int k = s - (KB - K);
+        if (k >= 0) {
+            idx[row * (size_t)K + k] = (int)bj[s];
+            dist2[row * (size_t)K + k] = bd[s];
+        }
+    }
+}
+
+// exhaustive: knn_dist2_kernel's tiling, candidates in ascending index
+template <int KB>
+__global__ void __launch_bounds__(256) knn_graph_exhaustive_kernel(int P, int K, const float *__restrict__ pts, int *__restrict__ idx,
+                                                                   float *__restrict__ dist2)
+{
+    __shared__ float4 tile[KNN_TILE];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    if (i < P) {
+        rx = pts[3 * (size_t)i];
+        ry = pts[3 * (size_t)i + 1];
+        rz = pts[3 * (size_t)i + 2];
+    }
+    float bd[KB];
+    uint32_t bj[KB];
+    knn_list_init<KB>(bd, bj, K);
+    for (int base = 0; base < P; base += KNN_TILE) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < KNN_TILE; t += 256) {
+            const int j = base + t;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j < P) v = make_float4(pts[3 * (size_t)j], pts[3 * (size_t)j + 1], pts[3 * (size_t)j + 2], 0.f);
+            tile[t] = v;
+        }
+        __syncthreads();
+        const int n = min(KNN_TILE, P - base);
+        for (int t = 0; t < n; ++t) {
+            const float4 v = tile[t];
+            const float dx = v.x - rx, dy = v.y - ry, dz = v.z - rz;
+            const float d = dx * dx + dy * dy + dz * dz;
+            if (base + t != i) knn_list_insert<KB>(bd, bj, d, (uint32_t)(base + t));   // self excluded by index
+        }
+    }
+    if (i < P) knn_list_store<KB>(bd, bj, K, (size_t)i, idx, dist2);
+}
+
+// grid: knn_query_kernel's walk -- one lane per query in sorted-cell order, Chebyshev rings -- with the list above
+template <int KB>
+__global__ void __launch_bounds__(256) knn_graph_query_kernel(int P, int K, KnnGrid g, const uint32_t *__restrict__ incl,
+                                                              const float4 *__restrict__ sorted, int *__restrict__ idx,
+                                                              float *__restrict__ dist2)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const float4 q = sorted[i];
+    const uint32_t self = __float_as_uint(q.w);
+    const int3 c = knn_cell(g, q.x, q.y, q.z);
+    float bd[KB];
+    uint32_t bj[KB];
+    knn_list_init<KB>(bd, bj, K);
+    auto scan = [&](uint32_t j0, uint32_t j1) {
+        for (uint32_t j = j0; j < j1; ++j) {
+            const float4 v = sorted[j];
+            const float dx = v.x - q.x, dy = v.y - q.y, dz = v.z - q.z;
+            const float d = dx * dx + dy * dy + dz * dz;
+            const uint32_t id = __float_as_uint(v.w);
+            if (id != self) knn_list_insert<KB>(bd, bj, d, id);
+        }
+    };
+    const int rmax = max(g.gx, max(g.gy, g.gz));
+    for (int r = 0; r <= rmax; ++r) {
+        const int z0 = max(c.z - r, 0), z1 = min(c.z + r, g.gz - 1);
+        const int y0 = max(c.y - r, 0), y1 = min(c.y + r, g.gy - 1);
+        const int x0 = max(c.x - r, 0), x1 = min(c.x + r, g.gx - 1);
+        for (int z = z0; z <= z1; ++z)
+            for (int y = y0; y <= y1; ++y) {
+                const bool shell_zy = (z == c.z - r) || (z == c.z + r) || (y == c.y - r) || (y == c.y + r);
+                const size_t row = ((size_t)z * g.gy + y) * g.gx;
+                if (shell_zy) {   // the whole x-run of cells (contiguous in the sorted array)
+                    scan((row + x0) ? incl[row + x0 - 1] : 0u, incl[row + x1]);
+                } else {          // only the two end cells
+                    if (c.x - r >= 0) scan((row + c.x - r) ? incl[row + c.x - r - 1] : 0u, incl[row + c.x - r]);
+                    if (r != 0 && c.x + r < g.gx) scan(incl[row + c.x + r - 1], incl[row + c.x + r]);
+                }
+            }
+        // The stop test of knn_query_kernel with b2 replaced by the K-th best, bd[KB - 1] (+inf while the list is short: no stop).
+        // `reach` is derived there: every point of a cell outside the block [c - r, c + r]^3 lies, in exact arithmetic, farther
+        // than `reach` from the query along one axis, so its true squared distance exceeds reach^2, and its float distance (three
+        // squares and two sums, each rounded) is >= the true one * (1 - 2^-21) > reach^2 * (1 - 1e-6) >= bd[KB - 1].  STRICTLY
+        // farther than the K-th best: an unseen point can neither displace a listed one nor tie with it, so no unseen smaller
+        // index is missed and the list is the exhaustive search's, pair for pair.
+        const bool all = x0 == 0 && y0 == 0 && z0 == 0 && x1 == g.gx - 1 && y1 == g.gy - 1 && z1 == g.gz - 1;
+        if (all) break;
+        constexpr double EPS3 = 3.0 / 16777216.0;
+        const double ih = 1.0 / (double)g.inv_h;
+        double reach = 1.0e300;
+        if (c.x - r > 0) reach = fmin(reach, ((double)q.x - (double)g.ox) - (double)(c.x - r) * ih * (1.0 + EPS3));
+        if (c.x + r < g.gx - 1) reach = fmin(reach, (double)(c.x + r + 1) * ih * (1.0 - EPS3) - ((double)q.x - (double)g.ox));
+        if (c.y - r > 0) reach = fmin(reach, ((double)q.y - (double)g.oy) - (double)(c.y - r) * ih * (1.0 + EPS3));
+        if (c.y + r < g.gy - 1) reach = fmin(reach, (double)(c.y + r + 1) * ih * (1.0 - EPS3) - ((double)q.y - (double)g.oy));
+        if (c.z - r > 0) reach = fmin(reach, ((double)q.z - (double)g.oz) - (double)(c.z - r) * ih * (1.0 + EPS3));
+        if (c.z + r < g.gz - 1) reach = fmin(reach, (double)(c.z + r + 1) * ih * (1.0 - EPS3) - ((double)q.z - (double)g.oz));
+        if (reach > 0.0 && (double)bd[KB - 1] <= reach * reach * (1.0 - 1.0e-6)) break;
+    }
+    knn_list_store<KB>(bd, bj, K, (size_t)self, idx, dist2);
+}
+
 }  // namespace r2
 
 // ---- host side.  The library does not allocate (include/r2hip.h): the grid search works inside a caller-provided workspace of
@@ -243,8 +394,12 @@ KnnWs knn_ws_layout(int P)
 }
 }  // namespace
 
+// The grid of a cloud, built inside the workspace: bounding box, cell size for about `per_cell` points per cell, the points
+// sorted by cell (*sorted_out) and the inclusive prefix of the cell counts (*incl_out).  Shared by r2_knn_dist2_ws (2 points per
+// cell) and r2_knn_graph (more for larger K); `what` names the caller in error texts.
 // -> 0, or a negative error code; 1 = not taken: run the exhaustive kernel (tiny inputs, degenerate boxes, clustered clouds)
-static int knn_grid(int P, const float *points, float *out, char *ws, hipStream_t s)
+static int knn_grid_setup(int P, const float *points, char *ws, hipStream_t s, double per_cell, const char *what, r2::KnnGrid *g_out,
+                          const uint32_t **incl_out, const float4 **sorted_out)
 {
     using namespace r2;
     constexpr int NOT_TAKEN = 1;
@@ -258,7 +413,7 @@ static int knn_grid(int P, const float *points, float *out, char *ws, hipStream_
     float hp[6 * nb];
     hipError_t e = hipMemcpyAsync(hp, partial, sizeof(hp), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error("r2_knn_dist2: %s", hipGetErrorString(e)); return -(int)e; }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return -(int)e; }
     float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
     for (int b = 0; b < nb; ++b)
         for (int a = 0; a < 3; ++a) {
@@ -274,7 +429,7 @@ static int knn_grid(int P, const float *points, float *out, char *ws, hipStream_
     if (!(emax > 0.0)) return NOT_TAKEN;   // all points identical
     for (int a = 0; a < 3; ++a) vol *= std::max(ext[a], emax * 1e-3);   // flat clouds: a thin slab of cells
     // ~2 points per cell; at most 512 cells per axis and as many cells as the workspace was sized for
-    double h = std::cbrt(vol / (0.5 * (double)P));
+    double h = std::cbrt(vol / ((1.0 / per_cell) * (double)P));
     h = std::max(h, emax / 512.0);
     KnnGrid g;
     size_t cells = 0;
@@ -291,22 +446,35 @@ static int knn_grid(int P, const float *points, float *out, char *ws, hipStream_
              *mx = reinterpret_cast<uint32_t *>(ws + L.off_max), *incl = reinterpret_cast<uint32_t *>(ws + L.off_incl);
     float4 *sorted = reinterpret_cast<float4 *>(ws + L.off_sorted);
     e = hipMemsetAsync(ws + L.off_cnt, 0, L.off_incl - L.off_cnt, s);   // counts, cursors, the maximum
-    if (e != hipSuccess) { set_error("r2_knn_dist2: %s", hipGetErrorString(e)); return -(int)e; }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return -(int)e; }
     const unsigned blocks = (unsigned)((P + 255) / 256);
     knn_count_kernel<<<dim3(blocks), dim3(256), 0, s>>>(P, points, g, cnt);
     knn_maxcount_kernel<<<dim3((unsigned)std::min<size_t>((cells + 255) / 256, 1024)), dim3(256), 0, s>>>(cells, cnt, mx);
     uint32_t fullest = 0;
     e = hipMemcpyAsync(&fullest, mx, sizeof(fullest), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error("r2_knn_dist2: %s", hipGetErrorString(e)); return -(int)e; }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return -(int)e; }
     // a query scans ~27 cells, one lane per query; the exhaustive kernel pays P pairs per query but ~10x faster per pair
     if ((size_t)fullest > std::max<size_t>(256, (size_t)P / 256)) return NOT_TAKEN;
     const int rc = inclusive_scan_u32(ws + L.off_tmp, L.tmp_bytes, cnt, incl, (int)cells, s);
     if (rc) return rc;
     knn_scatter_kernel<<<dim3(blocks), dim3(256), 0, s>>>(P, points, g, incl, cur, sorted);
-    knn_query_kernel<<<dim3(blocks), dim3(256), 0, s>>>(P, g, incl, sorted, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error("r2_knn_dist2: %s", hipGetErrorString(e)); return -(int)e; }
+    *g_out = g;
+    *incl_out = incl;
+    *sorted_out = sorted;
+    return 0;
+}
+
+static int knn_grid(int P, const float *points, float *out, char *ws, hipStream_t s)
+{
+    r2::KnnGrid g;
+    const uint32_t *incl = nullptr;
+    const float4 *sorted = nullptr;
+    const int rc = knn_grid_setup(P, points, ws, s, 2.0, "r2_knn_dist2", &g, &incl, &sorted);
+    if (rc != 0) return rc;
+    r2::knn_query_kernel<<<dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s>>>(P, g, incl, sorted, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { r2::set_error("r2_knn_dist2: %s", hipGetErrorString(e)); return -(int)e; }
     return 0;
 }
 
@@ -345,4 +513,56 @@ extern "C" int r2_knn_dist2(int P, const float *points, float *out, void *stream
         (void)hipFree(ws);
     }
     return rc;
+}
+
+
+// ---- r2_knn_graph (include/r2hip.h)
+namespace {
+// cell size of the graph's grid: a query needs K neighbours inside the block of cells it has covered, so larger K gets larger cells
+// (fewer rings of more points each).  K <= 4 keeps r2_knn_dist2's 2 points per cell.  Not tuned: DESIGN.md section 4.
+inline double knn_graph_per_cell(int K) { return K <= 4 ? 2.0 : 0.5 * (double)K; }
+
+template <int KB>
+void knn_graph_launch(int P, int K, const float *points, const r2::KnnGrid *g, const uint32_t *incl, const float4 *sorted, int *idx,
+                      float *dist2, hipStream_t s)
+{
+    const dim3 grid((unsigned)((P + 255) / 256)), block(256);
+    if (g) r2::knn_graph_query_kernel<KB><<<grid, block, 0, s>>>(P, K, *g, incl, sorted, idx, dist2);
+    else r2::knn_graph_exhaustive_kernel<KB><<<grid, block, 0, s>>>(P, K, points, idx, dist2);
+}
+}  // namespace
+
+extern "C" size_t r2_knn_graph_workspace_bytes(int P, int K)
+{
+    (void)K;   // the grid's layout is sized by P alone (at most 2 P + 4096 cells, whatever the cell size)
+    return P > 0 ? r2_knn_workspace_bytes(P) : 0;
+}
+
+extern "C" int r2_knn_graph(int P, const float *points, int K, int *idx, float *dist2, void *workspace, size_t workspace_bytes,
+                            void *stream)
+{
+    if (K < 1 || K > R2_KNN_GRAPH_MAX_K) {
+        r2::set_error("r2_knn_graph: K = %d is outside [1, %d]", K, R2_KNN_GRAPH_MAX_K);
+        return R2_ERR_INVALID;
+    }
+    if (P == 0) return 0;
+    if (P < 0 || !points || !idx || !dist2 || (size_t)P * (size_t)K > 0x7fffffffu) {
+        r2::set_error("r2_knn_graph: invalid argument");
+        return R2_ERR_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    { r2::StageScope t(r2::ST_KNN, s);
+    r2::KnnGrid g;
+    const uint32_t *incl = nullptr;
+    const float4 *sorted = nullptr;
+    int taken = 1;
+    if (workspace != nullptr && workspace_bytes >= r2_knn_graph_workspace_bytes(P, K))
+        taken = knn_grid_setup(P, points, static_cast<char *>(workspace), s, knn_graph_per_cell(K), "r2_knn_graph", &g, &incl, &sorted);
+    if (taken < 0) return taken;
+    const r2::KnnGrid *gp = taken == 0 ? &g : nullptr;
+    if (K <= 4) knn_graph_launch<4>(P, K, points, gp, incl, sorted, idx, dist2, s);
+    else if (K <= 8) knn_graph_launch<8>(P, K, points, gp, incl, sorted, idx, dist2, s);
+    else knn_graph_launch<16>(P, K, points, gp, incl, sorted, idx, dist2, s); }
+    R2_STAGE_CHECK(0, s, "knn graph");
+    return 0;
 }

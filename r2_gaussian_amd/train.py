@@ -53,6 +53,8 @@ class OptimizationParams:
     densify_grad_threshold, densify_scale_threshold = 5.0e-5, 0.1
     max_screen_size, max_scale = None, None
     max_num_gaussians = 500_000
+    # opt-in neighbour smoothness of the densities (graph.graph_smoothness, not in the reference): off at 0
+    lambda_graph, graph_k, graph_every = 0.0, 8, 100
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -199,7 +201,10 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     eval_exact: every evaluation also writes eval2d_<name>_exact.yml (evaluate); training itself is untouched.
     save_uncertainty = lambda > 0 (None: off): after the last iteration ``save_uncertainty`` writes fisher.npz and vol_std.npy
     into the last point_cloud/iteration_N; training itself is untouched.
-    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P)."""
+    opt.lambda_graph > 0 (absent = 0: off, the loop is then the one above and graph.py is never called): the loss gains
+    lambda_graph * graph.graph_smoothness(density[:, 0], G, kind="l1"), G = the opt.graph_k (8) nearest neighbours of
+    xyz.detach(), rebuilt every opt.graph_every (100) iterations and whenever the number of Gaussians changed.
+    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds)."""
     W = int(views_per_step)
     if W < 1:
         raise ValueError("views_per_step must be >= 1, got %r" % (views_per_step,))
@@ -224,6 +229,14 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
              ("render_test", test_views,
               torch.as_tensor(np.asarray(test_projs), dtype=torch.float32).to(dev).permute(1, 2, 0) if len(test_views) else None)]
     use_tv = opt.lambda_tv > 0
+    lambda_graph = float(getattr(opt, "lambda_graph", OptimizationParams.lambda_graph))
+    graph_k = int(getattr(opt, "graph_k", OptimizationParams.graph_k))
+    graph_every = int(getattr(opt, "graph_every", OptimizationParams.graph_every))
+    if lambda_graph > 0 and graph_every < 1:
+        raise ValueError("graph_every must be >= 1, got %r" % (graph_every,))
+    nbr_graph = None
+    if lambda_graph > 0:
+        from . import graph as NG
     tvN = torch.tensor([opt.tv_vol_size] * 3)
     tvS = torch.tensor(geometry["dVoxel"], dtype=torch.float32) * tvN
     settings = [_settings(v, dev) for v in train_views]
@@ -231,7 +244,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     pyrng = random.Random(seed)
     ckpt_path = osp.join(model_path, "ckpt")
     os.makedirs(ckpt_path, exist_ok=True)
-    out = {"evals": {}}
+    out = {"evals": {}, "graph_builds": 0}
     if first_iter == 0 and 0 in test_iterations:
         out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals, eval_exact)
     stack = []
@@ -253,6 +266,11 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
         if use_tv:
             c = (bbox[0] + tvS / 2) + (bbox[1] - tvS - bbox[0]) * torch.rand(3, generator=gen)
             loss = loss + opt.lambda_tv * FL.tv_3d_loss(_query(xyz, dens, scal, rot, c, tvN, tvS))
+        if lambda_graph > 0:
+            if nbr_graph is None or nbr_graph.P != xyz.shape[0] or iteration % graph_every == 0:
+                nbr_graph = NG.knn_graph(xyz.detach(), graph_k)
+                out["graph_builds"] += 1
+            loss = loss + lambda_graph * NG.graph_smoothness(dens[:, 0], nbr_graph, kind="l1")
         loss.backward()
         with torch.no_grad():
             gaussians.add_densification_stats(radii, screen.grad, grad_scale=float(W))
