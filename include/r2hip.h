@@ -428,6 +428,66 @@ R2_API int r2_graph_loss_backward(int P, int K, const float *v, const int *idx, 
                                   const int *in_edges, int kind, float delta, float scale, const float *g /* device scalar */,
                                   float *grad /* [P] */, void *stream);
 
+/* ---- moment-preserving merging of neighbouring Gaussians (no counterpart in the reference) ---- */
+/* Conventions of the three groups.  Gaussian i has mean mu_i, covariance Sigma_i = R^T diag(s^2) R with R = quat_to_rot(r, x, y, z)
+ *   of the quaternion AS GIVEN (what cov3d_from_scale_rot forms with mod = 1; the activated rotation is a unit quaternion), and
+ *   mass m_i = density_i * s1 s2 s3 (the factor (2 pi)^(3/2) cancels everywhere).  All four arrays are ACTIVATED parameters:
+ *   means [P,3], density [P,1], scaling [P,3], rotation [P,4].  Every per-pair operation of r2_merge_cost and r2_merge_emit is
+ *   double and the result is rounded to float once, at the store.  No atomics; every call gives the same bits; no host read
+ *   except r2_merge_count's.  A graph is idx [P,K] with in_offsets / in_edges of r2_graph_transpose on the same idx; an edge
+ *   e = i * K + k is valid when idx[e] is in [0, P), a self edge when idx[e] = i.
+ *   Arguments: P = 0 is a no-op returning 0 (r2_merge_count then writes counts = {0, 0}); K < 1, P < 0, P * K >= 2^31 or a
+ *   NULL array with P > 0: R2_ERR_INVALID.
+ * r2_merge_cost: Runnalls' Kullback-Leibler bound of merging the two ends of every edge, per unit mass.  For a valid edge
+ *   e = (i, k), j = idx[e] != i: a = min(i, j), b = max(i, j) (the two directions of a pair run the same operations on the same
+ *   operands: the same bits), alpha = m_a / (m_a + m_b), d = mu_a - mu_b,
+ *     Sigma_ab = alpha Sigma_a + (1 - alpha) Sigma_b + alpha (1 - alpha) d d^T,
+ *     cost[e] = max(0, 1/2 [log det Sigma_ab - alpha log det Sigma_a - (1 - alpha) log det Sigma_b]),
+ *   dimensionless and invariant under a common scaling of the cloud.  The determinants are the products of the L D L^T pivots.
+ *   cost[e] = +inf: an invalid or self edge; a density or scale <= 0 or a non-finite parameter at either end; a result that is
+ *   not finite; max_trace > 0 and trace Sigma_ab > max_trace.  The trace test bounds the merged scales: trace <= hi^2 keeps
+ *   every merged scale <= hi, and no merged scale is below the smallest of the parents' (lambda_min(Sigma_ab) >= the smaller
+ *   of the parents' lambda_min).
+ * r2_graph_match: a matching of ANY graph (not only one of r2_knn_graph) under ANY float costs (the two directions of a pair may
+ *   disagree): mate[i] = the partner of node i, or -1.  An edge is eligible when it is valid, no self edge, cost[e] <= max_cost
+ *   (a NaN never is; +inf is when max_cost is +inf) and both ends are unmatched.  The key of an eligible directed edge between
+ *   i and j is (cost[e], min(i, j), max(i, j)), compared lexicographically: a total order over pairs.  mate starts at -1; each
+ *   of `rounds` >= 0 rounds is two launches: POINT, every unmatched node takes the partner of its smallest-key eligible edge
+ *   among its own row and its incoming list; PAIR, i and j are matched when they point at each other.  The smallest key of all
+ *   is matched in every round, so the rounds end, and what they end in is the sequential greedy matching (take the edges in
+ *   key order, an edge when both ends are free); r2_merge_count's `open` tells whether they have.  A node with more than
+ *   R2_MERGE_HUB incoming edges has its list walked by its wave (lane l: entries l, l + 64, ...; the minima fold by xor
+ *   butterfly): a minimum of a total order, the same whatever the visiting order.  Entries of in_edges that are no edge to the
+ *   node they are listed under are skipped; nothing outside the inputs is read.  Workspace: r2_graph_match_workspace_bytes(P)
+ *   bytes (alignment >= 256 B), NULL or fewer with P > 0: R2_ERR_INVALID; rounds < 0: R2_ERR_INVALID.
+ * r2_merge_count + r2_merge_emit: the two-step shape of r2_densify_classify / r2_densify_emit.  count validates mate -- an entry
+ *   that is out of range, a self mate, not an involution (mate[mate[i]] != i), or whose pair has an end of non-positive or
+ *   non-finite mass counts as -1 -- scans the surviving rows and synchronises the stream ONCE to return
+ *   counts_host = {pairs, open}; open = the unmatched nodes that still have an eligible edge (r2_graph_match's rule, same cost
+ *   and max_cost) to an unmatched node: 0 means the matching is maximal.  The caller allocates Pn = P - pairs rows and calls
+ *   emit with the same parameters and the same scratch (r2_merge_scratch_bytes(P) bytes, alignment >= 256 B).  emit writes the
+ *   rows in ascending order of the original index, a pair at its lower index: src [Pn,2] = (a, b), b = -1 for an unmerged row,
+ *   whose four outputs are bit copies of row a.  A merged row: mu = alpha mu_a + (1 - alpha) mu_b; Sigma_ab as above; its
+ *   eigenvalues by R2_MERGE_JACOBI_SWEEPS sweeps of cyclic Jacobi (rotations (0,1), (0,2), (1,2)), ordered descending,
+ *   s = sqrt(lambda); the rows of R are the eigenvectors, the third flipped when det R < 0; the unit quaternion of R with
+ *   r >= 0, the first non-zero component positive when r = 0; density = (m_a + m_b) / (s1 s2 s3) with the scales as stored.
+ *   Rows at or beyond Pn are never written. */
+#define R2_MERGE_HUB 64
+#define R2_MERGE_JACOBI_SWEEPS 8
+R2_API int r2_merge_cost(int P, int K, const int *idx /* [P,K] */, const float *means, const float *density, const float *scaling,
+                         const float *rotation, float max_trace, float *cost /* [P,K] */, void *stream);
+R2_API size_t r2_graph_match_workspace_bytes(int P);
+R2_API int r2_graph_match(int P, int K, const int *idx /* [P,K] */, const int *in_offsets /* [P+1] */, const int *in_edges /* [P*K] */,
+                          const float *cost /* [P,K] */, float max_cost, int rounds, int *mate /* [P] */, void *workspace,
+                          size_t workspace_bytes, void *stream);
+R2_API size_t r2_merge_scratch_bytes(int P);
+R2_API int r2_merge_count(int P, int K, const int *idx, const int *in_offsets, const int *in_edges, const float *cost, float max_cost,
+                          const int *mate /* [P] */, const float *density, const float *scaling, void *scratch,
+                          unsigned int *counts_host /* [2] = pairs, open */, void *stream);
+R2_API int r2_merge_emit(int P, const float *means, const float *density, const float *scaling, const float *rotation,
+                         const void *scratch, int Pn, float *means_out, float *density_out, float *scaling_out,
+                         float *rotation_out, int *src /* [Pn,2] */, void *stream);
+
 /* ---- measurement: per-stage HIP-event timing on the caller's stream ---------------------------- */
 /* bit i of stage_mask enables stage i (0 = off, the default: no events are recorded).  Enabled stages are
  * bracketed by hipEventRecord on the stream they are launched on; r2_profile_read synchronises the recorded

@@ -22,6 +22,8 @@ R2_KNN_GRAPH_MAX_K = 16
 R2_GRAPH_KIND_L1, R2_GRAPH_KIND_L2, R2_GRAPH_KIND_HUBER = 0, 1, 2
 R2_GRAPH_LOSS_CHAIN = 17   # longest chain of float roundings in r2_graph_loss's reduction (include/r2hip.h)
 R2_GRAPH_LOSS_HUB = 64     # incoming lists longer than this are summed by a whole wave in r2_graph_loss_backward
+R2_MERGE_HUB = 64          # ... and walked by a whole wave in r2_graph_match / r2_merge_count
+R2_MERGE_JACOBI_SWEEPS = 8
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -55,6 +57,12 @@ _SIGNATURES = {
     "r2_graph_loss_scratch_floats": (C.c_size_t, [_i, _i]),
     "r2_graph_loss": (C.c_int, [_i, _i, _fp, _p, _fp, _i, _f, _f, _fp, _fp, _p]),
     "r2_graph_loss_backward": (C.c_int, [_i, _i, _fp, _p, _fp, _p, _p, _i, _f, _f, _fp, _fp, _p]),
+    "r2_merge_cost": (C.c_int, [_i, _i, _p, _fp, _fp, _fp, _fp, _f, _fp, _p]),
+    "r2_graph_match_workspace_bytes": (C.c_size_t, [_i]),
+    "r2_graph_match": (C.c_int, [_i, _i, _p, _p, _p, _fp, _f, _i, _p, _p, C.c_size_t, _p]),
+    "r2_merge_scratch_bytes": (C.c_size_t, [_i]),
+    "r2_merge_count": (C.c_int, [_i, _i, _p, _p, _p, _fp, _f, _p, _fp, _fp, _p, _p, _p]),
+    "r2_merge_emit": (C.c_int, [_i, _fp, _fp, _fp, _fp, _p, _i, _fp, _fp, _fp, _fp, _p, _p]),
     "r2_tile_first_stats": (None, [C.POINTER(C.c_longlong), _i]),
     "r2_defer_count_control": (None, [_i]),
     "r2_defer_count_resolve": (C.c_int, [_i, C.POINTER(C.c_int), _p]),

@@ -42,6 +42,8 @@ SOURCES = {
     "knn.hip": EXACT,
     # EXACT: the per-term operation order is the one include/r2hip.h states and tests/graph_ref.py bounds
     "graph_loss.hip": EXACT,
+    # EXACT: the per-pair double arithmetic is the one include/r2hip.h states, and the two directions of an edge must round alike
+    "gaussian_merge.hip": EXACT,
     "loss_ops.hip": FAST,
     "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,

@@ -259,6 +259,41 @@ class GaussianModel:
         self.max_radii2D, self.xyz_gradient_accum, self.denom = mr, ga.reshape(-1, 1), dn.reshape(-1, 1)
         self._activate()
 
+    @torch.no_grad()
+    def merge(self, max_cost, k=8, rounds=12):
+        """Merge neighbouring Gaussians that say the same thing (r2_gaussian_amd.merge, not in the reference): the edges of the
+        k-NN graph whose Runnalls cost is <= max_cost are matched and every pair is replaced by its moment-matched Gaussian; with
+        a scale bound no merged scale exceeds its upper end.  Survivors keep their raw parameters and Adam moments, bit for bit;
+        a merged row gets raw parameters through the inverse activations, as create_from_pcd forms them, and zero moments, as
+        the new rows of a densification do.  Step counts are kept, the densification statistics are reset, the activations
+        refreshed.  -> number of pairs merged (one host read)."""
+        from . import merge as MG
+        if self.P < 2:
+            return 0
+        xyz, dens, scal, rot = (t.detach() for t in self.activated())
+        hi = None if self.scale_bound is None else float(self.scale_bound[1])
+        m_xyz, m_dens, m_scal, m_rot, src, info = MG.merge_gaussians(xyz, dens, scal, rot, max_cost, k=k, rounds=rounds,
+                                                                     max_scale=hi)
+        if info["pairs"] == 0:
+            return 0
+        keep = src[:, 0].long()
+        merged = (src[:, 1] >= 0)[:, None]
+        if self.scale_bound is not None:
+            lo, hi = self.scale_bound
+            s = torch.clamp(m_scal, lo + EPS, hi - EPS)
+            s = torch.relu((s - lo) / (hi - lo))
+            s = torch.log(s / (1 - s))                                                  # inverse_sigmoid
+        else:
+            s = torch.log(m_scal)
+        fresh = {"xyz": m_xyz, "density": torch.log(torch.exp(m_dens) - 1), "scaling": s, "rotation": m_rot}   # inverse_softplus
+        zero = torch.zeros((), dtype=_F32, device=self.device)
+        raw = {n: torch.where(merged, fresh[n], self._raw[n].detach()[keep]) for n in NAMES}
+        moments = {n: (torch.where(merged, zero, self.exp_avg[n][keep]), torch.where(merged, zero, self.exp_avg_sq[n][keep]))
+                   for n in NAMES}
+        self._set(raw["xyz"], raw["density"], raw["scaling"], raw["rotation"], moments=moments, steps=self.steps)
+        self._reset_stats()
+        return info["pairs"]
+
     # ------------------------------------------------------------------------------------------------ files
     def save_ply(self, path):
         """point_cloud.pickle of RAW parameters (gaussian_model.py:263-286)."""

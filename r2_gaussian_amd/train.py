@@ -55,6 +55,9 @@ class OptimizationParams:
     max_num_gaussians = 500_000
     # opt-in neighbour smoothness of the densities (graph.graph_smoothness, not in the reference): off at 0
     lambda_graph, graph_k, graph_every = 0.0, 8, 100
+    # opt-in merging of neighbouring Gaussians (GaussianModel.merge, not in the reference): off at merge_interval 0
+    merge_interval, merge_cost, merge_k = 0, 0.1, 8
+    merge_from_iter, merge_until_iter = 500, 15000
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -204,7 +207,10 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     opt.lambda_graph > 0 (absent = 0: off, the loop is then the one above and graph.py is never called): the loss gains
     lambda_graph * graph.graph_smoothness(density[:, 0], G, kind="l1"), G = the opt.graph_k (8) nearest neighbours of
     xyz.detach(), rebuilt every opt.graph_every (100) iterations and whenever the number of Gaussians changed.
-    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds)."""
+    opt.merge_interval = N > 0 (absent = 0: off, the loop is then the one above and merge.py is never imported): every N-th
+    iteration with opt.merge_from_iter < iteration < opt.merge_until_iter, right after the densification slot,
+    gaussians.merge(opt.merge_cost, k=opt.merge_k) replaces neighbouring Gaussians that say the same thing by one.
+    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds, merged_pairs)."""
     W = int(views_per_step)
     if W < 1:
         raise ValueError("views_per_step must be >= 1, got %r" % (views_per_step,))
@@ -237,6 +243,13 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     nbr_graph = None
     if lambda_graph > 0:
         from . import graph as NG
+    merge_interval = int(getattr(opt, "merge_interval", OptimizationParams.merge_interval))
+    merge_cost = float(getattr(opt, "merge_cost", OptimizationParams.merge_cost))
+    merge_k = int(getattr(opt, "merge_k", OptimizationParams.merge_k))
+    merge_from = int(getattr(opt, "merge_from_iter", OptimizationParams.merge_from_iter))
+    merge_until = int(getattr(opt, "merge_until_iter", OptimizationParams.merge_until_iter))
+    if merge_interval < 0:
+        raise ValueError("merge_interval must be >= 0, got %r" % (merge_interval,))
     tvN = torch.tensor([opt.tv_vol_size] * 3)
     tvS = torch.tensor(geometry["dVoxel"], dtype=torch.float32) * tvN
     settings = [_settings(v, dev) for v in train_views]
@@ -244,7 +257,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     pyrng = random.Random(seed)
     ckpt_path = osp.join(model_path, "ckpt")
     os.makedirs(ckpt_path, exist_ok=True)
-    out = {"evals": {}, "graph_builds": 0}
+    out = {"evals": {}, "graph_builds": 0, "merged_pairs": 0}
     if first_iter == 0 and 0 in test_iterations:
         out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals, eval_exact)
     stack = []
@@ -278,6 +291,8 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
                 gaussians.densify_and_prune(opt.densify_grad_threshold, opt.density_min_threshold, opt.max_screen_size,
                                             max_scale, opt.max_num_gaussians, densify_scale_threshold, bbox,
                                             normals=torch.randn((2, gaussians.P, 3), generator=gen))
+            if merge_interval > 0 and merge_from < iteration < merge_until and iteration % merge_interval == 0:
+                out["merged_pairs"] += gaussians.merge(merge_cost, k=merge_k)
             if iteration < opt.iterations:
                 gaussians.step()
             else:
