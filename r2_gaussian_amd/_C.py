@@ -2,8 +2,8 @@
 (SUB/ext.cpp:17-23): the same five functions with the same argument lists and return tuples, implemented on
 top of the C ABI of libr2hip.so.  This file plays the role of the torch boundary
 SUB/rasterize_points.cu / SUB/voxelize_points.cu: it owns tensor allocation (outputs, zeroed gradient
-buffers, the three opaque uint8 state tensors handed to the kernels through allocation callbacks) and passes
-raw device pointers + the current HIP stream down.
+buffers, the three opaque uint8 state tensors handed to the kernels through allocation callbacks); how the call itself is
+made -- device, raw pointers, the current HIP stream, the return code -- is ``_boundary.call``'s business, as for every module.
 """
 import os
 
@@ -12,8 +12,8 @@ import threading
 import torch
 
 from . import _lib
-
-_F32 = torch.float32
+from ._boundary import _F32, call, require_gpu, workspace
+from ._boundary import stream as _stream   # noqa: F401  (tests and scripts import it from here)
 
 # The same torch boundary compiled (csrc/torch_shim.cpp -> _r2shim.so, built by r2_gaussian_amd.build): ~70 us less
 # interpreter time per training view than the ctypes path below.  Both drive the same libr2hip.so; R2_SHIM=0 forces ctypes.
@@ -72,9 +72,9 @@ def _dev_f32(t, like):
     return t
 
 
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise _lib.R2HipError("%s must be a GPU tensor: the MI355X kernels have no CPU fallback" % name)
+def _inputs(means3D, *ts):
+    """``means3D`` and ``ts`` as the kernels read them (``_dev_f32``: None, which goes down as NULL, for an absent one)."""
+    return [_dev_f32(t, means3D) for t in (means3D,) + ts]
 
 
 class _State:
@@ -139,25 +139,15 @@ def _hooks(device):
     return h
 
 
-class _on_device:
-    """``with torch.cuda.device(dev)`` only when dev is not already current (the context manager costs ~10 us)."""
-
-    __slots__ = ("ctx",)
-
-    def __init__(self, dev):
-        self.ctx = None if torch.cuda.current_device() == (dev.index or 0) else torch.cuda.device(dev)
-
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
+def _forward(name, dev, hk, *args):
+    """A forward entry with the three allocation callbacks in front of ``args`` -> (num_rendered, the three state buffers the
+    callbacks were asked for, ``hk.empty`` for one that was not)."""
+    st = hk.begin()
+    try:
+        rendered = call(name, dev, hk.cbs[0], None, hk.cbs[1], None, hk.cbs[2], None, *args)
+    finally:
+        bufs = hk.finish(st)
+    return rendered, bufs
 
 
 def rasterize_gaussians(means3D, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -167,7 +157,7 @@ def rasterize_gaussians(means3D, opacity, scales, rotations, scale_modifier, cov
     (SUB/rasterize_points.cu:28-97)."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     sh = _shim()
     if sh is not None:
@@ -182,20 +172,10 @@ def rasterize_gaussians(means3D, opacity, scales, rotations, scale_modifier, cov
     # both outputs are written in full by the kernels (every pixel, every Gaussian): no zero-fill needed
     out_color = torch.empty((1, H, W), dtype=_F32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
-    m3 = _dev_f32(means3D, means3D)
-    op, sc, ro, cp = (_dev_f32(t, means3D) for t in (opacity, scales, rotations, cov3D_precomp))
-    vm, pm, cam = (_dev_f32(t, means3D) for t in (viewmatrix, projmatrix, campos))
-    st = hk.begin()
-    try:
-        with _on_device(dev):
-            rc = _lib.lib().r2_raster_forward(
-                hk.cbs[0], None, hk.cbs[1], None, hk.cbs[2], None, P, W, H, _ptr(m3), _ptr(op), _ptr(sc),
-                float(scale_modifier), _ptr(ro), _ptr(cp), _ptr(vm), _ptr(pm), _ptr(cam), float(tan_fovx),
-                float(tan_fovy), int(bool(prefiltered)), int(mode), out_color.data_ptr(), radii.data_ptr(),
-                int(bool(debug)), _stream(dev))
-    finally:
-        bufs = hk.finish(st)
-    rendered = _lib.check(rc, "r2_raster_forward")
+    m3, op, sc, ro, cp, vm, pm, cam = _inputs(means3D, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
+    rendered, bufs = _forward("r2_raster_forward", dev, hk, P, W, H, m3, op, sc, float(scale_modifier), ro, cp, vm, pm, cam,
+                              float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), int(mode), out_color, radii,
+                              int(bool(debug)))
     return rendered, out_color, radii, bufs[0], bufs[1], bufs[2]
 
 
@@ -204,7 +184,7 @@ def rasterize_gaussians_backward(means3D, radii, scales, rotations, scale_modifi
                                  binningBuffer, imageBuffer, mode, debug):
     """-> (dL_dmeans2D[P,3], dL_dopacity[P,1], dL_dmu[P,1], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dscales[P,3],
     dL_drotations[P,4])  (SUB/rasterize_points.cu:99-164)."""
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     sh = _shim()
     if sh is not None:
@@ -231,19 +211,11 @@ def rasterize_gaussians_backward(means3D, radii, scales, rotations, scale_modifi
     dL_dmu = flat.as_strided((P, 1), (1, 1), o); o += P
     dL_dcov3D = flat.as_strided((P, 6), (6, 1), o)
     if P != 0:
-        m3 = _dev_f32(means3D, means3D)
-        sc, ro, cp = (_dev_f32(t, means3D) for t in (scales, rotations, cov3D_precomp))
-        vm, pm, cam = (_dev_f32(t, means3D) for t in (viewmatrix, projmatrix, campos))
-        g = _dev_f32(dL_dout_color, means3D)
-        rad = radii.contiguous()
-        with _on_device(dev):
-            rc = _lib.lib().r2_raster_backward(
-                P, int(R), W, H, _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(ro), _ptr(cp), _ptr(vm), _ptr(pm),
-                _ptr(cam), float(tan_fovx), float(tan_fovy), rad.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer),
-                _ptr(imageBuffer), _ptr(g), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
-                dL_dmu.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(), dL_dscales.data_ptr(),
-                dL_drot.data_ptr(), int(mode), int(bool(debug)), _stream(dev))
-        _lib.check(rc, "r2_raster_backward")
+        m3, sc, ro, cp, vm, pm, cam, g = _inputs(means3D, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                                 dL_dout_color)
+        call("r2_raster_backward", dev, P, int(R), W, H, m3, sc, float(scale_modifier), ro, cp, vm, pm, cam, float(tan_fovx),
+             float(tan_fovy), radii.contiguous(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), g, dL_dmeans2D,
+             dL_dconic, dL_dopacity, dL_dmu, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drot, int(mode), int(bool(debug)))
     return dL_dmeans2D, dL_dopacity, dL_dmu, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drot
 
 
@@ -255,7 +227,7 @@ def rasterize_gaussians_batch(means3D, opacity, scales, rotations, scale_modifie
     bit-identical to ``rasterize_gaussians`` for that view."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     if viewmatrices.ndim != 3 or viewmatrices.shape[1:] != (4, 4) or projmatrices.shape != viewmatrices.shape:
         raise RuntimeError("viewmatrices / projmatrices must have dimensions (num_views, 4, 4)")
     dev = means3D.device
@@ -266,19 +238,9 @@ def rasterize_gaussians_batch(means3D, opacity, scales, rotations, scale_modifie
             hk.empty, hk.empty, hk.empty
     out_color = torch.empty((V, H, W), dtype=_F32, device=dev)
     radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-    m3 = _dev_f32(means3D, means3D)
-    op, sc, ro, cp = (_dev_f32(t, means3D) for t in (opacity, scales, rotations, cov3D_precomp))
-    vm, pm = (_dev_f32(t, means3D) for t in (viewmatrices, projmatrices))
-    st = hk.begin()
-    try:
-        with _on_device(dev):
-            rc = _lib.lib().r2_raster_forward_batch(
-                hk.cbs[0], None, hk.cbs[1], None, hk.cbs[2], None, P, V, W, H, _ptr(m3), _ptr(op), _ptr(sc),
-                float(scale_modifier), _ptr(ro), _ptr(cp), _ptr(vm), _ptr(pm), float(tan_fovx), float(tan_fovy), int(mode),
-                out_color.data_ptr(), radii.data_ptr(), int(bool(debug)), _stream(dev))
-    finally:
-        bufs = hk.finish(st)
-    rendered = _lib.check(rc, "r2_raster_forward_batch")
+    m3, op, sc, ro, cp, vm, pm = _inputs(means3D, opacity, scales, rotations, cov3D_precomp, viewmatrices, projmatrices)
+    rendered, bufs = _forward("r2_raster_forward_batch", dev, hk, P, V, W, H, m3, op, sc, float(scale_modifier), ro, cp, vm, pm,
+                              float(tan_fovx), float(tan_fovy), int(mode), out_color, radii, int(bool(debug)))
     return rendered, out_color, radii, bufs[0], bufs[1], bufs[2]
 
 
@@ -288,7 +250,7 @@ def rasterize_gaussians_backward_batch(means3D, radii, scales, rotations, scale_
     """-> (dL_dmeans2D[V,P,3], dL_dopacity[P,1], dL_dmu[V,P], dL_dmeans3D[P,3], dL_dcov3D[P,6], dL_dscales[P,3],
     dL_drotations[P,4]): per-view screen-space gradients (the densification statistics are per view), parameter gradients
     summed over the V views in view order."""
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     P, V = means3D.shape[0], viewmatrices.shape[0]
     H, W = int(dL_dout_color.shape[-2]), int(dL_dout_color.shape[-1])
@@ -305,33 +267,22 @@ def rasterize_gaussians_backward_batch(means3D, radii, scales, rotations, scale_
     dL_dmeans2D = flat.as_strided((V, P, 3), (3 * P, 3, 1), o); o += 3 * V * P
     dL_dmu = flat.as_strided((V, P), (P, 1), o)
     if P != 0:
-        m3 = _dev_f32(means3D, means3D)
-        sc, ro, cp = (_dev_f32(t, means3D) for t in (scales, rotations, cov3D_precomp))
-        vm, pm = (_dev_f32(t, means3D) for t in (viewmatrices, projmatrices))
-        g = _dev_f32(dL_dout_color, means3D)
-        rad = radii.contiguous()
-        with _on_device(dev):
-            rc = _lib.lib().r2_raster_backward_batch(
-                P, V, int(R), W, H, _ptr(m3), _ptr(sc), float(scale_modifier), _ptr(ro), _ptr(cp), _ptr(vm), _ptr(pm),
-                float(tan_fovx), float(tan_fovy), rad.data_ptr(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
-                _ptr(g), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(), dL_dmu.data_ptr(),
-                dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(), dL_dscales.data_ptr(), dL_drot.data_ptr(), int(mode),
-                int(bool(debug)), _stream(dev))
-        _lib.check(rc, "r2_raster_backward_batch")
+        m3, sc, ro, cp, vm, pm, g = _inputs(means3D, scales, rotations, cov3D_precomp, viewmatrices, projmatrices, dL_dout_color)
+        call("r2_raster_backward_batch", dev, P, V, int(R), W, H, m3, sc, float(scale_modifier), ro, cp, vm, pm, float(tan_fovx),
+             float(tan_fovy), radii.contiguous(), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), g, dL_dmeans2D,
+             dL_dconic, dL_dopacity, dL_dmu, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drot, int(mode), int(bool(debug)))
     return dL_dmeans2D, dL_dopacity, dL_dmu, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drot
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):
     """-> bool[P], ``z_view > 0.2``  (SUB/rasterize_points.cu:166-185)."""
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     P = means3D.shape[0]
     present = torch.zeros((P,), dtype=torch.bool, device=dev)
     if P != 0:
-        m3, vm, pm = (_dev_f32(t, means3D) for t in (means3D, viewmatrix, projmatrix))
-        with _on_device(dev):
-            rc = _lib.lib().r2_mark_visible(P, _ptr(m3), _ptr(vm), _ptr(pm), present.data_ptr(), _stream(dev))
-        _lib.check(rc, "r2_mark_visible")
+        m3, vm, pm = _inputs(means3D, viewmatrix, projmatrix)
+        call("r2_mark_visible", dev, P, m3, vm, pm, present)
     return present
 
 
@@ -342,9 +293,7 @@ def defer_count_resolve(token, device=None):
     import ctypes
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     n = ctypes.c_int(0)
-    with _on_device(dev):
-        rc = _lib.lib().r2_defer_count_resolve(int(token), ctypes.byref(n), _stream(dev))
-    _lib.check(rc, "r2_defer_count_resolve")
+    call("r2_defer_count_resolve", dev, int(token), ctypes.byref(n))
     return n.value
 
 
@@ -378,7 +327,7 @@ def voxelize_gaussians_slab(means3D, opacity, scales, rotations, scale_modifier,
     to those voxels of the full call."""
     if means3D.ndim != 2 or means3D.shape[1] != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     t0, t1, nxs = _slab_tiles(nVoxel_x, tile_x0, tile_x1)
     sh = _shim()
@@ -395,19 +344,10 @@ def voxelize_gaussians_slab(means3D, opacity, scales, rotations, scale_modifier,
         return 0, torch.zeros((nxs, ny, nz), dtype=_F32, device=dev), z, z.clone(), z.clone(), hk.empty, hk.empty, hk.empty
     out = torch.empty((nxs, ny, nz), dtype=_F32, device=dev)      # written in full by the combine kernel
     radii = torch.empty((3, P), dtype=torch.int32, device=dev)    # written in full by the preprocess kernel
-    m3 = _dev_f32(means3D, means3D)
-    op, sc, ro, cp = (_dev_f32(t, means3D) for t in (opacity, scales, rotations, cov3D_precomp))
-    st = hk.begin()
-    try:
-        with _on_device(dev):
-            rc = _lib.lib().r2_voxel_forward_slab(
-                hk.cbs[0], None, hk.cbs[1], None, hk.cbs[2], None, P, nx, ny, nz, float(sVoxel_x), float(sVoxel_y),
-                float(sVoxel_z), float(center_x), float(center_y), float(center_z), t0, t1, _ptr(m3), _ptr(op), _ptr(sc),
-                float(scale_modifier), _ptr(ro), _ptr(cp), int(bool(prefiltered)), out.data_ptr(),
-                radii[0].data_ptr(), radii[1].data_ptr(), radii[2].data_ptr(), int(bool(debug)), _stream(dev))
-    finally:
-        bufs = hk.finish(st)
-    rendered = _lib.check(rc, "r2_voxel_forward_slab")
+    m3, op, sc, ro, cp = _inputs(means3D, opacity, scales, rotations, cov3D_precomp)
+    rendered, bufs = _forward("r2_voxel_forward_slab", dev, hk, P, nx, ny, nz, float(sVoxel_x), float(sVoxel_y), float(sVoxel_z),
+                              float(center_x), float(center_y), float(center_z), t0, t1, m3, op, sc, float(scale_modifier), ro, cp,
+                              int(bool(prefiltered)), out, radii[0], radii[1], radii[2], int(bool(debug)))
     return rendered, out, radii[0], radii[1], radii[2], bufs[0], bufs[1], bufs[2]
 
 
@@ -428,7 +368,7 @@ def voxelize_gaussians_backward_slab(means3D, radii_x, radii_y, radii_z, scales,
                                      nVoxel_y, nVoxel_z, sVoxel_x, sVoxel_y, sVoxel_z, center_x, center_y, center_z,
                                      debug, tile_x0, tile_x1):
     """Backward of ``voxelize_gaussians_slab`` (dL_dout_color = the slab's block)."""
-    _require_gpu(means3D, "means3D")
+    require_gpu(means3D, "means3D")
     dev = means3D.device
     t0, t1, _nxs = _slab_tiles(nVoxel_x, tile_x0, tile_x1)
     sh = _shim()
@@ -452,35 +392,25 @@ def voxelize_gaussians_backward_slab(means3D, radii_x, radii_y, radii_z, scales,
     dL_dcov3D = views[5].view(P, 6)
     dL_dscales = views[6].view(P, 3)
     if P != 0:
-        m3 = _dev_f32(means3D, means3D)
-        sc, ro, cp = (_dev_f32(t, means3D) for t in (scales, rotations, cov3D_precomp))
-        g = _dev_f32(dL_dout_color, means3D)
-        rx, ry, rz = radii_x.contiguous(), radii_y.contiguous(), radii_z.contiguous()
-        with _on_device(dev):
-            rc = _lib.lib().r2_voxel_backward_slab(
-                P, int(R), int(nVoxel_x), int(nVoxel_y), int(nVoxel_z), float(sVoxel_x), float(sVoxel_y),
-                float(sVoxel_z), float(center_x), float(center_y), float(center_z), t0, t1, _ptr(m3), _ptr(sc),
-                float(scale_modifier), _ptr(ro), _ptr(cp), rx.data_ptr(), ry.data_ptr(), rz.data_ptr(),
-                _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(g), dL_dmeans3D_norm.data_ptr(),
-                dL_dconic3D.data_ptr(), dL_dopacity.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-                dL_dscales.data_ptr(), dL_drot.data_ptr(), int(bool(debug)), _stream(dev))
-        _lib.check(rc, "r2_voxel_backward_slab")
+        m3, sc, ro, cp, g = _inputs(means3D, scales, rotations, cov3D_precomp, dL_dout_color)
+        call("r2_voxel_backward_slab", dev, P, int(R), int(nVoxel_x), int(nVoxel_y), int(nVoxel_z), float(sVoxel_x),
+             float(sVoxel_y), float(sVoxel_z), float(center_x), float(center_y), float(center_z), t0, t1, m3, sc,
+             float(scale_modifier), ro, cp, radii_x.contiguous(), radii_y.contiguous(), radii_z.contiguous(), _ptr(geomBuffer),
+             _ptr(binningBuffer), _ptr(imageBuffer), g, dL_dmeans3D_norm, dL_dconic3D, dL_dopacity, dL_dmeans3D, dL_dcov3D,
+             dL_dscales, dL_drot, int(bool(debug)))
     return dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drot
 
 
 def distCUDA2(points):
     """simple_knn._C.distCUDA2: mean squared distance to the 3 nearest neighbours, [P] f32."""
-    _require_gpu(points, "points")
+    require_gpu(points, "points")
     dev = points.device
     pts = _dev_f32(points, points)
     P = points.shape[0]
     out = torch.zeros((P,), dtype=_F32, device=dev)
     if P != 0:
-        L = _lib.lib()
         # the library does not allocate: the grid search's workspace comes from torch's allocator (r2hip.h)
-        nbytes = int(L.r2_knn_workspace_bytes(P))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        with _on_device(dev):
-            rc = L.r2_knn_dist2_ws(P, _ptr(pts), out.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
-        _lib.check(rc, "r2_knn_dist2_ws")
+        nbytes = int(_lib.lib().r2_knn_workspace_bytes(P))
+        ws = workspace(nbytes, dev)
+        call("r2_knn_dist2_ws", dev, P, pts, out, ws, nbytes)
     return out

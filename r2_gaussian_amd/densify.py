@@ -11,25 +11,20 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._C import _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, ptr_table, require_gpu
 
 NAMES = ("xyz", "density", "scaling", "rotation")
-_F32 = torch.float32
 
 
 def densification_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom):
     """In place (train.py:151-154, gaussian_model.py:552-556): for radii > 0: max_radii2D = max(., radii),
     grad_accum += ||viewspace_grad[:, :2]||, denom += 1.  One launch, no host synchronisation."""
-    _require_gpu(viewspace_grad, "viewspace_grad")
+    require_gpu(viewspace_grad, "viewspace_grad")
     P = radii.shape[0]
     assert viewspace_grad.shape == (P, 3) and viewspace_grad.is_contiguous() and radii.dtype == torch.int32
     for t in (max_radii2D, grad_accum, denom):
         assert t.numel() == P and t.is_contiguous() and t.dtype == _F32
-    dev = viewspace_grad.device
-    with _on_device(dev):
-        rc = _lib.lib().r2_densify_stats(P, radii.contiguous().data_ptr(), viewspace_grad.data_ptr(), max_radii2D.data_ptr(),
-                                         grad_accum.data_ptr(), denom.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_densify_stats")
+    call("r2_densify_stats", viewspace_grad.device, P, radii.contiguous(), viewspace_grad, max_radii2D, grad_accum, denom)
 
 
 def densification_stats_batch(radii, viewspace_grad, max_radii2D, grad_accum, denom, grad_scale=1.0):
@@ -37,7 +32,7 @@ def densification_stats_batch(radii, viewspace_grad, max_radii2D, grad_accum, de
     GaussianRasterizerBatch leaves them.  Every view in order: for radii > 0: max_radii2D = max(., radii), grad_accum +=
     grad_scale * ||viewspace_grad[v, :, :2]||, denom += 1; with grad_scale 1 bit-identical to V single-view calls.
     grad_scale = V undoes the 1 / V a mean-over-views loss leaves in the gradients (exact for V a power of two)."""
-    _require_gpu(viewspace_grad, "viewspace_grad")
+    require_gpu(viewspace_grad, "viewspace_grad")
     if radii.dim() != 2 or radii.shape[0] < 1:
         raise ValueError("radii must be [V, P] with V >= 1, got %s" % (tuple(radii.shape),))
     V, P = radii.shape
@@ -45,18 +40,8 @@ def densification_stats_batch(radii, viewspace_grad, max_radii2D, grad_accum, de
     assert radii.dtype == torch.int32
     for t in (max_radii2D, grad_accum, denom):
         assert t.numel() == P and t.is_contiguous() and t.dtype == _F32
-    dev = viewspace_grad.device
-    with _on_device(dev):
-        rc = _lib.lib().r2_densify_stats_batch(P, V, radii.contiguous().data_ptr(), viewspace_grad.data_ptr(), float(grad_scale),
-                                               max_radii2D.data_ptr(), grad_accum.data_ptr(), denom.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_densify_stats_batch")
-
-
-def _ptrs(ts):
-    arr = (C.c_void_p * 4)()
-    for i, t in enumerate(ts):
-        arr[i] = None if t is None else t.data_ptr()
-    return arr
+    call("r2_densify_stats_batch", viewspace_grad.device, P, V, radii.contiguous(), viewspace_grad, float(grad_scale), max_radii2D,
+         grad_accum, denom)
 
 
 def densify_and_prune(params, moments, max_radii2D, grad_accum, denom, normals, grad_threshold, scale_threshold, density_min,
@@ -68,7 +53,7 @@ def densify_and_prune(params, moments, max_radii2D, grad_accum, denom, normals, 
     rows whose max_radii2D exceeds the first or whose largest activated scale exceeds the second are pruned -- children of a
     split inherit the parent's max_radii2D and get its scale / 1.6.  Raises ValueError when nothing survives (train.py:169-172)."""
     xyz = params["xyz"]
-    _require_gpu(xyz, "xyz")
+    require_gpu(xyz, "xyz")
     dev, P = xyz.device, xyz.shape[0]
     L = _lib.lib()
     ps = [params[n].detach().to(_F32).contiguous() for n in NAMES]
@@ -84,24 +69,19 @@ def densify_and_prune(params, moments, max_radii2D, grad_accum, denom, normals, 
     counts = (C.c_uint * 4)()
     common = (float(grad_threshold), float(scale_threshold), float(density_min), box, lo, hi, int(bool(do_densify)),
               float(max_screen_size or 0.0), float(max_scale or 0.0))
-    with _on_device(dev):
-        rc = L.r2_densify_classify(P, ps[0].data_ptr(), ps[1].data_ptr(), ps[2].data_ptr(), ps[3].data_ptr(), mr.data_ptr(),
-                                   ga.data_ptr(), dn.data_ptr(), nrm.data_ptr(), *common, scratch.data_ptr(), counts, _stream(dev))
-        _lib.check(rc, "r2_densify_classify")
-        cnt = tuple(int(c) for c in counts)
-        Pn = sum(cnt)
-        if Pn == 0:
-            raise ValueError("No Gaussian left. Change adaptive control hyperparameters!")   # train.py:169-172
-        widths = (3, 1, 3, 4)
-        po = [torch.empty((Pn, w), dtype=_F32, device=dev) for w in widths]
-        mo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
-        vo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
-        mro, gao, dno = (torch.empty(Pn, dtype=_F32, device=dev) for _ in range(3))
-        rc = L.r2_densify_emit(P, _ptrs(ps), _ptrs(ms) if have_m else None, _ptrs(vs) if have_m else None, mr.data_ptr(),
-                               ga.data_ptr(), dn.data_ptr(), nrm.data_ptr(), *common, scratch.data_ptr(), _ptrs(po),
-                               _ptrs(mo) if have_m else None, _ptrs(vo) if have_m else None, mro.data_ptr(), gao.data_ptr(),
-                               dno.data_ptr(), _stream(dev))
-        _lib.check(rc, "r2_densify_emit")
+    call("r2_densify_classify", dev, P, *ps, mr, ga, dn, nrm, *common, scratch, counts)
+    cnt = tuple(int(c) for c in counts)
+    Pn = sum(cnt)
+    if Pn == 0:
+        raise ValueError("No Gaussian left. Change adaptive control hyperparameters!")   # train.py:169-172
+    widths = (3, 1, 3, 4)
+    po = [torch.empty((Pn, w), dtype=_F32, device=dev) for w in widths]
+    mo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
+    vo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
+    mro, gao, dno = (torch.empty(Pn, dtype=_F32, device=dev) for _ in range(3))
+    call("r2_densify_emit", dev, P, ptr_table(ps), ptr_table(ms) if have_m else None, ptr_table(vs) if have_m else None, mr, ga,
+         dn, nrm, *common, scratch, ptr_table(po), ptr_table(mo) if have_m else None, ptr_table(vo) if have_m else None, mro,
+         gao, dno)
     new_params = dict(zip(NAMES, po))
     new_moments = {n: (m, v) for n, m, v in zip(NAMES, mo, vo)} if have_m else None
     return new_params, new_moments, mro, gao, dno, cnt

@@ -16,11 +16,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
 from . import scene as S
-from ._C import _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, require_gpu
 
-_F32 = torch.float32
 FILTERS = ("ram_lak", "shepp_logan", "cosine", "hamming", "hann")
 
 
@@ -62,34 +60,26 @@ def ramp_taps(n_u, n_v=None, name="ram_lak"):
 
 def fdk_filter(projs, du, dv, DSD, DSO, filter_name="ram_lak", cone=True):
     """projs [V,H,W] (GPU) -> pre-weighted, ramp-filtered projections, TRANSPOSED: [V,W,H]."""
-    _require_gpu(projs, "projs")
+    require_gpu(projs, "projs")
     p = projs.to(_F32).contiguous()
     V, H, W = p.shape
     taps = torch.from_numpy(ramp_taps(W, H, filter_name)).to(p.device)
     out = torch.empty((V, W, H), dtype=_F32, device=p.device)
     scale = ((DSD / DSO) if cone else 1.0) * (2.0 * math.pi / V) / (4.0 * du)
-    L = _lib.lib()
-    with _on_device(p.device):
-        rc = L.r2_fdk_filter(V, H, W, p.data_ptr(), taps.data_ptr(), float(scale), int(bool(cone)), float(DSD), float(du),
-                             float(dv), out.data_ptr(), _stream(p.device))
-    _lib.check(rc, "r2_fdk_filter")
+    call("r2_fdk_filter", p.device, V, H, W, p, taps, float(scale), int(bool(cone)), float(DSD), float(du), float(dv), out)
     return out
 
 
 def fdk_backproject(filtered_t, full_proj, DSO, nVoxel, sVoxel, center, cone=True):
     """filtered_t [V,W,H] from ``fdk_filter``; full_proj [V,4,4] (``full_proj_transform`` of the views) -> vol [nx,ny,nz]."""
-    _require_gpu(filtered_t, "filtered_t")
+    require_gpu(filtered_t, "filtered_t")
     q = filtered_t.to(_F32).contiguous()
     V, W, H = q.shape
     M = full_proj.to(device=q.device, dtype=_F32).reshape(V, 16).contiguous()
     nx, ny, nz = (int(n) for n in nVoxel)
     vol = torch.empty((nx, ny, nz), dtype=_F32, device=q.device)
-    L = _lib.lib()
-    with _on_device(q.device):
-        rc = L.r2_fdk_backproject(V, H, W, q.data_ptr(), M.data_ptr(), int(bool(cone)), float(DSO), nx, ny, nz,
-                                  float(sVoxel[0]), float(sVoxel[1]), float(sVoxel[2]), float(center[0]), float(center[1]),
-                                  float(center[2]), vol.data_ptr(), _stream(q.device))
-    _lib.check(rc, "r2_fdk_backproject")
+    call("r2_fdk_backproject", q.device, V, H, W, q, M, int(bool(cone)), float(DSO), nx, ny, nz, float(sVoxel[0]), float(sVoxel[1]),
+         float(sVoxel[2]), float(center[0]), float(center[1]), float(center[2]), vol)
     return vol
 
 

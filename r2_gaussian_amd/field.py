@@ -10,13 +10,7 @@ scattered samples), and the operator is differentiable in the points as well as 
 import torch
 
 from . import _lib
-from ._C import _on_device, _require_gpu, _stream
-
-_F32 = torch.float32
-
-
-def _f32c(t):
-    return t if t.dtype == _F32 and t.is_contiguous() else t.to(_F32).contiguous()
+from ._boundary import _F32, call, cloud, f32c, require_gpu, workspace
 
 
 def _spread10(v):
@@ -58,16 +52,13 @@ class _QueryPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, xyz, density, scaling, rotation, scale_modifier, perm):
         N, P = points.shape[0], xyz.shape[0]
-        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
-        pts = _f32c(points.detach())
+        x, d, s, r = cloud(xyz, density, scaling, rotation)
+        pts = f32c(points.detach())
         inv = None
         if perm is not None:
             pts, inv = pts[perm].contiguous(), inverse_permutation(perm)
         out = torch.empty((N,), dtype=_F32, device=x.device)
-        with _on_device(x.device):
-            rc = _lib.lib().r2_query_gaussians(N, pts.data_ptr(), P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                               float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(x.device))
-        _lib.check(rc, "r2_query_gaussians")
+        call("r2_query_gaussians", x.device, N, pts, P, x, d, s, float(scale_modifier), r, out)
         ctx.save_for_backward(pts, x, d, s, r, perm, inv)
         ctx.mod = float(scale_modifier)
         return out if inv is None else out[inv]
@@ -76,19 +67,13 @@ class _QueryPoints(torch.autograd.Function):
     def backward(ctx, G):
         pts, x, d, s, r, perm, inv = ctx.saved_tensors
         N, P = pts.shape[0], x.shape[0]
-        G = _f32c(G)
+        G = f32c(G)
         if perm is not None:
             G = G[perm].contiguous()
         gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
         gp = torch.empty_like(pts) if ctx.needs_input_grad[0] else None
-        L = _lib.lib()
-        ws = torch.empty((max(int(L.r2_query_gaussians_workspace_bytes(N)), 1),), dtype=torch.uint8, device=x.device)
-        with _on_device(x.device):
-            rc = L.r2_query_gaussians_backward(N, pts.data_ptr(), P, x.data_ptr(), d.data_ptr(), s.data_ptr(), ctx.mod,
-                                               r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(),
-                                               gr.data_ptr(), None if gp is None else gp.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               _stream(x.device))
-        _lib.check(rc, "r2_query_gaussians_backward")
+        ws = workspace(_lib.lib().r2_query_gaussians_workspace_bytes(N), x.device, at_least=1)
+        call("r2_query_gaussians_backward", x.device, N, pts, P, x, d, s, ctx.mod, r, G, gx, gd, gs, gr, gp, ws, ws.numel())
         if gp is not None and inv is not None:
             gp = gp[inv]
         return gp, gx, gd, gs, gr, None, None
@@ -104,7 +89,7 @@ def _check_cloud(xyz, density, scaling, rotation):
     if scaling.shape[0] != P or rotation.shape[0] != P:
         raise ValueError("xyz, scaling and rotation differ in P: %d, %d, %d" % (P, scaling.shape[0], rotation.shape[0]))
     for name, t in (("xyz", xyz), ("density", density), ("scaling", scaling), ("rotation", rotation)):
-        _require_gpu(t, name)
+        require_gpu(t, name)
         if t.device != xyz.device:
             raise ValueError("%s is on %s, xyz on %s" % (name, t.device, xyz.device))
     if P > (1 << 29):
@@ -123,7 +108,7 @@ def query_points(points, xyz, density, scaling, rotation, scale_modifier=1.0, so
     and the gradients; the result is the same."""
     if not isinstance(points, torch.Tensor) or points.dim() < 1 or points.shape[-1] != 3:
         raise ValueError("points must be a tensor [..., 3], got %s" % (tuple(getattr(points, "shape", ())),))
-    _require_gpu(points, "points")
+    require_gpu(points, "points")
     _check_cloud(xyz, density, scaling, rotation)
     if points.device != xyz.device:
         raise ValueError("points are on %s, xyz on %s" % (points.device, xyz.device))
@@ -151,7 +136,7 @@ def query_plane(origin, du, dv, H, W, xyz, density, scaling, rotation, scale_mod
     world coordinates each."""
     if not isinstance(xyz, torch.Tensor):
         raise ValueError("xyz must be a tensor [P,3]")
-    _require_gpu(xyz, "xyz")
+    require_gpu(xyz, "xyz")
     return query_points(plane_points(origin, du, dv, H, W, xyz.device), xyz, density, scaling, rotation, scale_modifier)
 
 

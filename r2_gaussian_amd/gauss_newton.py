@@ -16,9 +16,8 @@ without ever forming J: every CG iteration is one JVP launch and one backward la
 """
 import torch
 
-from . import _lib
 from . import projector
-from ._C import _on_device, _stream
+from ._boundary import call
 from .gaussian_projector import (check_projection_arguments, plan_projection_rays, project_gaussians_rays, project_gaussians_rays_jvp,
                                  world_ray_params)
 from .uncertainty import CloudTuple, _check_group_tuple, _cloud, fisher_diagonal_rays
@@ -40,12 +39,7 @@ def _backward(rays, cone, H, W, cloud, G, scale_modifier):
     P = x.shape[0]
     out = CloudTuple(torch.empty((P, 3), dtype=_F32, device=dev), torch.empty((P, 1), dtype=_F32, device=dev),
                      torch.empty((P, 3), dtype=_F32, device=dev), torch.empty((P, 4), dtype=_F32, device=dev))
-    with _on_device(dev):
-        rc = _lib.lib().r2_project_gaussians_backward(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                      s.data_ptr(), float(scale_modifier), r.data_ptr(), G.data_ptr(),
-                                                      out.xyz.data_ptr(), out.density.data_ptr(), out.scaling.data_ptr(),
-                                                      out.rotation.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_backward")
+    call("r2_project_gaussians_backward", dev, V, H, W, rays, int(bool(cone)), P, x, d, s, float(scale_modifier), r, G, *out)
     return out
 
 

@@ -24,19 +24,13 @@ import torch
 
 from . import _lib
 from . import projector
-from ._C import _on_device, _require_gpu, _stream
-
-_F32 = torch.float32
+from ._boundary import _F32, call, cloud, f32c, require_gpu, workspace
 
 
 def world_ray_params(views):
     """[V,12] float32 ray parameters {a, p00, pu, pv} of ``views`` (``scene.View`` list) in world coordinates: what
     ``projector.ray_params`` gives for a unit voxel grid whose index coordinates are the world's."""
     return projector.ray_params(views, (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), (1, 1, 1))
-
-
-def _f32c(t):
-    return t if t.dtype == _F32 and t.is_contiguous() else t.to(_F32).contiguous()
 
 
 _PLAN_SOURCES = ("rays", "xyz", "density", "scaling", "rotation")
@@ -81,18 +75,21 @@ class ProjectionPlan:
         return self.offsets.data_ptr(), self.ids.data_ptr(), self.ids.numel()
 
 
+def _call_planned(name, plan, dev, *args):
+    """``_boundary.call`` of the entry ``name``, or, with a plan, of ``name + "_planned"``: the planned entries take the plan's
+    three arguments last before the stream (``_lib._SIGNATURES``)."""
+    if plan is None:
+        return call(name, dev, *args)
+    return call(name + "_planned", dev, *args, *plan._args())
+
+
 def _plan_count(rays, cone, H, W, x, d, s, r, scale_modifier):
     """``r2_project_gaussians_plan_count`` on kernel-ready tensors -> (offsets, the workspace that holds the table)."""
     V, P, dev = rays.shape[0], x.shape[0], x.device
-    L = _lib.lib()
     T = ((H + 15) // 16) * ((W + 15) // 16)
     offsets = torch.empty((V * T + 1,), dtype=torch.int64, device=dev)
-    ws = torch.empty((max(int(L.r2_project_gaussians_plan_workspace_bytes(V, H, W, P)), 1),), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = L.r2_project_gaussians_plan_count(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                               float(scale_modifier), r.data_ptr(), offsets.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_plan_count")
+    ws = workspace(_lib.lib().r2_project_gaussians_plan_workspace_bytes(V, H, W, P), dev, at_least=1)
+    call("r2_project_gaussians_plan_count", dev, V, H, W, rays, cone, P, x, d, s, float(scale_modifier), r, offsets, ws, ws.numel())
     return offsets, ws
 
 
@@ -100,12 +97,8 @@ def _plan_fill(rays, cone, H, W, x, d, s, r, scale_modifier, offsets, ws, instan
     """``r2_project_gaussians_plan_fill`` after ``_plan_count`` -> ids [instances]."""
     V, P, dev = rays.shape[0], x.shape[0], x.device
     ids = torch.empty((instances,), dtype=torch.int32, device=dev)
-    with _on_device(dev):
-        rc = _lib.lib().r2_project_gaussians_plan_fill(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                       float(scale_modifier), r.data_ptr(), offsets.data_ptr(),
-                                                       ids.data_ptr() if instances else None, instances, ws.data_ptr(), ws.numel(),
-                                                       _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_plan_fill")
+    call("r2_project_gaussians_plan_fill", dev, V, H, W, rays, cone, P, x, d, s, float(scale_modifier), r, offsets,
+         ids if instances else None, instances, ws, ws.numel())
     return ids
 
 
@@ -125,7 +118,7 @@ def plan_projection_rays(rays, cone, H, W, xyz, density, scaling, rotation, scal
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
     rdev = projector.device_rays(rays.detach(), dev)
-    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    x, d, s, r = cloud(xyz, density, scaling, rotation)
     c = int(bool(cone))
     offsets, ws = _plan_count(rdev, c, H, W, x, d, s, r, scale_modifier)
     instances = int(offsets[-1])   # the one host read
@@ -171,17 +164,9 @@ class _ProjectGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, density, scaling, rotation, rays, cone, H, W, scale_modifier, out, plan=None):
         V, P = rays.shape[0], xyz.shape[0]
-        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+        x, d, s, r = cloud(xyz, density, scaling, rotation)
         rays = rays.detach()
-        with _on_device(x.device):
-            if plan is None:
-                rc = _lib.lib().r2_project_gaussians(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                     float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(x.device))
-            else:
-                rc = _lib.lib().r2_project_gaussians_planned(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
-                                                             s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(),
-                                                             *plan._args(), _stream(x.device))
-        _lib.check(rc, "r2_project_gaussians" if plan is None else "r2_project_gaussians_planned")
+        _call_planned("r2_project_gaussians", plan, x.device, V, H, W, rays, cone, P, x, d, s, float(scale_modifier), r, out)
         ctx.save_for_backward(x, d, s, r, rays)
         ctx.args = (cone, H, W, float(scale_modifier))
         ctx.plan = plan
@@ -193,31 +178,16 @@ class _ProjectGaussians(torch.autograd.Function):
         x, d, s, r, rays = ctx.saved_tensors
         cone, H, W, mod = ctx.args
         V, P = rays.shape[0], x.shape[0]
-        G = _f32c(G)
-        L = _lib.lib()
+        G = f32c(G)
         gx = gd = gs = gr = grays = None
         if any(ctx.needs_input_grad[:4]):
             gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
-            with _on_device(x.device):
-                rc = L.r2_project_gaussians_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                     mod, r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(),
-                                                     gr.data_ptr(), _stream(x.device))
-            _lib.check(rc, "r2_project_gaussians_backward")
+            call("r2_project_gaussians_backward", x.device, V, H, W, rays, cone, P, x, d, s, mod, r, G, gx, gd, gs, gr)
         if ctx.needs_input_grad[4]:
             grays = torch.empty_like(rays)
-            ws = torch.empty((max(int(L.r2_project_gaussians_rays_backward_workspace_bytes(V, H, W)), 1),), dtype=torch.uint8,
-                             device=x.device)
-            with _on_device(x.device):
-                if ctx.plan is None:
-                    rc = L.r2_project_gaussians_rays_backward(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
-                                                              s.data_ptr(), mod, r.data_ptr(), G.data_ptr(), grays.data_ptr(),
-                                                              ws.data_ptr(), ws.numel(), _stream(x.device))
-                else:
-                    rc = L.r2_project_gaussians_rays_backward_planned(V, H, W, rays.data_ptr(), cone, P, x.data_ptr(), d.data_ptr(),
-                                                                      s.data_ptr(), mod, r.data_ptr(), G.data_ptr(),
-                                                                      grays.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                                      *ctx.plan._args(), _stream(x.device))
-            _lib.check(rc, "r2_project_gaussians_rays_backward" if ctx.plan is None else "r2_project_gaussians_rays_backward_planned")
+            ws = workspace(_lib.lib().r2_project_gaussians_rays_backward_workspace_bytes(V, H, W), x.device, at_least=1)
+            _call_planned("r2_project_gaussians_rays_backward", ctx.plan, x.device, V, H, W, rays, cone, P, x, d, s, mod, r, G, grays,
+                          ws, ws.numel())
         return gx, gd, gs, gr, grays, None, None, None, None, None, None
 
 
@@ -287,18 +257,10 @@ def _ray_jacobian(rays, cone, H, W, xyz, density, scaling, rotation, scale_modif
     plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
     rays = projector.device_rays(rays.detach(), dev)
-    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    x, d, s, r = cloud(xyz, density, scaling, rotation)
     out = torch.empty((V, 6, H, W), dtype=_F32, device=dev)
-    L = _lib.lib()
-    with _on_device(dev):
-        if plan is None:
-            rc = L.r2_project_gaussians_ray_jacobian(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                     s.data_ptr(), float(scale_modifier), r.data_ptr(), out.data_ptr(), _stream(dev))
-        else:
-            rc = L.r2_project_gaussians_ray_jacobian_planned(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(),
-                                                             d.data_ptr(), s.data_ptr(), float(scale_modifier), r.data_ptr(),
-                                                             out.data_ptr(), *plan._args(), _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_ray_jacobian" if plan is None else "r2_project_gaussians_ray_jacobian_planned")
+    _call_planned("r2_project_gaussians_ray_jacobian", plan, dev, V, H, W, rays, int(bool(cone)), P, x, d, s, float(scale_modifier),
+                  r, out)
     return out
 
 
@@ -340,16 +302,10 @@ def project_gaussians_rays_jvp(rays, cone, H, W, xyz, density, scaling, rotation
         from .uncertainty import _check_group_tuple
         tx, td, ts, tr = _check_group_tuple(tangents, P, dev, "tangents")
         rdev = projector.device_rays(rays.detach(), dev)
-        x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+        x, d, s, r = cloud(xyz, density, scaling, rotation)
         out = torch.empty((V, H, W), dtype=_F32, device=dev)
-        args = (V, H, W, rdev.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(), s.data_ptr(), float(scale_modifier),
-                r.data_ptr(), tx.data_ptr(), td.data_ptr(), ts.data_ptr(), tr.data_ptr(), out.data_ptr())
-        with _on_device(dev):
-            if plan is None:
-                rc = _lib.lib().r2_project_gaussians_jvp(*args, _stream(dev))
-            else:
-                rc = _lib.lib().r2_project_gaussians_jvp_planned(*args, *plan._args(), _stream(dev))
-        _lib.check(rc, "r2_project_gaussians_jvp" if plan is None else "r2_project_gaussians_jvp_planned")
+        _call_planned("r2_project_gaussians_jvp", plan, dev, V, H, W, rdev, int(bool(cone)), P, x, d, s, float(scale_modifier), r,
+                      tx, td, ts, tr, out)
     if ray_tangent is not None:
         ray_tangent = torch.as_tensor(ray_tangent)
         if tuple(ray_tangent.shape) != (V, 12):
@@ -380,7 +336,7 @@ def _integrate_forward(ctx, entries, origins, directions, xyz, density, scaling,
     orders, by gathers alone."""
     from .field import inverse_permutation
     N, P = origins.shape[0], xyz.shape[0]
-    x, d, s, r = _f32c(xyz.detach()), _f32c(density.detach()), _f32c(scaling.detach()), _f32c(rotation.detach())
+    x, d, s, r = cloud(xyz, density, scaling, rotation)
     ginv = None
     if gperm is not None:
         x, d, s, r = (t[gperm].contiguous() for t in (x, d, s, r))
@@ -390,13 +346,8 @@ def _integrate_forward(ctx, entries, origins, directions, xyz, density, scaling,
     if perm is not None:
         rays, inv = rays[perm].contiguous(), inverse_permutation(perm)
     out = torch.empty((N,), dtype=_F32, device=x.device)
-    L = _lib.lib()
-    ws = torch.empty((max(int(getattr(L, entries[2])(N, P)), 1),), dtype=torch.uint8, device=x.device)
-    with _on_device(x.device):
-        rc = getattr(L, entries[0])(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                    float(scale_modifier), r.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    _stream(x.device))
-    _lib.check(rc, entries[0])
+    ws = workspace(getattr(_lib.lib(), entries[2])(N, P), x.device, at_least=1)
+    call(entries[0], x.device, N, rays, half_line, P, x, d, s, float(scale_modifier), r, out, ws, ws.numel())
     ctx.save_for_backward(rays, x, d, s, r, perm, inv, ginv)
     ctx.args = (float(scale_modifier), half_line)
     return out if inv is None else out[inv]
@@ -406,18 +357,13 @@ def _integrate_backward(ctx, entries, G):
     rays, x, d, s, r, perm, inv, ginv = ctx.saved_tensors
     mod, half_line = ctx.args
     N, P = rays.shape[0], x.shape[0]
-    G = _f32c(G)
+    G = f32c(G)
     if perm is not None:
         G = G[perm].contiguous()
     gx, gd, gs, gr = torch.empty_like(x), torch.empty_like(d), torch.empty_like(s), torch.empty_like(r)
     grays = torch.empty_like(rays) if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] else None
-    L = _lib.lib()
-    ws = torch.empty((max(int(getattr(L, entries[2])(N, P)), 1),), dtype=torch.uint8, device=x.device)
-    with _on_device(x.device):
-        rc = getattr(L, entries[1])(N, rays.data_ptr(), half_line, P, x.data_ptr(), d.data_ptr(), s.data_ptr(), mod,
-                                    r.data_ptr(), G.data_ptr(), gx.data_ptr(), gd.data_ptr(), gs.data_ptr(), gr.data_ptr(),
-                                    None if grays is None else grays.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x.device))
-    _lib.check(rc, entries[1])
+    ws = workspace(getattr(_lib.lib(), entries[2])(N, P), x.device, at_least=1)
+    call(entries[1], x.device, N, rays, half_line, P, x, d, s, mod, r, G, gx, gd, gs, gr, grays, ws, ws.numel())
     if ginv is not None:
         gx, gd, gs, gr = gx[ginv], gd[ginv], gs[ginv], gr[ginv]
     go = gdir = None
@@ -553,8 +499,8 @@ def integrate_rays(origins, directions, xyz, density, scaling, rotation, scale_m
             raise ValueError("%s must be a tensor [..., 3], got %s" % (name, tuple(getattr(t, "shape", ()))))
     if origins.shape != directions.shape:
         raise ValueError("origins and directions differ in shape: %s, %s" % (tuple(origins.shape), tuple(directions.shape)))
-    _require_gpu(origins, "origins")
-    _require_gpu(directions, "directions")
+    require_gpu(origins, "origins")
+    require_gpu(directions, "directions")
     from .field import _check_cloud
     _check_cloud(xyz, density, scaling, rotation)
     if origins.device != xyz.device or directions.device != xyz.device:

@@ -14,15 +14,13 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
 from . import densify as D
-from ._C import _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, ptr_table, require_gpu
 
 NAMES = ("xyz", "density", "scaling", "rotation")
 WIDTHS = {"xyz": 3, "density": 1, "scaling": 3, "rotation": 4}
 BETAS, ADAM_EPS = (0.9, 0.999), 1e-15      # gaussian_model.py:213 (torch.optim.Adam defaults, eps 1e-15)
 EPS = 1e-5                                  # gaussian_model.py:34: keeps the initial scales inside the bound
-_F32 = torch.float32
 
 
 def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
@@ -48,26 +46,16 @@ def _bound(scale_bound):
     return lo, hi
 
 
-def _ptrs(ts):
-    arr = (C.c_void_p * 4)()
-    for i, t in enumerate(ts):
-        arr[i] = None if t is None else t.data_ptr()
-    return arr
-
-
 def activate(density, scaling, rotation, scale_bound=None):
     """-> (density_act [P,1], scaling_act [P,3], rotation_act [P,4]) of raw parameters: one launch (r2_gaussian_activate)."""
-    _require_gpu(density, "density")
+    require_gpu(density, "density")
     P = density.shape[0]
     dev = density.device
     lo, hi = _bound(scale_bound)
     ins = [t.detach().to(_F32).contiguous() for t in (density, scaling, rotation)]
     assert [tuple(t.shape) for t in ins] == [(P, 1), (P, 3), (P, 4)]
     outs = [torch.empty((P, w), dtype=_F32, device=dev) for w in (1, 3, 4)]
-    with _on_device(dev):
-        rc = _lib.lib().r2_gaussian_activate(P, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), lo, hi,
-                                             outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_gaussian_activate")
+    call("r2_gaussian_activate", dev, P, *ins, lo, hi, *outs)
     return tuple(outs)
 
 
@@ -219,12 +207,9 @@ class GaussianModel:
             bc2 = (C.c_double * 4)(*[1.0 - BETAS[1] ** self.steps[n] if g is not None else 1.0 for n, g in zip(NAMES, grads)])
             lo, hi = _bound(self.scale_bound)
             a = self._act
-            with _on_device(self.device):
-                rc = _lib.lib().r2_gaussian_adam_step(
-                    self.P, _ptrs([self._raw[n] for n in NAMES]), _ptrs(grads), _ptrs([self.exp_avg[n] for n in NAMES]),
-                    _ptrs([self.exp_avg_sq[n] for n in NAMES]), lrs, bc1, bc2, lo, hi, a["density"].data_ptr(),
-                    a["scaling"].data_ptr(), a["rotation"].data_ptr(), _stream(self.device))
-            _lib.check(rc, "r2_gaussian_adam_step")
+            call("r2_gaussian_adam_step", self.device, self.P, ptr_table([self._raw[n] for n in NAMES]), ptr_table(grads),
+                 ptr_table([self.exp_avg[n] for n in NAMES]), ptr_table([self.exp_avg_sq[n] for n in NAMES]), lrs, bc1, bc2, lo, hi,
+                 a["density"], a["scaling"], a["rotation"])
         for t in leaves:
             t.grad = None
 

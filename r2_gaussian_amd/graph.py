@@ -10,7 +10,7 @@ operators), so rebuild the graph from ``xyz.detach()`` whenever the cloud has mo
 import torch
 
 from . import _lib
-from ._C import _F32, _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, require_gpu, workspace
 
 _I32 = torch.int32
 KINDS = {"l1": _lib.R2_GRAPH_KIND_L1, "l2": _lib.R2_GRAPH_KIND_L2, "huber": _lib.R2_GRAPH_KIND_HUBER}
@@ -31,15 +31,11 @@ class NeighbourGraph:
 def _transpose(idx):
     P, K = idx.shape
     dev = idx.device
-    L = _lib.lib()
     in_offsets = torch.empty((P + 1,), dtype=_I32, device=dev)
     in_edges = torch.empty((P * K,), dtype=_I32, device=dev)
-    nbytes = int(L.r2_graph_transpose_workspace_bytes(P, K))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = L.r2_graph_transpose(P, K, idx.data_ptr() if P else None, in_offsets.data_ptr(), in_edges.data_ptr() if P else None,
-                                  ws.data_ptr() if nbytes else None, nbytes, _stream(dev))
-    _lib.check(rc, "r2_graph_transpose")
+    nbytes = int(_lib.lib().r2_graph_transpose_workspace_bytes(P, K))
+    ws = workspace(nbytes, dev)
+    call("r2_graph_transpose", dev, P, K, idx if P else None, in_offsets, in_edges if P else None, ws if nbytes else None, nbytes)
     return in_offsets, in_edges
 
 
@@ -47,22 +43,18 @@ def knn_graph(xyz, k):
     """The k nearest neighbours of every point of xyz [P, 3] (float32 on the GPU), ordered by (squared distance, index), self
     excluded by index, and the transposed graph, built on the tensor's device and current stream.  Rows of fewer than k
     neighbours (P - 1 < k) end in idx = -1, dist2 = +inf.  1 <= k <= 16."""
-    _require_gpu(xyz, "xyz")
+    require_gpu(xyz, "xyz")
     if xyz.ndim != 2 or xyz.shape[1] != 3:
         raise ValueError("xyz must have dimensions (num_points, 3), got %s" % (tuple(xyz.shape),))
     dev = xyz.device
     pts = xyz.detach().to(_F32).contiguous()
     P, K = int(pts.shape[0]), int(k)
-    L = _lib.lib()
     idx = torch.empty((P, max(K, 0)), dtype=_I32, device=dev)
     dist2 = torch.empty((P, max(K, 0)), dtype=_F32, device=dev)
     # the library does not allocate: the grid search's workspace comes from torch's allocator
-    nbytes = int(L.r2_knn_graph_workspace_bytes(P, K))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with _on_device(dev):
-        rc = L.r2_knn_graph(P, pts.data_ptr() if P else None, K, idx.data_ptr() if P else None, dist2.data_ptr() if P else None,
-                            ws.data_ptr() if nbytes else None, nbytes, _stream(dev))
-    _lib.check(rc, "r2_knn_graph")
+    nbytes = int(_lib.lib().r2_knn_graph_workspace_bytes(P, K))
+    ws = workspace(nbytes, dev)
+    call("r2_knn_graph", dev, P, pts if P else None, K, idx if P else None, dist2 if P else None, ws if nbytes else None, nbytes)
     in_offsets, in_edges = _transpose(idx)
     return NeighbourGraph(idx, dist2, in_offsets, in_edges, P * min(K, max(P - 1, 0)))
 
@@ -70,7 +62,7 @@ def knn_graph(xyz, k):
 def graph_from_indices(idx):
     """A caller-made graph: idx [P, K] integer tensor on the GPU, row i = the targets of node i's edges, anything outside [0, P)
     = no edge.  Transpose only (dist2 = None).  Reads the number of valid edges back from in_offsets[P]: one host read."""
-    _require_gpu(idx, "idx")
+    require_gpu(idx, "idx")
     if idx.ndim != 2 or idx.shape[1] < 1:
         raise ValueError("idx must have dimensions (num_points, K >= 1), got %s" % (tuple(idx.shape),))
     idx = idx.to(_I32).contiguous()
@@ -101,14 +93,10 @@ class _GraphSmoothness(torch.autograd.Function):
         v = values.detach().to(_F32).contiguous().view(-1)
         dev = v.device
         P, K = graph.P, graph.K
-        L = _lib.lib()
-        scratch = torch.empty(int(L.r2_graph_loss_scratch_floats(P, K)), dtype=_F32, device=dev)
+        scratch = torch.empty(int(_lib.lib().r2_graph_loss_scratch_floats(P, K)), dtype=_F32, device=dev)
         loss = torch.empty(1, dtype=_F32, device=dev)
-        with _on_device(dev):
-            rc = L.r2_graph_loss(P, K, v.data_ptr() if P else None, graph.idx.data_ptr() if P else None,
-                                 weights.data_ptr() if weights is not None and P else None, kind, delta, scale,
-                                 scratch.data_ptr(), loss.data_ptr(), _stream(dev))
-        _lib.check(rc, "r2_graph_loss")
+        call("r2_graph_loss", dev, P, K, v if P else None, graph.idx if P else None, weights if P else None, kind, delta, scale,
+             scratch, loss)
         ctx.save_for_backward(v)
         ctx.graph, ctx.weights, ctx.args = graph, weights, (kind, delta, scale)
         ctx.shape, ctx.dtype = values.shape, values.dtype
@@ -124,11 +112,7 @@ class _GraphSmoothness(torch.autograd.Function):
         grad = torch.empty(P, dtype=_F32, device=dev)
         if P:
             gd = g.detach().to(_F32).contiguous().view(1)
-            with _on_device(dev):
-                rc = _lib.lib().r2_graph_loss_backward(P, K, v.data_ptr(), graph.idx.data_ptr(), w.data_ptr() if w is not None else None,
-                                                       graph.in_offsets.data_ptr(), graph.in_edges.data_ptr(), kind, delta, scale,
-                                                       gd.data_ptr(), grad.data_ptr(), _stream(dev))
-            _lib.check(rc, "r2_graph_loss_backward")
+            call("r2_graph_loss_backward", dev, P, K, v, graph.idx, w, graph.in_offsets, graph.in_edges, kind, delta, scale, gd, grad)
         return grad.view(ctx.shape).to(ctx.dtype), None, None, None, None, None
 
 
@@ -137,7 +121,7 @@ def graph_smoothness(values, graph, weights=None, kind="l1", delta=None, reducti
     in ``values`` ([P] or [P, 1]) only.  kind: "l1" |x|, "l2" x^2, "huber" (needs delta > 0).  weights: None (1) or [P, K]
     non-negative (edge_weights).  reduction: "mean" (scale = 1 / max(valid edges, 1)) or "sum".  Shapes that disagree with
     the graph raise ValueError."""
-    _require_gpu(values, "values")
+    require_gpu(values, "values")
     if kind not in KINDS:
         raise ValueError("kind must be one of %s, got %r" % (sorted(KINDS), kind))
     if reduction not in ("mean", "sum"):

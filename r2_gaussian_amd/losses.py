@@ -4,14 +4,10 @@ autograd node whose forward already computes the gradient (two / one kernel laun
 vendor convolution).  The results are device scalars: nothing here synchronises with the host (train.py:204-209 calls
 ``.item()`` on every loss every iteration; read the tensors only when something is logged).
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._C import _on_device, _require_gpu, _stream
-
-_F32 = torch.float32
+from ._boundary import _F32, call, ptr_table, require_gpu
 
 
 def _check_image_shapes(image, gt):
@@ -28,18 +24,14 @@ class _ImageLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, gt, w_l1, w_ssim):
         _check_image_shapes(image, gt)
-        _require_gpu(image, "image")
+        require_gpu(image, "image")
         img = image.reshape(image.shape[-2], image.shape[-1]).to(_F32).contiguous()
         ref = gt.reshape(gt.shape[-2], gt.shape[-1]).to(device=img.device, dtype=_F32).contiguous()
         H, W = img.shape
-        L = _lib.lib()
         grad = torch.empty_like(img)
-        scratch = torch.empty(L.r2_loss_l1_ssim_scratch_floats(W, H), dtype=_F32, device=img.device)
+        scratch = torch.empty(_lib.lib().r2_loss_l1_ssim_scratch_floats(W, H), dtype=_F32, device=img.device)
         scalars = torch.empty(3, dtype=_F32, device=img.device)
-        with _on_device(img.device):
-            rc = L.r2_loss_l1_ssim(W, H, img.data_ptr(), ref.data_ptr(), float(w_l1), float(w_ssim), grad.data_ptr(),
-                                   scratch.data_ptr(), scalars.data_ptr(), _stream(img.device))
-        _lib.check(rc, "r2_loss_l1_ssim")
+        call("r2_loss_l1_ssim", img.device, W, H, img, ref, float(w_l1), float(w_ssim), grad, scratch, scalars)
         ctx.save_for_backward(grad)
         ctx.shape, ctx.dtype = image.shape, image.dtype
         ctx.mark_non_differentiable(scalars)
@@ -82,21 +74,17 @@ class _ImageLossBatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, images, gts, w_l1, w_ssim):
         _check_batch_shapes(images, gts)
-        _require_gpu(images, "images")
+        require_gpu(images, "images")
         img = images.to(_F32).contiguous()
         V, H, W = img.shape
         # the ground truths are read where they lie; only one on another device / of another type / strided is converted
         refs = list(gts.to(device=img.device, dtype=_F32).contiguous()) if torch.is_tensor(gts) else [
             t.reshape(H, W).to(device=img.device, dtype=_F32).contiguous() for t in gts]
-        table = (C.c_void_p * V)(*[t.data_ptr() for t in refs])
-        L = _lib.lib()
         grad = torch.empty_like(img)
-        scratch = torch.empty(L.r2_loss_l1_ssim_batch_scratch_floats(V, W, H), dtype=_F32, device=img.device)
+        scratch = torch.empty(_lib.lib().r2_loss_l1_ssim_batch_scratch_floats(V, W, H), dtype=_F32, device=img.device)
         scalars = torch.empty((V + 1, 3), dtype=_F32, device=img.device)
-        with _on_device(img.device):
-            rc = L.r2_loss_l1_ssim_batch(V, W, H, img.data_ptr(), table, float(w_l1), float(w_ssim), grad.data_ptr(),
-                                         scratch.data_ptr(), scalars.data_ptr(), _stream(img.device))
-        _lib.check(rc, "r2_loss_l1_ssim_batch")
+        call("r2_loss_l1_ssim_batch", img.device, V, W, H, img, ptr_table(refs), float(w_l1), float(w_ssim), grad, scratch,
+             scalars)
         ctx.save_for_backward(grad)
         ctx.dtype = images.dtype
         ctx.mark_non_differentiable(scalars)
@@ -121,17 +109,13 @@ def image_loss_batch(images, gts, lambda_dssim=0.25):
 class _TV3D(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vol):
-        _require_gpu(vol, "vol")
+        require_gpu(vol, "vol")
         v = vol.to(_F32).contiguous()
         nx, ny, nz = v.shape
-        L = _lib.lib()
         grad = torch.empty_like(v)
-        scratch = torch.empty(L.r2_loss_tv3d_scratch_floats(nx, ny, nz), dtype=_F32, device=v.device)
+        scratch = torch.empty(_lib.lib().r2_loss_tv3d_scratch_floats(nx, ny, nz), dtype=_F32, device=v.device)
         scalars = torch.empty(2, dtype=_F32, device=v.device)
-        with _on_device(v.device):
-            rc = L.r2_loss_tv3d(nx, ny, nz, v.data_ptr(), 1.0, grad.data_ptr(), scratch.data_ptr(), scalars.data_ptr(),
-                                _stream(v.device))
-        _lib.check(rc, "r2_loss_tv3d")
+        call("r2_loss_tv3d", v.device, nx, ny, nz, v, 1.0, grad, scratch, scalars)
         ctx.save_for_backward(grad)
         ctx.dtype = vol.dtype
         return scalars[0]

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._C import _F32, _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, require_gpu, workspace
 from .graph import NeighbourGraph, knn_graph
 
 _I32 = torch.int32
@@ -33,7 +33,7 @@ def _params(graph, xyz, density, scaling, rotation):
     dev = _check_graph(graph)
     out = []
     for (name, w), t in zip(_WIDTHS, (xyz, density, scaling, rotation)):
-        _require_gpu(t, name)
+        require_gpu(t, name)
         if name == "density" and t.ndim == 1:
             t = t[:, None]
         if t.ndim != 2 or tuple(t.shape) != (graph.P, w):
@@ -45,14 +45,14 @@ def _params(graph, xyz, density, scaling, rotation):
 
 
 def _edge_array(graph, t, name, dtype):
-    _require_gpu(t, name)
+    require_gpu(t, name)
     if tuple(t.shape) != (graph.P, graph.K) or t.device != graph.idx.device:
         raise ValueError("%s must be [P, K] = [%d, %d] on the graph's device, got %s" % (name, graph.P, graph.K, tuple(t.shape)))
     return t.detach().to(dtype).contiguous()
 
 
 def _node_array(graph, t, name):
-    _require_gpu(t, name)
+    require_gpu(t, name)
     if tuple(t.shape) != (graph.P,) or t.device != graph.idx.device:
         raise ValueError("%s must be [P] = [%d] on the graph's device, got %s" % (name, graph.P, tuple(t.shape)))
     return t.detach().to(_I32).contiguous()
@@ -81,10 +81,7 @@ def merge_costs(graph, xyz, density, scaling, rotation, max_scale=None):
     dev, P, K = graph.idx.device, graph.P, graph.K
     cost = torch.empty((P, K), dtype=_F32, device=dev)
     if P:
-        with _on_device(dev):
-            rc = _lib.lib().r2_merge_cost(P, K, graph.idx.data_ptr(), p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(),
-                                          p[3].data_ptr(), max_trace, cost.data_ptr(), _stream(dev))
-        _lib.check(rc, "r2_merge_cost")
+        call("r2_merge_cost", dev, P, K, graph.idx, *p, max_trace, cost)
     return cost
 
 
@@ -100,13 +97,9 @@ def match_edges(graph, cost, max_cost, rounds=12):
     dev, P, K = graph.idx.device, graph.P, graph.K
     mate = torch.empty((P,), dtype=_I32, device=dev)
     if P:
-        L = _lib.lib()
-        nbytes = int(L.r2_graph_match_workspace_bytes(P))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        with _on_device(dev):
-            rc = L.r2_graph_match(P, K, graph.idx.data_ptr(), graph.in_offsets.data_ptr(), graph.in_edges.data_ptr(),
-                                  cost.data_ptr(), float(max_cost), rounds, mate.data_ptr(), ws.data_ptr(), nbytes, _stream(dev))
-        _lib.check(rc, "r2_graph_match")
+        nbytes = int(_lib.lib().r2_graph_match_workspace_bytes(P))
+        ws = workspace(nbytes, dev)
+        call("r2_graph_match", dev, P, K, graph.idx, graph.in_offsets, graph.in_edges, cost, float(max_cost), rounds, mate, ws, nbytes)
     return mate
 
 
@@ -122,22 +115,15 @@ def merge_pairs(graph, cost, max_cost, mate, xyz, density, scaling, rotation):
     dev, P, K = graph.idx.device, graph.P, graph.K
     if P == 0:
         return p[0], p[1], p[2], p[3], torch.empty((0, 2), dtype=_I32, device=dev), dict(pairs=0, open=0, P=0)
-    L = _lib.lib()
-    scratch = torch.empty((int(L.r2_merge_scratch_bytes(P)),), dtype=torch.uint8, device=dev)
+    scratch = torch.empty((int(_lib.lib().r2_merge_scratch_bytes(P)),), dtype=torch.uint8, device=dev)
     counts = (C.c_uint * 2)()
-    with _on_device(dev):
-        rc = L.r2_merge_count(P, K, graph.idx.data_ptr(), graph.in_offsets.data_ptr(), graph.in_edges.data_ptr(), cost.data_ptr(),
-                              float(max_cost), mate.data_ptr(), p[1].data_ptr(), p[2].data_ptr(), scratch.data_ptr(), counts,
-                              _stream(dev))
-        _lib.check(rc, "r2_merge_count")
-        pairs, n_open = int(counts[0]), int(counts[1])
-        Pn = P - pairs
-        outs = [torch.empty((Pn, w), dtype=_F32, device=dev) for _n, w in _WIDTHS]
-        src = torch.empty((Pn, 2), dtype=_I32, device=dev)
-        rc = L.r2_merge_emit(P, p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), p[3].data_ptr(), scratch.data_ptr(), Pn,
-                             outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), src.data_ptr(),
-                             _stream(dev))
-        _lib.check(rc, "r2_merge_emit")
+    call("r2_merge_count", dev, P, K, graph.idx, graph.in_offsets, graph.in_edges, cost, float(max_cost), mate, p[1], p[2], scratch,
+         counts)
+    pairs, n_open = int(counts[0]), int(counts[1])
+    Pn = P - pairs
+    outs = [torch.empty((Pn, w), dtype=_F32, device=dev) for _n, w in _WIDTHS]
+    src = torch.empty((Pn, 2), dtype=_I32, device=dev)
+    call("r2_merge_emit", dev, P, *p, scratch, Pn, *outs, src)
     return outs[0], outs[1], outs[2], outs[3], src, dict(pairs=pairs, open=n_open, P=Pn)
 
 
@@ -146,7 +132,7 @@ def merge_gaussians(xyz, density, scaling, rotation, max_cost, k=8, rounds=12, m
     with cost <= max_cost, the merged cloud.  max_cost is capped at the largest finite float32: an edge whose cost is +inf
     (unusable parameters, a trace beyond max_scale^2) is never merged here, whereas match_edges with max_cost = +inf takes its
     costs literally.  -> merge_pairs' tuple."""
-    _require_gpu(xyz, "xyz")
+    require_gpu(xyz, "xyz")
     max_cost = min(float(max_cost), float(np.finfo(np.float32).max))
     if graph is None:
         graph = knn_graph(xyz, k)

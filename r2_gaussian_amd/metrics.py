@@ -18,9 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._C import _on_device, _stream
-
-_F32 = torch.float32
+from ._boundary import _F32, call
 
 
 def _to_device(t, device=None):
@@ -64,12 +62,9 @@ def _run(gt, pred, perm, axes, flags, out):
     saxes = [perm.index(a) for a in axes]
     scratch = torch.empty(max(L.r2_metric_slices_scratch_floats(*n, a) for a in saxes), dtype=_F32, device=g.device)
     row = 0
-    with _on_device(g.device):
-        for a in saxes:
-            rc = L.r2_metric_slices(*n, a, g.data_ptr(), p.data_ptr(), flags, out[row:].data_ptr(), scratch.data_ptr(),
-                                    _stream(g.device))
-            _lib.check(rc, "r2_metric_slices")
-            row += n[a]
+    for a in saxes:
+        call("r2_metric_slices", g.device, *n, a, g, p, flags, out[row:], scratch)
+        row += n[a]
     return out
 
 

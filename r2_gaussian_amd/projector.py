@@ -28,9 +28,8 @@ import torch
 
 from . import _lib
 from . import scene as S
-from ._C import _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, f32c, require_gpu
 
-_F32 = torch.float32
 PROJECTION_TYPES = ("interpolated", "siddon")
 # (direction, projection_type) -> the C function and whether it takes ``accuracy``
 _ENTRY_POINTS = {
@@ -77,13 +76,9 @@ def _check_extent(sVoxel, center):
 def _check_operand(t, name, layout, projection_type):
     """The model first, then the GPU requirement, then the operand's rank."""
     check_projection_type(projection_type)
-    _require_gpu(t, name)
+    require_gpu(t, name)
     if t.dim() != 3:
         raise ValueError("%s must be %s, got shape %s" % (name, layout, tuple(t.shape)))
-
-
-def _f32c(t):
-    return t if t.dtype == _F32 and t.is_contiguous() else t.to(_F32).contiguous()
 
 
 def device_rays(rays, device):
@@ -95,8 +90,8 @@ def device_rays(rays, device):
     if rays.is_cuda:
         if rays.device != device:
             raise ValueError("rays are on %s, the operand on %s" % (rays.device, device))
-        return _f32c(rays)
-    return _f32c(rays).pin_memory().to(device, non_blocking=True)
+        return f32c(rays)
+    return f32c(rays).pin_memory().to(device, non_blocking=True)
 
 
 def _output(out, shape, device, layout):
@@ -131,12 +126,10 @@ def _voxel_sizes(dVoxel):
 def _launch(direction, projection_type, rays, cone, H, W, nVoxel, dVoxel, accuracy, src, dst):
     """``dst`` = A ``src`` ("project") or A^T ``src`` ("backproject") on checked, contiguous float32 GPU operands."""
     name, takes_accuracy = _ENTRY_POINTS[direction, projection_type]
-    args = [rays.shape[0], H, W, rays.data_ptr(), int(bool(cone))] + list(nVoxel) + list(dVoxel)
+    args = [rays.shape[0], H, W, rays, int(bool(cone))] + list(nVoxel) + list(dVoxel)
     if takes_accuracy:
         args.append(float(accuracy))
-    with _on_device(src.device):
-        rc = getattr(_lib.lib(), name)(*args, src.data_ptr(), dst.data_ptr(), _stream(src.device))
-    _lib.check(rc, name)
+    call(name, src.device, *args, src, dst)
     return dst
 
 
@@ -180,7 +173,7 @@ def project_rays(vol, rays, cone, H, W, dVoxel, accuracy=0.5, out=None, projecti
     rays = device_rays(rays, vol.device)
     H, W = int(H), int(W)
     out = _output(out, (rays.shape[0], H, W), vol.device, "[%d,%d,%d]" % (rays.shape[0], H, W))
-    v32 = _f32c(vol)
+    v32 = f32c(vol)
     return _launch("project", projection_type, rays, cone, H, W, v32.shape, _voxel_sizes(dVoxel), accuracy, v32, out)
 
 
@@ -195,7 +188,7 @@ def backproject_rays(projs, rays, cone, nVoxel, dVoxel, accuracy=0.5, out=None, 
     if rays.shape[0] != V:
         raise ValueError("%d projections for %d views' rays" % (V, rays.shape[0]))
     out = _volume_output(out, nVoxel, projs.device)
-    return _launch("backproject", projection_type, rays, cone, H, W, out.shape, _voxel_sizes(dVoxel), accuracy, _f32c(projs),
+    return _launch("backproject", projection_type, rays, cone, H, W, out.shape, _voxel_sizes(dVoxel), accuracy, f32c(projs),
                    out)
 
 

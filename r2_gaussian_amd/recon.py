@@ -35,10 +35,8 @@ import torch
 from . import _lib
 from . import fdk as F
 from . import projector as P
-from ._C import _on_device, _require_gpu, _stream
+from ._boundary import _F32, call, require_gpu
 from .projector import Operator, _projections, backproject, backproject_views   # noqa: F401
-
-_F32 = torch.float32
 _F64 = torch.float64
 METHODS = ("fdk", "sart", "ossart", "asd_pocs", "os_asd_pocs", "cgls")
 
@@ -152,7 +150,7 @@ def _init(init, op):
 def tv_descent(vol, step, n_iter, scratch=None):
     """``n_iter`` steps x <- x - step g / |g|_2, g = grad TV_eps(x) (include/r2hip.h, r2_tv_descent), in place on ``vol``
     [nx,ny,nz] (contiguous float32, GPU).  ``step``: a float or a 0-d device tensor (read on the device).  -> vol."""
-    _require_gpu(vol, "vol")
+    require_gpu(vol, "vol")
     if vol.dim() != 3 or vol.dtype != _F32 or not vol.is_contiguous():
         raise ValueError("vol must be a contiguous float32 [nx,ny,nz] tensor")
     if int(n_iter) < 0:
@@ -162,14 +160,10 @@ def tv_descent(vol, step, n_iter, scratch=None):
     else:
         st = torch.full((), float(step), dtype=_F32, device=vol.device)
     nx, ny, nz = vol.shape
-    L = _lib.lib()
-    nbytes = int(L.r2_tv_descent_scratch_bytes(nx, ny, nz))
+    nbytes = int(_lib.lib().r2_tv_descent_scratch_bytes(nx, ny, nz))
     if scratch is None or scratch.numel() * scratch.element_size() < nbytes or scratch.device != vol.device:
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=vol.device)
-    with _on_device(vol.device):
-        rc = L.r2_tv_descent(nx, ny, nz, vol.data_ptr(), st.data_ptr(), int(n_iter), scratch.data_ptr(),
-                             scratch.numel() * scratch.element_size(), _stream(vol.device))
-    _lib.check(rc, "r2_tv_descent")
+    call("r2_tv_descent", vol.device, nx, ny, nz, vol, st, int(n_iter), scratch, scratch.numel() * scratch.element_size())
     return vol
 
 

@@ -21,13 +21,10 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib
 from . import projector
-from ._C import _on_device, _require_gpu, _stream
-from .field import _check_cloud, _f32c, inverse_permutation, morton_order
-from .gaussian_projector import check_projection_arguments, world_ray_params
-
-_F32 = torch.float32
+from ._boundary import _F32, call, cloud, f32c, require_gpu
+from .field import _check_cloud, inverse_permutation, morton_order
+from .gaussian_projector import _call_planned, _checked_plan, check_projection_arguments, world_ray_params
 
 CloudTuple = collections.namedtuple("CloudTuple", ("xyz", "density", "scaling", "rotation"))
 CloudTuple.__doc__ = "One float32 tensor per parameter group, in the shapes of the cloud: [P,3], [P,1], [P,3], [P,4]."
@@ -35,7 +32,8 @@ CloudTuple.__doc__ = "One float32 tensor per parameter group, in the shapes of t
 
 def _cloud(xyz, density, scaling, rotation):
     """Detached contiguous float32 copies (or the tensors themselves) for the kernels; density as [P]."""
-    return _f32c(xyz.detach()), _f32c(density.detach()).reshape(-1), _f32c(scaling.detach()), _f32c(rotation.detach())
+    x, d, s, r = cloud(xyz, density, scaling, rotation)
+    return x, d.reshape(-1), s, r
 
 
 def _check_group_tuple(t, P, device, name):
@@ -49,7 +47,7 @@ def _check_group_tuple(t, P, device, name):
             raise ValueError("%s.%s must be a tensor [%d,%d], got %s" % (name, g, P, cols, tuple(getattr(a, "shape", ()))))
         if a.device != device:
             raise ValueError("%s.%s is on %s, xyz on %s" % (name, g, a.device, device))
-        out.append(_f32c(a.detach()).reshape(-1) if cols == 1 else _f32c(a.detach()))
+        out.append(f32c(a.detach()).reshape(-1) if cols == 1 else f32c(a.detach()))
     return out
 
 
@@ -66,17 +64,12 @@ def fisher_diagonal_rays(rays, cone, H, W, xyz, density, scaling, rotation, weig
     if weights is not None:
         if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != (V, H, W) or weights.device != dev:
             raise ValueError("weights must be a tensor [%d,%d,%d] on %s, got %s" % (V, H, W, dev, tuple(getattr(weights, "shape", ()))))
-        weights = _f32c(weights.detach())
+        weights = f32c(weights.detach())
     rays = projector.device_rays(rays.detach(), dev)
     x, d, s, r = _cloud(xyz, density, scaling, rotation)
     F = CloudTuple(torch.empty((P, 3), dtype=_F32, device=dev), torch.empty((P, 1), dtype=_F32, device=dev),
                    torch.empty((P, 3), dtype=_F32, device=dev), torch.empty((P, 4), dtype=_F32, device=dev))
-    with _on_device(dev):
-        rc = _lib.lib().r2_project_gaussians_fisher(V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(),
-                                                    s.data_ptr(), float(scale_modifier), r.data_ptr(),
-                                                    None if weights is None else weights.data_ptr(), F.xyz.data_ptr(),
-                                                    F.density.data_ptr(), F.scaling.data_ptr(), F.rotation.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_fisher")
+    call("r2_project_gaussians_fisher", dev, V, H, W, rays, int(bool(cone)), P, x, d, s, float(scale_modifier), r, weights, *F)
     return F
 
 
@@ -112,13 +105,13 @@ def field_variance(points, xyz, density, scaling, rotation, variance, scale_modi
     differentiable.  No host synchronisation."""
     if not isinstance(points, torch.Tensor) or points.dim() < 1 or points.shape[-1] != 3:
         raise ValueError("points must be a tensor [..., 3], got %s" % (tuple(getattr(points, "shape", ())),))
-    _require_gpu(points, "points")
+    require_gpu(points, "points")
     _check_cloud(xyz, density, scaling, rotation)
     dev, P = xyz.device, xyz.shape[0]
     if points.device != dev:
         raise ValueError("points are on %s, xyz on %s" % (points.device, dev))
     vx, vd, vs, vr = _check_group_tuple(variance, P, dev, "variance")
-    pts = _f32c(points.detach().reshape(-1, 3))
+    pts = f32c(points.detach().reshape(-1, 3))
     N = pts.shape[0]
     if N >= (1 << 31):
         raise ValueError("fewer than 2^31 points, got %d" % N)
@@ -128,11 +121,7 @@ def field_variance(points, xyz, density, scaling, rotation, variance, scale_modi
         pts, inv = pts[perm].contiguous(), inverse_permutation(perm)
     x, d, s, r = _cloud(xyz, density, scaling, rotation)
     out = torch.empty((N,), dtype=_F32, device=dev)
-    with _on_device(dev):
-        rc = _lib.lib().r2_query_gaussians_variance(N, pts.data_ptr(), P, x.data_ptr(), d.data_ptr(), s.data_ptr(),
-                                                    float(scale_modifier), r.data_ptr(), vx.data_ptr(), vd.data_ptr(), vs.data_ptr(),
-                                                    vr.data_ptr(), out.data_ptr(), _stream(dev))
-    _lib.check(rc, "r2_query_gaussians_variance")
+    call("r2_query_gaussians_variance", dev, N, pts, P, x, d, s, float(scale_modifier), r, vx, vd, vs, vr, out)
     if inv is not None:
         out = out[inv]
     return out.reshape(points.shape[:-1])
@@ -144,7 +133,6 @@ def projection_variance_rays(rays, cone, H, W, xyz, density, scaling, rotation, 
     independent parameter variances ``variance``.  Not differentiable.  No host synchronisation.  ``plan``: a
     ``gaussian_projector.ProjectionPlan`` built from these very tensors; the launch then walks its lists
     (``r2_project_gaussians_variance_planned``) and gives the same bits."""
-    from .gaussian_projector import _checked_plan
     rays, H, W = check_projection_arguments(rays, H, W, xyz, density, scaling, rotation)
     plan = _checked_plan(plan, rays, cone, H, W, xyz, density, scaling, rotation, scale_modifier)
     V, P, dev = rays.shape[0], xyz.shape[0], xyz.device
@@ -152,14 +140,8 @@ def projection_variance_rays(rays, cone, H, W, xyz, density, scaling, rotation, 
     rays = projector.device_rays(rays.detach(), dev)
     x, d, s, r = _cloud(xyz, density, scaling, rotation)
     out = torch.empty((V, H, W), dtype=_F32, device=dev)
-    args = (V, H, W, rays.data_ptr(), int(bool(cone)), P, x.data_ptr(), d.data_ptr(), s.data_ptr(), float(scale_modifier),
-            r.data_ptr(), vx.data_ptr(), vd.data_ptr(), vs.data_ptr(), vr.data_ptr(), out.data_ptr())
-    with _on_device(dev):
-        if plan is None:
-            rc = _lib.lib().r2_project_gaussians_variance(*args, _stream(dev))
-        else:
-            rc = _lib.lib().r2_project_gaussians_variance_planned(*args, *plan._args(), _stream(dev))
-    _lib.check(rc, "r2_project_gaussians_variance" if plan is None else "r2_project_gaussians_variance_planned")
+    _call_planned("r2_project_gaussians_variance", plan, dev, V, H, W, rays, int(bool(cone)), P, x, d, s, float(scale_modifier), r,
+                  vx, vd, vs, vr, out)
     return out
 
 

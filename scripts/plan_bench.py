@@ -86,7 +86,7 @@ def main():
     for V in a.views:
         rays = torch.from_numpy(GP.world_ray_params(S.make_views(V, (H, W)))).to(dev)
         args = (rays, True, H, W, *leaves)
-        x, d, s, r = (GP._f32c(t) for t in leaves)
+        x, d, s, r = (GP.f32c(t) for t in leaves)
         with torch.no_grad():
             plan = GP.plan_projection_rays(*args)
             offsets, ws = GP._plan_count(rays, 1, H, W, x, d, s, r, 1.0)
