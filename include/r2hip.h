@@ -194,6 +194,43 @@ R2_API size_t r2_loss_l1_ssim_batch_scratch_floats(int V, int width, int height)
 R2_API int r2_loss_l1_ssim_batch(int V, int width, int height, const float *imgs /* [V,H,W] */,
                                  const float *const *gts_host /* V device pointers */, float w_l1, float w_ssim,
                                  float *dL_dimg /* [V,H,W] */, float *scratch, float *scalars /* [V + 1][3] */, void *stream);
+/* r2_loss_l1_ssim_weighted: the same loss with per-pixel weights w [height,width] (a 0/1 mask is the special case; the
+ * penalised weighted least squares of CT reconstruction).  A weight counts only where it is > 0: a negative, zero or NaN
+ * weight is 0; the others must be finite.  A pixel of weight 0 is unmeasured: its gt is never used as a value (it may hold
+ * NaN, Inf or anything else), the measurement taken in its place is the image's own value there, held constant:
+ *   y'(p) = w(p) > 0 ? gt(p) : img(p),  sum_w = sum_p w(p),  S = the SSIM map of (img, y') as r2_loss_l1_ssim forms it,
+ *   l1 = sum w |img - y'| / sum_w,  ssim = sum w S / sum_w,  loss = w_l1 * l1 + w_ssim * (1 - ssim),
+ *   dL/dimg(p) = w_l1 w(p) sign(img(p) - y'(p)) / sum_w
+ *                - w_ssim / sum_w * sum_q W(q - p) w(q) [D1(q) + 2 img(p) D2(q) + y'(p) D3(q)]
+ * (r2_loss_l1_ssim's formula with 1 / N -> 1 / sum_w, D_i -> w D_i, gt -> y'; an unmeasured pixel still receives the SSIM part
+ * through its weighted neighbours).  sum_w = 0 (no measured pixel): l1 = 0, ssim = 1, loss = 0 and a gradient of zeros, no
+ * NaN.  weights == NULL is a weight of 1 everywhere; that, and an array of ones, give the bits of r2_loss_l1_ssim.  Scaling
+ * all weights by a power of two changes no bit of the gradient or of the first three scalars.
+ *   scalars [4] = {l1, ssim, loss, sum_w}: per-block sums folded in a fixed order in double, sum_w rounded to float once.
+ *   Three launches (forward, a one-block fold of sum_w and the scalars, backward); no atomics, no host synchronisation, no
+ *   allocation; bit-reproducible.  scratch: at least r2_loss_l1_ssim_weighted_scratch_floats(width, height) device floats,
+ *   8-byte aligned; 0 for sizes the call rejects.
+ *   R2_ERR_INVALID: width or height <= 0, a NULL img / gt / dL_dimg / scratch / scalars, a grid beyond the batch bound.
+ * r2_loss_l1_ssim_weighted_batch: V >= 1 views for the mean over the views of each view's own weighted loss (every view is
+ * normalised by its own sum_w), three launches per R2_LOSS_BATCH_CHUNK views.  weights_host: NULL (unit weights for every
+ * view), or a HOST array of V device pointers, each to a [height,width] array or NULL (unit weights for that view).
+ *   scalars [V + 1][4]: row v < V is bit-identical to what r2_loss_l1_ssim_weighted(img_v, gt_v, weights_v, w_l1, w_ssim)
+ *     writes; row V = the means of the first three columns of those float rows over the views, summed in view order in
+ *     double, and the sum of their sum_w.  A view with sum_w = 0 contributes loss 0 and a zero gradient and still counts in V.
+ *   dL_dimg [V,height,width]: dL_dimg[v] is bit-identical to what r2_loss_l1_ssim_weighted(img_v, gt_v, weights_v,
+ *     w_l1 / V, w_ssim / V) writes, the two quotients formed in float.
+ *   scratch: at least r2_loss_l1_ssim_weighted_batch_scratch_floats(V, width, height) device floats, 8-byte aligned.
+ *   R2_ERR_INVALID: those of r2_loss_l1_ssim_batch; a NULL weights_host or weights_host[v] is allowed. */
+R2_API size_t r2_loss_l1_ssim_weighted_scratch_floats(int width, int height);
+R2_API int r2_loss_l1_ssim_weighted(int width, int height, const float *img, const float *gt,
+                                    const float *weights /* [H,W] or NULL = 1 */, float w_l1, float w_ssim,
+                                    float *dL_dimg, float *scratch, float *scalars /* [4] */, void *stream);
+R2_API size_t r2_loss_l1_ssim_weighted_batch_scratch_floats(int V, int width, int height);
+R2_API int r2_loss_l1_ssim_weighted_batch(int V, int width, int height, const float *imgs /* [V,H,W] */,
+                                          const float *const *gts_host /* V device pointers */,
+                                          const float *const *weights_host /* NULL, or V device pointers, each may be NULL = 1 */,
+                                          float w_l1, float w_ssim, float *dL_dimg /* [V,H,W] */, float *scratch,
+                                          float *scalars /* [V + 1][4] */, void *stream);
 R2_API size_t r2_loss_tv3d_scratch_floats(int nx, int ny, int nz);
 R2_API int r2_loss_tv3d(int nx, int ny, int nz, const float *vol, float weight, float *dL_dvol, float *scratch,
                         float *scalars /* [2] */, void *stream);

@@ -84,6 +84,10 @@ _SIGNATURES = {
     "r2_loss_l1_ssim": (C.c_int, [_i, _i, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
     "r2_loss_l1_ssim_batch_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "r2_loss_l1_ssim_batch": (C.c_int, [_i, _i, _i, _fp, _p, _f, _f, _fp, _fp, _fp, _p]),
+    "r2_loss_l1_ssim_weighted_scratch_floats": (C.c_size_t, [_i, _i]),
+    "r2_loss_l1_ssim_weighted": (C.c_int, [_i, _i, _fp, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
+    "r2_loss_l1_ssim_weighted_batch_scratch_floats": (C.c_size_t, [_i, _i, _i]),
+    "r2_loss_l1_ssim_weighted_batch": (C.c_int, [_i, _i, _i, _fp, _p, _p, _f, _f, _fp, _fp, _fp, _p]),
     "r2_loss_tv3d_scratch_floats": (C.c_size_t, [_i, _i, _i]),
     "r2_loss_tv3d": (C.c_int, [_i, _i, _i, _fp, _f, _fp, _fp, _fp, _p]),
     "r2_metric_slices_scratch_floats": (C.c_size_t, [_i, _i, _i, _i]),

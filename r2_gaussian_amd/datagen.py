@@ -14,6 +14,11 @@ Training angles are linspace(0, totalAngle, n_train + 1)[:-1] + startAngle, test
 ``numpy.random.RandomState`` (``--seed``), so a seed reproduces a dataset bit for bit -- the reference draws from numpy's
 global generator.  ``--projection_type siddon`` projects with the ray-voxel intersection model instead of the interpolated
 one; a case made with a model named explicitly records it as ``projection_type`` in its saved scanner config.
+
+``--dead_pixels F``, ``--dead_lines N``, ``--gap C0 C1`` (none by default) draw one static detector mask (``weights.defect_mask``,
+after every other draw): the masked pixels of the TRAINING projections are written as 0, the mask as ``weights_train.npy``
+([H, W] float32, 1 = measured) and under the key ``weights_train`` of ``meta_data.json``.  Without them a case is, byte for
+byte, what it was.
 """
 import argparse
 import json
@@ -60,8 +65,10 @@ def angles_for(cfg, n_train, n_test, rng):
     return train, test
 
 
-def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles_test):
-    """The on-disk layout of generate_data.py:70-100 for given projections [V, H, W]; -> the meta dictionary written."""
+def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles_test, weights_train=None):
+    """The on-disk layout of generate_data.py:70-100 for given projections [V, H, W]; -> the meta dictionary written.
+    ``weights_train`` ([H, W], shared by the training views, or [V, H, W]; None: the case records none and is the
+    reference's layout): saved as ``weights_train.npy`` and recorded under the key ``weights_train``."""
     os.makedirs(case_dir, exist_ok=True)
     np.save(osp.join(case_dir, "vol_gt.npy"), np.asarray(vol, dtype=np.float32))
     entries = {}
@@ -74,6 +81,12 @@ def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles
             entries[split].append({"file_path": name, "angle": float(angles[i])})
     meta = {"scanner": cfg, "vol": "vol_gt.npy", "bbox": [[-1, -1, -1], [1, 1, 1]],
             "proj_train": entries["proj_train"], "proj_test": entries["proj_test"]}
+    if weights_train is not None:
+        w = np.ascontiguousarray(weights_train, dtype=np.float32)
+        if w.shape != np.shape(projs_train)[-2:] and w.shape != np.shape(projs_train):
+            raise ValueError("weights_train is %s but the training projections are %s" % (w.shape, np.shape(projs_train)))
+        np.save(osp.join(case_dir, "weights_train.npy"), w)
+        meta["weights_train"] = "weights_train.npy"
     with open(osp.join(case_dir, "meta_data.json"), "w", encoding="utf-8") as f:
         json.dump(meta, f, indent=4)
     return meta
@@ -84,10 +97,13 @@ def recorded_projection_type(cfg):
     return P.check_projection_type(cfg.get("projection_type", "interpolated"))
 
 
-def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda", projection_type=None):
+def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda", projection_type=None, defects=None):
     """Project ``vol`` [nx,ny,nz] with the raw scanner config ``cfg`` and write the case ``{output}/{vol_name}_{mode}``;
     -> the case directory.  ``projection_type``: "interpolated" or "siddon", written into the case's saved scanner config;
-    None takes the config's own ``projection_type`` ("interpolated" if absent) and saves the config as it is."""
+    None takes the config's own ``projection_type`` ("interpolated" if absent) and saves the config as it is.
+    ``defects``: None, or the keyword arguments of ``weights.defect_mask`` (dead_pixels, dead_lines, gap) for one static
+    detector mask, drawn after every other draw: the training projections are written with 0 in the masked pixels and the mask
+    as the case's ``weights_train``."""
     if projection_type is None:
         projection_type = recorded_projection_type(cfg)
     else:
@@ -99,7 +115,12 @@ def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device=
     train = noisy_train(train, cfg, rng)
     test = P.project(vol, test_angles, cfg, device=device, projection_type=projection_type).cpu().numpy()
     case_dir = osp.join(output, "%s_%s" % (vol_name, cfg["mode"]))
-    write_case(case_dir, cfg, vol, train, train_angles, test, test_angles)
+    mask = None
+    if defects:
+        from .weights import defect_mask
+        mask = defect_mask(cfg["nDetector"], rng, **defects)
+        train = np.where(mask > 0, train, np.float32(0)).astype(np.float32)
+    write_case(case_dir, cfg, vol, train, train_angles, test, test_angles, weights_train=mask)
     return case_dir
 
 
@@ -114,14 +135,21 @@ def main(argv=None):
     ap.add_argument("--seed", default=0, type=int, help="Seed of every random draw (test angles, noise).")
     ap.add_argument("--projection_type", default=None, choices=P.PROJECTION_TYPES,
                     help="Projector model (default: the scanner configuration's, else interpolated).")
+    ap.add_argument("--dead_pixels", default=0.0, type=float, help="Fraction of singly dead detector pixels.")
+    ap.add_argument("--dead_lines", default=0, type=int, help="Number of dead detector rows or columns.")
+    ap.add_argument("--gap", default=None, type=int, nargs=2, metavar=("C0", "C1"),
+                    help="A band of unmeasured detector columns C0 <= c < C1.")
     args = ap.parse_args(argv)
     import yaml
     with open(args.scanner, "r") as f:
         cfg = yaml.safe_load(f)
     vol_name = osp.basename(args.vol)[:-4]
     print("Generate data for case %s_%s" % (vol_name, cfg["mode"]))
+    defects = None
+    if args.dead_pixels > 0 or args.dead_lines > 0 or args.gap is not None:
+        defects = dict(dead_pixels=args.dead_pixels, dead_lines=args.dead_lines, gap=None if args.gap is None else tuple(args.gap))
     case_dir = generate(np.load(args.vol), cfg, args.output, vol_name, args.n_train, args.n_test, args.seed,
-                        projection_type=args.projection_type)
+                        projection_type=args.projection_type, defects=defects)
     print("Generate data for case %s complete!" % osp.basename(case_dir))
     return case_dir
 

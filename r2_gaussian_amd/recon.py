@@ -303,7 +303,8 @@ def run_ct_recon_algs(projs, angles, cfg, ct_gt, save_path, method, projection_t
 
 def _read_case(case_dir):
     """The case written by ``datagen.write_case``: raw config, projections and angles per split, the ground truth, and the
-    reference reader's scene_scale (dataset_readers.py:62-76)."""
+    reference reader's scene_scale (dataset_readers.py:62-76).  ``weights_train``: the recorded weights of the training
+    projections, float32 [H, W] (shared by the views) or [V, H, W]; None for a case that records none."""
     with open(osp.join(case_dir, "meta_data.json"), "r", encoding="utf-8") as f:
         meta = json.load(f)
     cfg = meta["scanner"]
@@ -312,6 +313,12 @@ def _read_case(case_dir):
         e = meta["proj_" + split]
         out[split] = (np.stack([np.load(osp.join(case_dir, x["file_path"])) for x in e]).astype(np.float32),
                       np.array([x["angle"] for x in e], dtype=np.float64))
+    out["weights_train"] = None
+    if "weights_train" in meta:
+        w = np.load(osp.join(case_dir, meta["weights_train"])).astype(np.float32)
+        if w.shape != out["train"][0].shape[1:] and w.shape != out["train"][0].shape:
+            raise ValueError("weights_train is %s but the training projections are %s" % (w.shape, out["train"][0].shape))
+        out["weights_train"] = w
     return out
 
 

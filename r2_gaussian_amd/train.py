@@ -19,6 +19,13 @@ render, one batched loss node (the mean over the views), one backward, one batch
 Iterations, the densification window and the learning-rate horizons then count optimiser steps, and the learning rates are
 NOT rescaled: DESIGN.md section 6 has the two configurations the PSNR study measured (W = 8 with the reference's schedule
 for equal steps; iterations, window, interval and horizons / 8 and all learning rates x 8 for equal views).
+
+``--loss_weights {auto,none,file,noise}`` (not a flag of the reference; default auto): per-pixel weights of the training
+projections in the image loss (losses.image_loss(..., weights=)): a pixel of weight 0 -- a dead pixel, a panel gap -- is never
+used, whatever it holds.  auto: the weights the case records (datagen's ``weights_train``), none for a case that records none,
+whose loop is then unchanged; none: ignore them; file: require them; noise: uncertainty.noise_weights of the raw training stack
+under the scanner config's noise model, times the recorded weights if there are any.  The FDK initialisation then sees the
+projections with their unmeasured pixels filled (weights.fill_unmeasured), ``--save_uncertainty`` the same weights.
 """
 import argparse
 import os
@@ -144,17 +151,18 @@ def evaluate(gaussians, iteration, model_path, geometry, vol_gt, evals, eval_exa
 
 
 @torch.no_grad()
-def write_uncertainty(gaussians, views, geometry, path, prior_precision, batch=8):
+def write_uncertainty(gaussians, views, geometry, path, prior_precision, batch=8, weights=None):
     """fisher.npz (xyz [P,3], density [P,1], scaling [P,3], rotation [P,4]: the Fisher diagonal of the activated parameters
-    over `views` with unit weights, `batch` views per launch) and vol_std.npy ([nx, ny, nz]: the square root of the field's
-    predictive variance at the voxel centres of the evaluation grid, under the Laplace variances 1 / (F + prior_precision))
-    into `path`."""
+    over `views` with unit weights, or with `weights`: one [H, W] device tensor per view; `batch` views per launch) and
+    vol_std.npy ([nx, ny, nz]: the square root of the field's predictive variance at the voxel centres of the evaluation
+    grid, under the Laplace variances 1 / (F + prior_precision)) into `path`."""
     from . import uncertainty as U
     from .field import voxel_centres
     xyz, d, s, r = (t.detach() for t in gaussians.activated())
     F = None
     for i in range(0, len(views), batch):
-        Fi = U.fisher_diagonal(views[i:i + batch], xyz, d, s, r)
+        Fi = U.fisher_diagonal(views[i:i + batch], xyz, d, s, r,
+                               None if weights is None else torch.stack(list(weights[i:i + batch])))
         F = Fi if F is None else U.CloudTuple(*(a + b for a, b in zip(F, Fi)))
     var = U.parameter_variance(F, prior_precision)
     pts = voxel_centres(geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"], xyz.device)
@@ -164,16 +172,17 @@ def write_uncertainty(gaussians, views, geometry, path, prior_precision, batch=8
     np.save(osp.join(path, "vol_std.npy"), std.cpu().numpy())
 
 
-def render_loss_batch(gaussians, views, gts, lambda_dssim, dev):
+def render_loss_batch(gaussians, views, gts, lambda_dssim, dev, weights=None):
     """The image term of a step on several views: ONE GaussianRasterizerBatch call on `views` (scene.View list) and ONE
-    losses.image_loss_batch node against `gts` (their ground truths, [H, W] device tensors).
+    losses.image_loss_batch node against `gts` (their ground truths, [H, W] device tensors), weighted per pixel by `weights`
+    (None, or the views' [H, W] device tensors).
     -> (loss: the mean over the views, radii [W, P], screen [W, P, 3]: the leaf whose .grad the backward fills with every
     view's dL/dmeans2D of that mean loss)."""
     xyz, dens, scal, rot = gaussians.activated()
     screen = torch.zeros((len(views),) + tuple(xyz.shape), dtype=torch.float32, device=dev, requires_grad=True)
     img, radii = GaussianRasterizerBatch(_settings(views[0], dev, views))(means3D=xyz, means2D=screen, opacities=dens, scales=scal,
                                                                           rotations=rot, cov3D_precomp=None)
-    loss, _parts = FL.image_loss_batch(img, gts, lambda_dssim)
+    loss, _parts = FL.image_loss_batch(img, gts, lambda_dssim, weights)
     return loss, radii, screen
 
 
@@ -191,7 +200,7 @@ def pick_views(stack, n_views, count, rng):
 
 def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry, init_points, opt, model_path,
              scale_bound=None, test_iterations=(), save_iterations=(), checkpoint_iterations=(), start_checkpoint=None,
-             seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False, save_uncertainty=None):
+             seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False, save_uncertainty=None, train_weights=None):
     """The training loop of train.py:34-216.  views: scene.View lists; projections: [V, H, W] in scene units (times
     scene_scale); vol_gt [nx, ny, nz]; geometry: the NORMALISED scanner config (nVoxel, sVoxel, offOrigin, dVoxel);
     init_points [N, 4] = xyz | density; scale_bound: (lo, hi) in scene units or None.  Randomness (view order, TV patch centres,
@@ -210,6 +219,10 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     opt.merge_interval = N > 0 (absent = 0: off, the loop is then the one above and merge.py is never imported): every N-th
     iteration with opt.merge_from_iter < iteration < opt.merge_until_iter, right after the densification slot,
     gaussians.merge(opt.merge_cost, k=opt.merge_k) replaces neighbouring Gaussians that say the same thing by one.
+    train_weights (None: off, the loop is then the one above): per-pixel weights of the training projections, [H, W] shared by
+    the views or [V, H, W] (weights.resolve_weights): the image term becomes the weighted loss of losses.image_loss /
+    image_loss_batch, in which a pixel whose weight is not > 0 is never used (train_projs may hold anything there, NaN
+    included), and save_uncertainty weighs the Fisher diagonal with them.  The evaluation metrics stay unweighted.
     -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds, merged_pairs)."""
     W = int(views_per_step)
     if W < 1:
@@ -230,6 +243,14 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     max_scale = opt.max_scale * volume_to_world if opt.max_scale else None
     densify_scale_threshold = opt.densify_scale_threshold * volume_to_world if opt.densify_scale_threshold else None
     gts = [torch.as_tensor(np.asarray(p), dtype=torch.float32).to(dev) for p in train_projs]
+    wts = None
+    if train_weights is not None:
+        w = np.asarray(train_weights, dtype=np.float32)
+        if w.shape != tuple(gts[0].shape) and w.shape != (len(gts),) + tuple(gts[0].shape):
+            raise ValueError("train_weights is %s but the training projections are %s" % (w.shape, (len(gts),) + tuple(gts[0].shape)))
+        with np.errstate(invalid="ignore"):
+            w = torch.from_numpy(np.where(w > 0, w, np.float32(0))).to(dev)
+        wts = [w] * len(gts) if w.dim() == 2 else list(w)
     vol_gt = torch.as_tensor(np.asarray(vol_gt), dtype=torch.float32).to(dev)
     evals = [("render_train", train_views, torch.stack(gts, -1)),
              ("render_test", test_views,
@@ -272,10 +293,10 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
             screen = torch.zeros_like(xyz, requires_grad=True)
             img, radii = GaussianRasterizer(raster_settings=settings[vi])(means3D=xyz, means2D=screen, opacities=dens,
                                                                           scales=scal, rotations=rot, cov3D_precomp=None)
-            loss, _parts = FL.image_loss(img, gts[vi], opt.lambda_dssim)
+            loss, _parts = FL.image_loss(img, gts[vi], opt.lambda_dssim, None if wts is None else wts[vi])
         else:
             loss, radii, screen = render_loss_batch(gaussians, [train_views[vi] for vi in picked], [gts[vi] for vi in picked],
-                                                    opt.lambda_dssim, dev)
+                                                    opt.lambda_dssim, dev, None if wts is None else [wts[vi] for vi in picked])
         if use_tv:
             c = (bbox[0] + tvS / 2) + (bbox[1] - tvS - bbox[0]) * torch.rand(3, generator=gen)
             loss = loss + opt.lambda_tv * FL.tv_3d_loss(_query(xyz, dens, scal, rot, c, tvN, tvS))
@@ -315,7 +336,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
             log("[ITER %d] Evaluating: psnr3d %.3f, ssim3d %.3f, P %d" % (iteration, e["psnr_3d"], e["ssim_3d"], gaussians.P))
     if save_uncertainty is not None:
         write_uncertainty(gaussians, train_views, geometry, osp.join(model_path, "point_cloud", "iteration_%d" % opt.iterations),
-                          float(save_uncertainty))
+                          float(save_uncertainty), weights=wts)
     out["it_per_s"] = n_timed / t_train if t_train > 0 else float("nan")
     out["views_per_s"] = W * out["it_per_s"]
     out["model"] = gaussians
@@ -330,10 +351,13 @@ def _rate(out, W):
 
 
 # ---------------------------------------------------------------------------------------------- the case on disk
-def load_case(source_path, ply_path="", seed=0):
+def load_case(source_path, ply_path="", seed=0, loss_weights="none"):
     """Scene + initialize_gaussian for a case in datagen's layout: the views (scene.make_view on the raw config), the
     projections times scene_scale, the normalised geometry (dataset_readers.py:62-76), and the initial points from
-    ``init_<case>.npy``, else `ply_path` (.npy), else fdk.init_pcd on the normalised scene."""
+    ``init_<case>.npy``, else `ply_path` (.npy), else fdk.init_pcd on the normalised scene.
+    loss_weights: a mode of weights.resolve_weights; its result is ``train_weights`` (None for "none", and for "auto" on a case
+    that records no weights: weights.py is then not imported), and with weights the FDK initialisation reads the training
+    projections with their unmeasured pixels filled (weights.fill_unmeasured)."""
     from . import fdk
     from .recon import _read_case
     case = _read_case(source_path)
@@ -345,7 +369,10 @@ def load_case(source_path, ply_path="", seed=0):
         if k in geo:
             geo[k] = (np.array(geo[k]) * scale).tolist()
     det = tuple(int(x) for x in cfg["nDetector"])
-    out = {"geometry": geo, "vol_gt": case["vol"], "scale": scale}
+    out = {"geometry": geo, "vol_gt": case["vol"], "scale": scale, "train_weights": None}
+    if loss_weights != "none" and (loss_weights != "auto" or case["weights_train"] is not None):
+        from . import weights as WT
+        out["train_weights"] = WT.resolve_weights(case, loss_weights)
     for split in ("train", "test"):
         projs, angles = case[split]
         out[split + "_views"] = [S.make_view(a, det, cfg) for a in angles]
@@ -359,6 +386,8 @@ def load_case(source_path, ply_path="", seed=0):
         out["init_points"] = np.load(ply_path)
     else:
         projs, angles = case["train"]
+        if out["train_weights"] is not None:
+            projs = WT.fill_unmeasured(projs, out["train_weights"])
         projs = projs * np.float32(scale)
         # initialize_pcd.py's 50000 points, or every voxel above its threshold in a smaller reconstruction
         n_points = min(50000, int((fdk.recon_volume(projs, angles, geo) > 0.05).sum()))
@@ -401,9 +430,14 @@ def build_parser():
     ap.add_argument("--eval_exact", action="store_true", default=False,
                     help="every evaluation also writes eval2d_render_{train,test}_exact.yml: the 2D metrics on the exact line "
                          "integrals of the model (gaussian_projector) next to those on the rasterizer's image of it")
+    ap.add_argument("--loss_weights", choices=("auto", "none", "file", "noise"), default="auto",
+                    help="per-pixel weights of the training projections in the image loss (a weight of 0 excludes the pixel, "
+                         "whatever it holds): auto = the case's recorded weights_train if it has any, none = ignore them, file = "
+                         "require them, noise = the inverse variances of the scanner config's noise model (uncertainty.noise_weights "
+                         "on the raw training stack), times the recorded weights if any")
     ap.add_argument("--save_uncertainty", type=float, default=None, metavar="LAMBDA",
                     help="after the last iteration write fisher.npz (the Fisher diagonal of the activated parameters over the "
-                         "training views, unit weights) and vol_std.npy (the standard deviation of the field on the evaluation "
+                         "training views, unit weights or those of --loss_weights) and vol_std.npy (the standard deviation of the field on the evaluation "
                          "grid under the Laplace variances 1 / (F + LAMBDA)) into the last point_cloud/iteration_N")
     return ap
 
@@ -434,7 +468,12 @@ def main(argv=None):
     os.makedirs(args.model_path, exist_ok=True)
     print("Optimizing " + args.model_path)
     torch.autograd.set_detect_anomaly(args.detect_anomaly)
-    case = load_case(args.source_path, args.ply_path)
+    try:
+        case = load_case(args.source_path, args.ply_path, loss_weights=args.loss_weights)
+    except ValueError as e:
+        if "--loss_weights" not in str(e):
+            raise
+        ap.error(str(e))
     volume_to_world = max(case["geometry"]["sVoxel"])
     scale_bound = None
     if args.scale_min > 0 and args.scale_max > 0:
@@ -445,7 +484,8 @@ def main(argv=None):
     out = training(case["train_views"], case["train_projs"], case["test_views"], case["test_projs"], case["vol_gt"],
                    case["geometry"], case["init_points"], opt, args.model_path, scale_bound, set(args.test_iterations),
                    set(args.save_iterations), set(args.checkpoint_iterations), args.start_checkpoint, log=log,
-                   views_per_step=args.views_per_step, eval_exact=args.eval_exact, save_uncertainty=args.save_uncertainty)
+                   views_per_step=args.views_per_step, eval_exact=args.eval_exact, save_uncertainty=args.save_uncertainty,
+                   train_weights=case["train_weights"])
     print("Training complete. " + _rate(out, args.views_per_step))
     return out
 
