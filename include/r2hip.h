@@ -173,7 +173,8 @@ R2_API int r2_raster_backward_batch(
  * scratch: device floats, at least r2_loss_*_scratch_floats(...).  Per-block sums are folded in a fixed order in double.
  * r2_loss_l1_ssim_batch: V >= 1 projections imgs [V,height,width] against V ground truths, for the loss
  *   mean over the views v of  w_l1 * mean|img_v - gt_v| + w_ssim * (1 - SSIM(img_v, gt_v)),
- * forward and gradient, with the kernels of r2_loss_l1_ssim run on a grid whose third dimension is the view.  gts_host: a
+ * forward and gradient, by the kernels of r2_loss_l1_ssim: their grid's third dimension is the view, and r2_loss_l1_ssim is
+ * their launch with one view and no batch row (so it refuses an image beyond the grid bound below as well).  gts_host: a
  * HOST array of V device pointers, each to a [height,width] image (a step's ground truths are picks from a training set and
  * need not be contiguous with each other; they are read in place).  The table travels to the kernels by value,
  * R2_LOSS_BATCH_CHUNK views per pair of launches: ceil(V / R2_LOSS_BATCH_CHUNK) * 2 launches, no host synchronisation, no
@@ -185,7 +186,8 @@ R2_API int r2_raster_backward_batch(
  *   scratch: at least r2_loss_l1_ssim_batch_scratch_floats(V, width, height) device floats, 8-byte aligned ([V][3][height]
  *     [width] derivative maps, then every view's per-block partial sums); 0 for sizes the call rejects.
  *   R2_ERR_INVALID: V < 1, width or height <= 0, a NULL imgs / gts_host / gts_host[v] / dL_dimg / scratch / scalars, a
- *     grid beyond the bound above. */
+ *     grid beyond the bound above (also more than 65535 tiles of 16 rows: height > 1048560).  r2_loss_l1_ssim: the same
+ *     with V = 1. */
 R2_API size_t r2_loss_l1_ssim_scratch_floats(int width, int height);
 R2_API int r2_loss_l1_ssim(int width, int height, const float *img, const float *gt, float w_l1, float w_ssim,
                            float *dL_dimg, float *scratch, float *scalars /* [3] */, void *stream);

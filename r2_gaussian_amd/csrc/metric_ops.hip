@@ -4,7 +4,7 @@
 //
 // The reference loops over slices with five vendor conv2d calls and one host sync each; the vendor convolution reads past its
 // 484-byte weight tensor on this stack (loss_ops.hip), so that loop can fault the device.  Here the SSIM of every slice of one
-// axis is one launch of the tile scheme of ssim_forward_kernel (16 x 16 output tile, 26 x 26 halo in LDS, horizontal then
+// axis is one launch of the loss's tile function (ssim_window.hpp: 16 x 16 output tile, 26 x 26 halo in LDS, horizontal then
 // vertical 11-tap blur of the five moments) with the slice in blockIdx.z, followed by one small launch that folds the per-block
 // partials of each slice in a fixed order in double: bit-reproducible, no atomics.
 //
@@ -12,13 +12,14 @@
 // first transposed to [n2][n0][n1] into scratch through LDS tiles, then read the same way.  Without SSIM (PSNR only) the blur
 // is skipped: a plain SSE / maximum pass with a wave along each row.  R2_METRIC_NORMALIZE (metric_proj) divides every slice of
 // both inputs by its own maximum (multiplying by the reciprocal) before both metrics; the maxima come from a first such pass.
+#include "block_fold.hpp"
 #include "ssim_window.hpp"
 
 namespace r2 {
 
 namespace {
 
-constexpr int LT = SSIM_LT, WIN = SSIM_WIN, HALO = SSIM_HALO, LR = SSIM_LR;
+constexpr int LT = SSIM_LT, HALO = SSIM_HALO;
 constexpr int NT = LT * LT;     // 256 threads = 4 waves in every kernel here
 constexpr int SROWS = 16;       // rows per block of the SSE / maximum pass
 constexpr int TT = 32;          // transpose tile
@@ -35,22 +36,13 @@ SliceGeom slice_geom(int n0, int n1, int n2, int axis)
 
 size_t ssim_blocks(const SliceGeom &g) { return (size_t)((g.W + LT - 1) / LT) * ((g.H + LT - 1) / LT); }
 
-// {sum, sum, max, max} over the block in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ float4 block_reduce(float4 v, float4 *red)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        v.x += __shfl_xor(v.x, d); v.y += __shfl_xor(v.y, d);
-        v.z = fmaxf(v.z, __shfl_xor(v.z, d)); v.w = fmaxf(v.w, __shfl_xor(v.w, d));
+// the fold of {sum, sum, max, max}
+struct FoldSumSumMaxMax {
+    __device__ __forceinline__ float4 operator()(float4 a, float4 b) const
+    {
+        return make_float4(a.x + b.x, a.y + b.y, fmaxf(a.z, b.z), fmaxf(a.w, b.w));
     }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float4 t = red[0];
-    for (int w = 1; w < NT / 64; ++w) {
-        t.x += red[w].x; t.y += red[w].y; t.z = fmaxf(t.z, red[w].z); t.w = fmaxf(t.w, red[w].w);
-    }
-    return t;
-}
+};
 
 // per-slice reciprocals of the maxima (normalisation), or 1
 __device__ __forceinline__ float2 slice_scale(const float *__restrict__ norm, int s)
@@ -80,58 +72,35 @@ __global__ void __launch_bounds__(NT) metric_sse_max_kernel(int W, int H, size_t
             acc.y += d * d;
             acc.z = fmaxf(acc.z, u); acc.w = fmaxf(acc.w, v);
         }
-    const float4 t = block_reduce(acc, red);
+    const float4 t = block_fold<NT / 64>(acc, red, FoldSumSumMaxMax());
     if (threadIdx.x == 0) partial[(size_t)s * gridDim.x + blockIdx.x] = t;
 }
 
-// the SSIM map of a 16 x 16 tile of slice blockIdx.z (ssim_forward_kernel without the derivative maps), with the tile's SSE and
-// maxima; one partial per (block, slice)
+// the SSIM map of a 16 x 16 tile of slice blockIdx.z (the loss's forward pass without the derivative maps: the same
+// ssim_tile_moments), with the tile's SSE and maxima; one partial per (block, slice)
 __global__ void __launch_bounds__(NT) metric_ssim_kernel(int W, int H, size_t rs, size_t ss, const float *__restrict__ gt,
                                                          const float *__restrict__ pred, SsimWindow win,
                                                          const float *__restrict__ norm, float4 *__restrict__ partial)
 {
-    __shared__ float sx[LR][LR + 1], sy[LR][LR + 1];
-    __shared__ float hb[5][LR][LT + 1];   // horizontally blurred x, y, x^2, y^2, xy
+    __shared__ SsimTile tile;
     __shared__ float4 red[NT / 64];
     const int tid = threadIdx.x, tx = tid % LT, ty = tid / LT, s = blockIdx.z;
-    const int ox = blockIdx.x * LT, oy = blockIdx.y * LT;
     const float *g = gt + (size_t)s * ss, *p = pred + (size_t)s * ss;
     const float2 sc = slice_scale(norm, s);
-    for (int i = tid; i < LR * LR; i += NT) {
-        const int ry = i / LR, rx = i % LR, X = ox + rx - HALO, Y = oy + ry - HALO;
-        const bool in = X >= 0 && X < W && Y >= 0 && Y < H;   // zero padding AFTER the normalisation, as conv2d pads
-        sx[ry][rx] = in ? g[(size_t)Y * rs + X] * sc.x : 0.f;
-        sy[ry][rx] = in ? p[(size_t)Y * rs + X] * sc.y : 0.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < LR * LT; i += NT) {
-        const int ry = i / LT, cx = i % LT;
-        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-        for (int k = 0; k < WIN; ++k) {
-            const float u = sx[ry][cx + k], v = sy[ry][cx + k], w = win.w[k];
-            a += w * u; b += w * v; aa += w * (u * u); bb += w * (v * v); ab += w * (u * v);
-        }
-        hb[0][ry][cx] = a; hb[1][ry][cx] = b; hb[2][ry][cx] = aa; hb[3][ry][cx] = bb; hb[4][ry][cx] = ab;
-    }
-    __syncthreads();
-    float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
-#pragma unroll
-    for (int k = 0; k < WIN; ++k) {
-        const float w = win.w[k];
-        m1 += w * hb[0][ty + k][tx]; m2 += w * hb[1][ty + k][tx]; e11 += w * hb[2][ty + k][tx];
-        e22 += w * hb[3][ty + k][tx]; e12 += w * hb[4][ty + k][tx];
-    }
+    // zero padding AFTER the normalisation, as conv2d pads
+    const SsimMoments m = ssim_tile_moments(tile, W, H, win, [&](int X, int Y, bool in) {
+        return in ? make_float2(g[(size_t)Y * rs + X] * sc.x, p[(size_t)Y * rs + X] * sc.y) : make_float2(0.f, 0.f);
+    });
     float4 acc = make_float4(0.f, 0.f, -INFINITY, -INFINITY);
-    if (ox + tx < W && oy + ty < H) {
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float s1 = e11 - m1 * m1, s2 = e22 - m2 * m2, s12 = e12 - m1 * m2;
-        const float u = sx[ty + HALO][tx + HALO], v = sy[ty + HALO][tx + HALO], d = u - v;
+    if (blockIdx.x * LT + tx < W && blockIdx.y * LT + ty < H) {
+        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f, m1 = m.m1, m2 = m.m2;
+        const float s1 = m.e11 - m1 * m1, s2 = m.e22 - m2 * m2, s12 = m.e12 - m1 * m2;
+        const float u = tile.x[ty + HALO][tx + HALO], v = tile.y[ty + HALO][tx + HALO], d = u - v;
         acc.x = (2.f * m1 * m2 + C1) * (2.f * s12 + C2) / ((m1 * m1 + m2 * m2 + C1) * (s1 + s2 + C2));
         acc.y = d * d;
         acc.z = u; acc.w = v;
     }
-    float4 t = block_reduce(acc, red);
+    float4 t = block_fold<NT / 64>(acc, red, FoldSumSumMaxMax());
     if (tid == 0) {
         if (norm) { t.z = norm[4 * s + 2]; t.w = norm[4 * s + 3]; }   // report the maxima of the inputs, not of the scaled slices
         partial[((size_t)s * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = t;
@@ -139,34 +108,27 @@ __global__ void __launch_bounds__(NT) metric_ssim_kernel(int W, int H, size_t rs
 }
 
 // per slice (blockIdx.x): fold its nb partials in a fixed order, the sums in double
+struct SliceFold { double S, E; float gm, pm; };
+
 __global__ void __launch_bounds__(NT) metric_finish_kernel(const float4 *__restrict__ partial, int nb, double inv_area, int ssim,
                                                            float *__restrict__ per_slice)
 {
-    __shared__ double rs[NT / 64][2];
-    __shared__ float rm[NT / 64][2];
-    const int s = blockIdx.x, tid = threadIdx.x;
+    __shared__ SliceFold red[NT / 64];
+    const int s = blockIdx.x;
     const float4 *q = partial + (size_t)s * nb;
-    double S = 0.0, E = 0.0;
-    float gm = -INFINITY, pm = -INFINITY;
-    for (int i = tid; i < nb; i += NT) {
+    SliceFold f = {0.0, 0.0, -INFINITY, -INFINITY};
+    for (int i = threadIdx.x; i < nb; i += NT) {
         const float4 v = q[i];
-        S += v.x; E += v.y; gm = fmaxf(gm, v.z); pm = fmaxf(pm, v.w);
+        f.S += v.x; f.E += v.y; f.gm = fmaxf(f.gm, v.z); f.pm = fmaxf(f.pm, v.w);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        S += __shfl_xor(S, d); E += __shfl_xor(E, d);
-        gm = fmaxf(gm, __shfl_xor(gm, d)); pm = fmaxf(pm, __shfl_xor(pm, d));
-    }
-    if ((tid & 63) == 0) { rs[tid >> 6][0] = S; rs[tid >> 6][1] = E; rm[tid >> 6][0] = gm; rm[tid >> 6][1] = pm; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < NT / 64; ++w) {
-            rs[0][0] += rs[w][0]; rs[0][1] += rs[w][1]; rm[0][0] = fmaxf(rm[0][0], rm[w][0]); rm[0][1] = fmaxf(rm[0][1], rm[w][1]);
-        }
-        per_slice[4 * s + 0] = ssim ? (float)(rs[0][0] * inv_area) : NAN;
-        per_slice[4 * s + 1] = (float)rs[0][1];
-        per_slice[4 * s + 2] = rm[0][0];
-        per_slice[4 * s + 3] = rm[0][1];
+    f = block_fold<NT / 64>(f, red, [](SliceFold a, SliceFold b) {
+        return SliceFold{a.S + b.S, a.E + b.E, fmaxf(a.gm, b.gm), fmaxf(a.pm, b.pm)};
+    });
+    if (threadIdx.x == 0) {
+        per_slice[4 * s + 0] = ssim ? (float)(f.S * inv_area) : NAN;
+        per_slice[4 * s + 1] = (float)f.E;
+        per_slice[4 * s + 2] = f.gm;
+        per_slice[4 * s + 3] = f.pm;
     }
 }
 

@@ -9,8 +9,8 @@
 * achieved GB/s = the bytes the algorithm must move (each input read once per axis, the transposed copy of axis 2 written
   and read) over the device time;
 * VALU fraction as DESIGN.md section 4 prices it: wave-level VALU instructions x 2.8 cycles / (1024 SIMDs x 2.4 GHz) over the
-  device time.  The instruction counts are a model read off the gfx950 ISA of the kernels (per wave: SSIM tile 473, SSE /
-  maximum pass 35 + 9 per 64-wide row segment, finish 120, transpose 43), not counters;
+  device time.  The instruction counts are a model read off the gfx950 ISA of the kernels (per wave, the mean of a block's
+  four: SSIM tile 469, SSE / maximum pass 35 + 9 per 64-wide row segment, finish 120, transpose 43), not counters;
 * once, the wall time of the host evaluation model_io.metric_vol(..., "ssim") at 256^3 on the CPU threads this process has.
 """
 import argparse
@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 from r2_gaussian_amd import _lib, metrics as Mx, model_io   # noqa: E402
 
 SIMDS, CLOCK, CYCLES = 1024, 2.4e9, 2.8
-VALU_SSIM, VALU_FINISH, VALU_T = 473, 120, 43
+VALU_SSIM, VALU_FINISH, VALU_T = 469, 120, 43
 
 
 def device_ms(fn, reps):

@@ -179,7 +179,7 @@ def run_views(args):
     return {n: (legs[n][0], v) for n, v in rates.items()}
 
 
-VIEW_KERNELS = ("ssim_forward_batch_kernel", "ssim_backward_batch_kernel", "densify_stats_batch_kernel")
+VIEW_KERNELS = ("ssim_forward_kernel", "ssim_backward_kernel", "densify_stats_batch_kernel")
 
 
 def profile_views(args):
