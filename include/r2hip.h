@@ -527,6 +527,72 @@ R2_API int r2_merge_emit(int P, const float *means, const float *density, const 
                          const void *scratch, int Pn, float *means_out, float *density_out, float *scaling_out,
                          float *rotation_out, int *src /* [Pn,2] */, void *stream);
 
+/* ---- relocation and position noise: a fixed budget of Gaussians (no counterpart in the reference) ---- */
+/* The density control of "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al. 2024) for a field that is a plain
+ *   sum: n + 1 copies of a Gaussian with density rho / (n + 1) each ARE that Gaussian, so relocation leaves the field and every
+ *   projection unchanged and the original method's scale correction is not needed.
+ * Randomness (csrc/philox.hpp): Philox4x32-10 as published, key = the 64-bit seed (low word, high word), counter = (index,
+ *   purpose, call low word, call high word); purpose 0 = noise, 1 = relocation draw, 2 = spread; `call` is the caller's (the
+ *   trainer passes the iteration).  Normals are Box-Muller on words (a, b): u1 = ((a >> 8) + 1) 2^-24, u2 = (b >> 8) 2^-24,
+ *   z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2) in float32; the three normals of an index are z0, z1 of
+ *   words (0, 1) and z0 of words (2, 3).  R below is quat_to_rot(r, x, y, z) of the quaternion AS GIVEN, R[j][i] = row j,
+ *   column i, the covariance R S^2 R^T of r2_query_gaussians and r2_project_gaussians.
+ * r2_gaussian_noise: in place on the RAW xyz [P,3]; density [P,1], scaling [P,3], rotation [P,4] are the ACTIVATED arrays
+ *   (r2_gaussian_activate's, or r2_gaussian_adam_step's after a step).  One thread per Gaussian, float32, no contraction:
+ *     eps = the three normals of (index = row, purpose 0, call);  gate = 1 / (1 + exp(sharpness (rho / density_threshold - 1)));
+ *     a_i = (R[0][i] eps_0 + R[1][i] eps_1) + R[2][i] eps_2;  b_i = (s_i s_i) a_i;  d_j = (R[j][0] b_0 + R[j][1] b_1) + R[j][2] b_2;
+ *     xyz_j = xyz_j + float(lr * double(gate)) d_j,
+ *   that is xyz += lr gate R S^2 R^T eps: Langevin noise shaped by the covariance that fades out above density_threshold (at
+ *   density_threshold 0.005 and sharpness 0.5 the gate is the original method's sigmoid(100 (0.005 - rho))).  lr is the host's
+ *   product of the xyz learning rate and the noise scale.  A row with a non-finite density, scale or quaternion component is
+ *   left untouched.  No atomics, no workspace, no host read; the same (seed, call) gives the same bits.  P = 0 is a no-op;
+ *   P < 0, a NULL array, lr or sharpness outside [0, inf), density_threshold outside (0, inf): R2_ERR_INVALID.
+ * r2_relocate_plan + r2_relocate_emit: the two-step shape of r2_densify_classify / r2_densify_emit, without the host read: the
+ *   result has P + n_new rows whatever the data.  params / exp_avg / exp_avg_sq (+ _out): 4 device pointers each in the order
+ *   xyz [.,3], density [.,1], scaling [.,3], rotation [.,4], RAW parameters; density_act [P,1] (and scaling_act, rotation_act for
+ *   the spread) their activations.
+ *   Dead and alive.  A row is dead when density_act is not inside (dead_density, +inf) or any of its eleven raw parameters is
+ *   not finite; every other row is alive.  D = the number of dead rows.  Slot k < D is the k-th dead row in index order, slot
+ *   D + j (j < n_new) the appended row P + j.
+ *   Weights.  w_i = weights[i], or density_act[i] for weights = NULL, of the alive rows whose w is finite and > 0 (the drawable
+ *   rows); w_max their maximum; q_i = max(1, trunc(float(w_i / w_max) * 2^32)) as a 64-bit integer, q_i = 0 for every other
+ *   row; cdf = the inclusive prefix sum of q, T = its last entry (P + n_new <= 2^29 keeps it below 2^62).  Integer sums: exact
+ *   in any order.
+ *   Draws.  Slot k takes words (0, 1) of (index = k, purpose 1, call): r = word0 * 2^32 + word1, t = (r * T) >> 64, and its
+ *   source is the first i with cdf[i] > t.  plan writes sources [P + n_new] (slot k's source; -1 for k >= D + n_new and for
+ *   T = 0) and draws [P] (n_i = the number of slots whose source is i) and fills the workspace emit reads
+ *   (r2_relocate_workspace_bytes(P, n_new) bytes, alignment >= 256 B; its 64-bit scan works in tiles of R2_RELOCATE_SCAN_TILE).
+ *   plan synchronises the stream only when counts_host is not NULL: counts_host = {dead, alive, drawable}.
+ *   Emit, out of place into arrays of P + n_new rows, one thread per output row, never synchronising.  A source (n_i >= 1)
+ *   keeps xyz, scaling and rotation bit for bit, gets the raw density softplus^-1(float(density_act_i / float(n_i + 1))) and
+ *   zero moments; softplus^-1(x) = x for x > 20, else log(expm1(x)) evaluated in double and rounded once.  A slot is a bit
+ *   copy of its source's xyz, scaling and rotation with that same raw density and zero moments; with spread > 0 its xyz is
+ *   xyz_j + spread ((R[j][0] v_0 + R[j][1] v_1) + R[j][2] v_2), v_i = s_i eps_i, eps = the three normals of (index = k, purpose
+ *   2, call), s and R the source's ACTIVATED scale and rotation -- sources are never displaced; spread = 0 is the
+ *   field-preserving case.  Every other row is copied bit for bit with its moments.  The three statistics are copied for
+ *   untouched rows and zeroed for sources and slots.  T = 0 (nothing drawable): every row is copied unchanged, dead ones
+ *   included, and appended row j is a copy of row j mod P with raw density -100, zero moments and zero statistics: a finite row
+ *   that is dead and is relocated next time.  The moment arrays may be NULL as a whole (no optimizer state), the statistics
+ *   too; scaling_act / rotation_act may be NULL when spread = 0.
+ *   Arguments: P = 0 with n_new = 0 is a no-op returning 0; P < 0, n_new < 0, P + n_new > 2^29, P = 0 with n_new > 0, a NULL
+ *   array, a NaN dead_density, spread outside [0, inf), a workspace that is NULL or too small: R2_ERR_INVALID. */
+#define R2_RELOCATE_SCAN_TILE 4096
+R2_API int r2_gaussian_noise(int P, float *xyz /* [P,3] raw, in place */, const float *density, const float *scaling,
+                             const float *rotation, double lr, float density_threshold, float sharpness,
+                             unsigned long long seed, unsigned long long call, void *stream);
+R2_API size_t r2_relocate_workspace_bytes(int P, int n_new);
+R2_API int r2_relocate_plan(int P, int n_new, const float *const *params, const float *density_act,
+                            const float *weights /* [P] or NULL */, float dead_density, unsigned long long seed,
+                            unsigned long long call, int *sources /* [P + n_new] */, unsigned int *draws /* [P] */,
+                            void *workspace, size_t workspace_bytes, unsigned int *counts_host /* [3] or NULL */, void *stream);
+R2_API int r2_relocate_emit(int P, int n_new, const float *const *params, const float *const *exp_avg,
+                            const float *const *exp_avg_sq, const float *density_act, const float *scaling_act,
+                            const float *rotation_act, const float *max_radii2D, const float *grad_accum, const float *denom,
+                            float spread, unsigned long long seed, unsigned long long call, const int *sources,
+                            const unsigned int *draws, const void *workspace, size_t workspace_bytes,
+                            float *const *params_out, float *const *exp_avg_out, float *const *exp_avg_sq_out,
+                            float *max_radii2D_out, float *grad_accum_out, float *denom_out, void *stream);
+
 /* ---- measurement: per-stage HIP-event timing on the caller's stream ---------------------------- */
 /* bit i of stage_mask enables stage i (0 = off, the default: no events are recorded).  Enabled stages are
  * bracketed by hipEventRecord on the stream they are launched on; r2_profile_read synchronises the recorded

@@ -24,6 +24,7 @@ R2_GRAPH_LOSS_CHAIN = 17   # longest chain of float roundings in r2_graph_loss's
 R2_GRAPH_LOSS_HUB = 64     # incoming lists longer than this are summed by a whole wave in r2_graph_loss_backward
 R2_MERGE_HUB = 64          # ... and walked by a whole wave in r2_graph_match / r2_merge_count
 R2_MERGE_JACOBI_SWEEPS = 8
+R2_RELOCATE_SCAN_TILE = 4096   # elements per workgroup of r2_relocate_plan's 64-bit scan
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -63,6 +64,11 @@ _SIGNATURES = {
     "r2_merge_scratch_bytes": (C.c_size_t, [_i]),
     "r2_merge_count": (C.c_int, [_i, _i, _p, _p, _p, _fp, _f, _p, _fp, _fp, _p, _p, _p]),
     "r2_merge_emit": (C.c_int, [_i, _fp, _fp, _fp, _fp, _p, _i, _fp, _fp, _fp, _fp, _p, _p]),
+    "r2_gaussian_noise": (C.c_int, [_i, _fp, _fp, _fp, _fp, C.c_double, _f, _f, C.c_ulonglong, C.c_ulonglong, _p]),
+    "r2_relocate_workspace_bytes": (C.c_size_t, [_i, _i]),
+    "r2_relocate_plan": (C.c_int, [_i, _i, _p, _fp, _fp, _f, C.c_ulonglong, C.c_ulonglong, _p, _p, _p, C.c_size_t, _p, _p]),
+    "r2_relocate_emit": (C.c_int, [_i, _i, _p, _p, _p, _fp, _fp, _fp, _fp, _fp, _fp, _f, C.c_ulonglong, C.c_ulonglong, _p, _p,
+                                   _p, C.c_size_t, _p, _p, _p, _fp, _fp, _fp, _p]),
     "r2_tile_first_stats": (None, [C.POINTER(C.c_longlong), _i]),
     "r2_defer_count_control": (None, [_i]),
     "r2_defer_count_resolve": (C.c_int, [_i, C.POINTER(C.c_int), _p]),

@@ -44,6 +44,8 @@ SOURCES = {
     "graph_loss.hip": EXACT,
     # EXACT: the per-pair double arithmetic is the one include/r2hip.h states, and the two directions of an edge must round alike
     "gaussian_merge.hip": EXACT,
+    # EXACT: the noise and the spread are, operation for operation, the float32 restatement of tests/mcmc_ref.py
+    "gaussian_mcmc.hip": EXACT,
     "loss_ops.hip": FAST,
     "metric_ops.hip": FAST,
     "densify_ops.hip": EXACT,

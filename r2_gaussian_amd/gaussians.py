@@ -279,6 +279,45 @@ class GaussianModel:
         self._reset_stats()
         return info["pairs"]
 
+    @torch.no_grad()
+    def add_noise(self, call, noise_lr=5e5, density=0.005, sharpness=0.5, seed=0):
+        """Covariance-shaped Langevin noise on the positions of Gaussians whose density has faded (r2_gaussian_amd.mcmc, not in the
+        reference): xyz += lr_xyz * noise_lr * gate * R S^2 R^T eps with the current xyz learning rate, gate = 1 / (1 + exp(
+        sharpness (rho / density - 1))), eps from (seed, call, row): the trainer passes the iteration as `call`, so a resumed run
+        draws what the uninterrupted one would.  In place on the raw xyz, from the activations as they stand (``_act`` after a
+        step); moments and step counts are untouched.  The defaults are the original method's and untuned for CT.  No host read."""
+        from . import mcmc as MC
+        if self.P:
+            a = self._act
+            MC.position_noise(self._raw["xyz"], a["density"], a["scaling"], a["rotation"], float(self.lr["xyz"]) * float(noise_lr),
+                              density_threshold=density, sharpness=sharpness, seed=seed, call=call)
+
+    @torch.no_grad()
+    def relocate(self, call, dead_density, cap_max, growth=0.05, spread=0.0, seed=0):
+        """Keep a fixed budget (r2_gaussian_amd.mcmc.relocate, not in the reference): every Gaussian whose density is not above
+        dead_density (or that holds a non-finite parameter) moves onto a live one drawn in proportion to its density, and
+        n_new = max(0, min(cap_max, ceil((1 + growth) P)) - P) rows are appended the same way; a Gaussian drawn n times and its n
+        copies share its density, so with spread = 0 the field is unchanged.  Moved, appended and drawn rows get zero Adam
+        moments and statistics, every other row keeps its bits; step counts are kept, the activations refreshed.  -> n_new.
+        No host read."""
+        from . import mcmc as MC
+        P = self.P
+        if P == 0:
+            return 0
+        n_new = max(0, min(int(cap_max), int(np.ceil((1.0 + float(growth)) * P))) - P)
+        a = self._act
+        new_p, new_m, st, _info = MC.relocate(
+            {n: self._raw[n].detach() for n in NAMES}, {n: (self.exp_avg[n], self.exp_avg_sq[n]) for n in NAMES},
+            (self.max_radii2D, self.xyz_gradient_accum, self.denom), dead_density, n_new=n_new, spread=spread, seed=seed,
+            call=call, activated=(a["density"].detach(), a["scaling"].detach(), a["rotation"].detach()))
+        self._raw = {n: new_p[n] for n in NAMES}
+        self._raw["xyz"].requires_grad_(True)
+        self.exp_avg = {n: new_m[n][0] for n in NAMES}
+        self.exp_avg_sq = {n: new_m[n][1] for n in NAMES}
+        self.max_radii2D, self.xyz_gradient_accum, self.denom = st[0], st[1].reshape(-1, 1), st[2].reshape(-1, 1)
+        self._activate()
+        return n_new
+
     # ------------------------------------------------------------------------------------------------ files
     def save_ply(self, path):
         """point_cloud.pickle of RAW parameters (gaussian_model.py:263-286)."""

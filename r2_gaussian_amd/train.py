@@ -26,6 +26,12 @@ used, whatever it holds.  auto: the weights the case records (datagen's ``weight
 whose loop is then unchanged; none: ignore them; file: require them; noise: uncertainty.noise_weights of the raw training stack
 under the scanner config's noise model, times the recorded weights if there are any.  The FDK initialisation then sees the
 projections with their unmeasured pixels filled (weights.fill_unmeasured), ``--save_uncertainty`` the same weights.
+
+``--densify_strategy {threshold,mcmc}`` (not a flag of the reference; default threshold = its loop): mcmc keeps a fixed budget
+of Gaussians (mcmc.py, DESIGN.md section 4 "Relocation and position noise"): the densification slot relocates the Gaussians
+whose density is not above ``--dead_density`` onto live ones and grows the cloud by 5 % up to ``--cap_max``, every optimiser step
+is followed by position noise on the faded Gaussians, and the loss gains L1 penalties on density and scale.  Its defaults are
+the original method's numbers and have not been tuned for CT.
 """
 import argparse
 import os
@@ -65,6 +71,12 @@ class OptimizationParams:
     # opt-in merging of neighbouring Gaussians (GaussianModel.merge, not in the reference): off at merge_interval 0
     merge_interval, merge_cost, merge_k = 0, 0.1, 8
     merge_from_iter, merge_until_iter = 500, 15000
+    # opt-in fixed budget of Gaussians (GaussianModel.relocate / add_noise, not in the reference): off at "threshold".  The
+    # numbers, like add_noise's defaults, are the original method's ("3DGS as MCMC"); nobody has tuned them for CT data yet.
+    # cap_max None: max_num_gaussians
+    densify_strategy = "threshold"
+    dead_density, cap_max = 0.005, None
+    lambda_density_l1, lambda_scale_l1 = 0.01, 0.01
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -223,7 +235,13 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     the views or [V, H, W] (weights.resolve_weights): the image term becomes the weighted loss of losses.image_loss /
     image_loss_batch, in which a pixel whose weight is not > 0 is never used (train_projs may hold anything there, NaN
     included), and save_uncertainty weighs the Fisher diagonal with them.  The evaluation metrics stay unweighted.
-    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds, merged_pairs)."""
+    opt.densify_strategy = "mcmc" (absent = "threshold": the loop is then the one above and mcmc.py is never imported): the
+    densification slot calls gaussians.relocate(iteration, opt.dead_density, opt.cap_max or opt.max_num_gaussians, seed=seed)
+    instead of densify_and_prune; every step() is followed by gaussians.add_noise(iteration, seed=seed) at its defaults; and
+    the loss gains opt.lambda_density_l1 * density.mean() + opt.lambda_scale_l1 *
+    scaling.mean() on the activated leaves.  The generator is keyed by (seed, iteration): a resumed run draws what the
+    uninterrupted one would.
+    -> dict(model, evals {iteration: eval3d}, it_per_s, views_per_s, P, graph_builds, merged_pairs, relocations)."""
     W = int(views_per_step)
     if W < 1:
         raise ValueError("views_per_step must be >= 1, got %r" % (views_per_step,))
@@ -271,6 +289,16 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     merge_until = int(getattr(opt, "merge_until_iter", OptimizationParams.merge_until_iter))
     if merge_interval < 0:
         raise ValueError("merge_interval must be >= 0, got %r" % (merge_interval,))
+    strategy = getattr(opt, "densify_strategy", OptimizationParams.densify_strategy)
+    if strategy not in ("threshold", "mcmc"):
+        raise ValueError("densify_strategy must be 'threshold' or 'mcmc', got %r" % (strategy,))
+    mcmc = strategy == "mcmc"
+    if mcmc:
+        dead_density = float(getattr(opt, "dead_density", OptimizationParams.dead_density))
+        cap_max = getattr(opt, "cap_max", None)
+        cap_max = int(opt.max_num_gaussians if cap_max is None else cap_max)
+        lambda_density_l1 = float(getattr(opt, "lambda_density_l1", OptimizationParams.lambda_density_l1))
+        lambda_scale_l1 = float(getattr(opt, "lambda_scale_l1", OptimizationParams.lambda_scale_l1))
     tvN = torch.tensor([opt.tv_vol_size] * 3)
     tvS = torch.tensor(geometry["dVoxel"], dtype=torch.float32) * tvN
     settings = [_settings(v, dev) for v in train_views]
@@ -278,7 +306,7 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     pyrng = random.Random(seed)
     ckpt_path = osp.join(model_path, "ckpt")
     os.makedirs(ckpt_path, exist_ok=True)
-    out = {"evals": {}, "graph_builds": 0, "merged_pairs": 0}
+    out = {"evals": {}, "graph_builds": 0, "merged_pairs": 0, "relocations": 0}
     if first_iter == 0 and 0 in test_iterations:
         out["evals"][0] = evaluate(gaussians, 0, model_path, geometry, vol_gt, evals, eval_exact)
     stack = []
@@ -305,17 +333,25 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
                 nbr_graph = NG.knn_graph(xyz.detach(), graph_k)
                 out["graph_builds"] += 1
             loss = loss + lambda_graph * NG.graph_smoothness(dens[:, 0], nbr_graph, kind="l1")
+        if mcmc:   # the penalties that let Gaussians die: L1 on the activated densities and scales
+            loss = loss + lambda_density_l1 * dens.mean() + lambda_scale_l1 * scal.mean()
         loss.backward()
         with torch.no_grad():
             gaussians.add_densification_stats(radii, screen.grad, grad_scale=float(W))
             if opt.densify_from_iter < iteration < opt.densify_until_iter and iteration % opt.densification_interval == 0:
-                gaussians.densify_and_prune(opt.densify_grad_threshold, opt.density_min_threshold, opt.max_screen_size,
-                                            max_scale, opt.max_num_gaussians, densify_scale_threshold, bbox,
-                                            normals=torch.randn((2, gaussians.P, 3), generator=gen))
+                if mcmc:
+                    gaussians.relocate(iteration, dead_density, cap_max, seed=seed)
+                    out["relocations"] += 1
+                else:
+                    gaussians.densify_and_prune(opt.densify_grad_threshold, opt.density_min_threshold, opt.max_screen_size,
+                                                max_scale, opt.max_num_gaussians, densify_scale_threshold, bbox,
+                                                normals=torch.randn((2, gaussians.P, 3), generator=gen))
             if merge_interval > 0 and merge_from < iteration < merge_until and iteration % merge_interval == 0:
                 out["merged_pairs"] += gaussians.merge(merge_cost, k=merge_k)
             if iteration < opt.iterations:
                 gaussians.step()
+                if mcmc:
+                    gaussians.add_noise(iteration, seed=seed)
             else:
                 for t in gaussians.activated():
                     t.grad = None
@@ -409,6 +445,14 @@ def build_parser():
     g = ap.add_argument_group("Optimization Parameters")
     for k, v in vars(OptimizationParams).items():
         if k.startswith("_") or callable(v):
+            continue
+        if k == "densify_strategy":
+            g.add_argument("--" + k, default=v, choices=("threshold", "mcmc"),
+                           help="threshold: the reference's clone / split / prune.  mcmc: a fixed budget -- the densification slot "
+                                "relocates Gaussians whose density is not above --dead_density onto live ones and grows the cloud by "
+                                "5 %% up to --cap_max (default: max_num_gaussians), every step adds position noise to faded Gaussians, "
+                                "and the loss gains --lambda_density_l1 / --lambda_scale_l1 times the mean density / scale.  Its "
+                                "defaults are the original method's, untuned for CT")
             continue
         g.add_argument("--" + k, default=v, type=float if v is None else type(v))
     g = ap.add_argument_group("Pipeline Parameters")
