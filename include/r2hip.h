@@ -1063,6 +1063,33 @@ R2_API int r2_backproject_volume(int V, int H, int W, const float *rays /* [V,12
 R2_API size_t r2_tv_descent_scratch_bytes(int nx, int ny, int nz);
 R2_API int r2_tv_descent(int nx, int ny, int nz, float *vol, const float *step /* device scalar */, int n_iter, void *scratch,
                          size_t scratch_bytes, void *stream);
+/* r2_tv_prox: the proximal operator of the isotropic, unsmoothed total variation with a box constraint (ROF denoising;
+ * csrc/tv_prox.hip, recon.py: tv_prox, tv_denoise, fista_tv),
+ *     x = argmin_x 1/2 |x - y|^2 + lambda TV(x)  subject to  lo <= x <= hi,      TV(x) = sum_v |(D x)(v)|_2,
+ * for y, x [nx][ny][nz] (z fastest), D the forward differences of r2_tv_descent ((D_a x)(v) = x(v + e_a) - x(v), 0 at
+ * v_a = n_a - 1), by n_iter iterations of Beck and Teboulle's fast gradient projection on the dual p, r in R^{3 x N}, P_C the
+ * clamp to [lo, hi]:  r_1 = p_0 = 0, t_1 = 1, and for k = 1 .. n_iter
+ *     x_k = P_C(y - lambda D^T r_k),   q = r_k + (1 / (12 lambda)) D x_k,   p_k(v) = q(v) / max(1, |q(v)|_2),
+ *     t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2,   r_{k+1} = p_k + ((t_k - 1) / t_{k+1}) (p_k - p_{k-1});
+ * the result is x = P_C(y - lambda D^T p_{n_iter}), with (D^T p)(v) = sum_a (-p_a(v) [v_a < n_a - 1] + p_a(v - e_a) [v_a > 0]);
+ * 12 bounds |D|^2 (4 per axis).  n_iter = 0 gives x = P_C(y).
+ * lambda: a device scalar, read by the kernels (no host synchronisation).  A lambda that is <= 0 or NaN, or so small or so
+ * large that the float32 1 / (12 lambda) is infinite or zero, gives x = P_C(y) with no iteration.  lo, hi: host floats, lo <= hi,
+ * -inf / +inf for no bound.  The momentum factors (t_k - 1) / t_{k+1} are computed on the host in double and rounded to float32.
+ * Operation order, every operation a separately rounded IEEE float32 one (no FMA; division and square root correctly rounded),
+ * which tests/tv_prox_ref.py follows operation for operation:
+ *     t_a = (v_a > 0 ? d_a(v - e_a) : 0) - (v_a < n_a - 1 ? d_a(v) : 0),   div = (t_x + t_y) + t_z,   u = y(v) - lambda * div,
+ *     P_C(u) = u < lo ? lo : (u > hi ? hi : u)                                  (d = r_k, or p_{n_iter} for the result);
+ *     tau = 1 / (12 * lambda);   q_a = r_a + tau * (v_a < n_a - 1 ? x_k(v + e_a) - x_k(v) : 0);
+ *     n = sqrt((q_x * q_x + q_y * q_y) + q_z * q_z),   m = n > 1 ? n : 1,   p_a = q_a / m   (one division per component);
+ *     r_a' = p_a + mom * (p_a - p_a_previous).
+ * No allocation, no atomics, no reduction, no host synchronisation; bit-reproducible and independent of the launch shape.
+ * x may be y: the output pass reads y at its own voxel only (and the iterations never write x).  Neither may overlap the
+ * scratch: a device buffer of at least r2_tv_prox_scratch_bytes(nx, ny, nz) bytes (nine floats per voxel), 4-byte aligned,
+ * whose prior contents never matter. */
+R2_API size_t r2_tv_prox_scratch_bytes(int nx, int ny, int nz);
+R2_API int r2_tv_prox(int nx, int ny, int nz, const float *y, float *x, const float *lambda /* device scalar */, int n_iter,
+                      float lo, float hi, void *scratch, size_t scratch_bytes, void *stream);
 
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered

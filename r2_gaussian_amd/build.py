@@ -79,6 +79,8 @@ SOURCES = {
     # radius and the rectangle must round as theirs do (tests/test_gaussian_plan_gpu.py compares bit for bit)
     "gaussian_plan.hip": EXACT,
     "tv_descent.hip": FAST,
+    # EXACT: the per-voxel operation order is the one include/r2hip.h states and tests/tv_prox_ref.py follows bit for bit
+    "tv_prox.hip": EXACT,
     "dispatch.hip": FAST,
     "host_runtime.hip": FAST,
 }

@@ -118,9 +118,10 @@ def recon_volume(projs, angles, scanner_cfg, recon_method="fdk"):
 
 
 def init_pcd(projs, angles, scanner_cfg, n_points=50000, density_thresh=0.05, density_rescale=0.15, recon_method="fdk",
-             random_density_max=1.0, rng=np.random, save_path=None):
+             random_density_max=1.0, rng=np.random, save_path=None, tv_denoise=None):
     """initialize_pcd.py:36-90: [n_points, 4] = positions | densities.  ``rng``: the numpy generator the draws come from
-    (the reference seeds the global one with 0)."""
+    (the reference seeds the global one with 0).  ``tv_denoise``: None, or the lambda of ``recon.tv_prox`` (with x >= 0) the
+    reconstructed volume goes through before it is thresholded: the streaks of a sparse-view FDK otherwise pass the threshold."""
     if recon_method not in ("random", "fdk"):
         raise AssertionError("--recon_method not supported.")
     off, sVoxel = np.array(scanner_cfg["offOrigin"]), np.array(scanner_cfg["sVoxel"])
@@ -129,6 +130,9 @@ def init_pcd(projs, angles, scanner_cfg, n_points=50000, density_thresh=0.05, de
         dens = rng.rand(n_points) * random_density_max
     else:
         vol = recon_volume(projs, angles, scanner_cfg, recon_method)
+        if tv_denoise is not None:
+            from . import recon
+            vol = recon.tv_denoise(vol, tv_denoise, lo=0.0)
         valid = np.argwhere(vol > density_thresh)
         dVoxel = sVoxel / np.array(scanner_cfg["nVoxel"])
         assert valid.shape[0] >= n_points, "Valid voxels less than target number of sampling. Check threshold"
