@@ -8,8 +8,9 @@
 // weights become 64-bit integers, their prefix sum and the draws are exact -- so the sources and their counts depend on nothing
 // but the inputs, whatever order the device adds in; the only atomics are integer ones (the largest weight as its bit pattern,
 // the counts).  Compiled with -ffp-contract=off: the float arithmetic is, operation for operation, what tests/mcmc_ref.py
-// restates.  The inverse softplus of a split density is taken in double and rounded once.
+// restates.  The inverse softplus of a split density is taken in double and rounded once (cloud_model.hpp).
 #include "r2_common.hpp"
+#include "cloud_model.hpp"
 #include "philox.hpp"
 
 #include <cmath>
@@ -24,15 +25,6 @@ static_assert(RL_SCAN_TILE == RL_SCAN_THREADS * RL_SCAN_IPT, "r2hip.h states the
 constexpr long long RL_MAX_ROWS = 1ll << 29;          // P + n_new: keeps the prefix sum of the integer weights below 2^62
 
 inline unsigned mc_blocks(size_t n) { return (unsigned)((n + MC_THREADS - 1) / MC_THREADS); }
-
-// quat_to_rot (r2_math.hpp) of the quaternion as it comes, as rows: R[j][i] = row j, column i; Sigma = R S^2 R^T
-__device__ __forceinline__ void mc_rot(const float *__restrict__ q, float R[3][3])
-{
-    const float r = q[0], x = q[1], y = q[2], z = q[3];
-    R[0][0] = 1.f - 2.f * (y * y + z * z); R[0][1] = 2.f * (x * y - r * z); R[0][2] = 2.f * (x * z + r * y);
-    R[1][0] = 2.f * (x * y + r * z); R[1][1] = 1.f - 2.f * (x * x + z * z); R[1][2] = 2.f * (y * z - r * x);
-    R[2][0] = 2.f * (x * z - r * y); R[2][1] = 2.f * (y * z + r * x); R[2][2] = 1.f - 2.f * (x * x + y * y);
-}
 
 __device__ __forceinline__ bool mc_finite(float v) { return fabsf(v) < INFINITY; }
 
@@ -54,8 +46,8 @@ __global__ void __launch_bounds__(MC_THREADS) gaussian_noise_kernel(int P, float
     philox_normal3(seed, call, PHILOX_NOISE, (uint32_t)i, e);
     const float gate = 1.0f / (1.0f + expf(kappa * (rho / tau - 1.0f)));
     const float lg = (float)(lr * (double)gate);
-    float R[3][3], b[3];
-    mc_rot(q, R);
+    float R[3][3], b[3];   // Sigma = R S^2 R^T
+    quat_rot(q[0], q[1], q[2], q[3], R);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float a = (R[0][k] * e[0] + R[1][k] * e[1]) + R[2][k] * e[2];   // a = R^T eps
@@ -95,25 +87,21 @@ inline RlSpace rl_space(void *workspace, int P)
     return s;
 }
 
-struct RlIn {   // the cloud as the relocation reads it
-    const float *p[4];        // raw xyz [P,3], density [P,1], scaling [P,3], rotation [P,4]
-    const float *density_act;
-    const float *weights;     // nullable: the activated density
-};
-__device__ const int RL_W[4] = { 3, 1, 3, 4 };
-
-__global__ void __launch_bounds__(MC_THREADS) relocate_classify_kernel(int P, RlIn in, float dead_density, float *__restrict__ w,
-                                                                       uint32_t *__restrict__ dead, uint32_t *__restrict__ words)
+// weights: nullable (the activated density)
+__global__ void __launch_bounds__(MC_THREADS) relocate_classify_kernel(int P, CloudRows r, const float *density_act,
+                                                                       const float *weights, float dead_density,
+                                                                       float *__restrict__ w, uint32_t *__restrict__ dead,
+                                                                       uint32_t *__restrict__ words)
 {
     const int i = blockIdx.x * MC_THREADS + threadIdx.x;
     float wv = 0.f;
     if (i < P) {
         bool fin = true;
         for (int a = 0; a < 4; ++a)
-            for (int k = 0; k < RL_W[a]; ++k) fin = fin && mc_finite(in.p[a][(size_t)i * RL_W[a] + k]);
-        const float rho = in.density_act[i];
+            for (int k = 0; k < CLOUD_W[a]; ++k) fin = fin && mc_finite(r.p[a][(size_t)i * CLOUD_W[a] + k]);
+        const float rho = density_act[i];
         const bool alive = fin && rho > dead_density && rho < INFINITY;   // (a NaN fails both)
-        const float wi = in.weights ? in.weights[i] : rho;
+        const float wi = weights ? weights[i] : rho;
         if (alive && wi > 0.f && wi < INFINITY) wv = wi;
         w[i] = wv;
         dead[i] = alive ? 0u : 1u;
@@ -235,20 +223,11 @@ __global__ void __launch_bounds__(MC_THREADS) relocate_draw_kernel(int P, int n_
     atomicAdd(&draws[lo], 1u);
 }
 
-struct RlOut {
-    const float *m[4], *v[4];     // exp_avg, exp_avg_sq (all NULL: no optimizer state)
-    float *po[4], *mo[4], *vo[4];
-    const float *stat[3];         // max_radii2D, grad_accum, denom (all NULL: none)
-    float *stat_out[3];
-    const float *scaling_act, *rotation_act;
-};
-
-// softplus^-1 of a float, in double, rounded once
-__device__ __forceinline__ float rl_inv_softplus(float x) { return x > 20.f ? x : (float)log(expm1((double)x)); }
-
-// one thread per OUTPUT row: every word of the outputs has one writer
-__global__ void __launch_bounds__(MC_THREADS) relocate_emit_kernel(int P, int n_new, RlIn in, RlOut r, float spread, uint64_t seed,
-                                                                   uint64_t call, const uint32_t *__restrict__ dead,
+// one thread per OUTPUT row: every word of the outputs has one writer.  Moments and statistics: all there or all NULL
+__global__ void __launch_bounds__(MC_THREADS) relocate_emit_kernel(int P, int n_new, CloudRows r, const float *density_act,
+                                                                   const float *scaling_act,
+                                                                   const float *rotation_act, float spread,
+                                                                   uint64_t seed, uint64_t call, const uint32_t *__restrict__ dead,
                                                                    const uint32_t *__restrict__ deadpos,
                                                                    const uint64_t *__restrict__ cdf, const int *__restrict__ sources,
                                                                    const uint32_t *__restrict__ draws)
@@ -281,15 +260,7 @@ __global__ void __launch_bounds__(MC_THREADS) relocate_emit_kernel(int P, int n_
         src = (size_t)sidx;
         fresh = true;
     }
-    for (int a = 0; a < 4; ++a)
-        for (int k = 0; k < RL_W[a]; ++k) {
-            const size_t from = src * RL_W[a] + k, to = o * RL_W[a] + k;
-            r.po[a][to] = in.p[a][from];
-            if (r.mo[a]) {
-                r.mo[a][to] = fresh ? 0.f : r.m[a][from];
-                r.vo[a][to] = fresh ? 0.f : r.v[a][from];
-            }
-        }
+    cloud_copy_row(r, src, o, fresh);
     for (int k = 0; k < 3; ++k)
         if (r.stat_out[k]) r.stat_out[k][o] = fresh ? 0.f : r.stat[k][src];
     if (!fresh) return;
@@ -298,17 +269,18 @@ __global__ void __launch_bounds__(MC_THREADS) relocate_emit_kernel(int P, int n_
         return;
     }
     const uint32_t n = min(draws[src], 0x7ffffffeu);
-    r.po[1][o] = rl_inv_softplus(in.density_act[src] / (float)(n + 1u));
+    r.po[1][o] = inv_softplus_rounded(density_act[src] / (float)(n + 1u));
     if (slot >= 0 && spread > 0.f) {
         float e[3], R[3][3], v[3];
         philox_normal3(seed, call, PHILOX_SPREAD, (uint32_t)slot, e);
-        mc_rot(r.rotation_act + 4 * src, R);
+        const float *q = rotation_act + 4 * src;
+        quat_rot(q[0], q[1], q[2], q[3], R);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = r.scaling_act[3 * src + k] * e[k];
+        for (int k = 0; k < 3; ++k) v[k] = scaling_act[3 * src + k] * e[k];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const float d = (R[j][0] * v[0] + R[j][1] * v[1]) + R[j][2] * v[2];   // R S eps
-            r.po[0][3 * o + j] = in.p[0][3 * src + j] + spread * d;
+            r.po[0][3 * o + j] = r.p[0][3 * src + j] + spread * d;
         }
     }
 }
@@ -323,18 +295,6 @@ int scan64(const uint64_t *in, uint64_t *out, uint64_t *partial, int P, hipStrea
 }
 
 bool rl_shape_ok(int P, int n_new) { return P >= 0 && n_new >= 0 && (long long)P + n_new <= RL_MAX_ROWS && !(P == 0 && n_new > 0); }
-
-bool rl_in(const float *const *params, const float *density_act, const float *weights, RlIn &in)
-{
-    if (!params || !density_act) return false;
-    for (int a = 0; a < 4; ++a) {
-        in.p[a] = params[a];
-        if (!in.p[a]) return false;
-    }
-    in.density_act = density_act;
-    in.weights = weights;
-    return true;
-}
 
 }  // namespace
 }  // namespace r2
@@ -377,8 +337,8 @@ extern "C" int r2_relocate_plan(int P, int n_new, const float *const *params, co
     }
     if (counts_host) counts_host[0] = counts_host[1] = counts_host[2] = 0u;
     if (P == 0) return 0;
-    RlIn in;
-    if (!rl_in(params, density_act, weights, in) || !sources || !draws || !(dead_density == dead_density)) {
+    CloudRows r;
+    if (!cloud_rows(r, params).params || !density_act || !sources || !draws || !(dead_density == dead_density)) {
         set_error("r2_relocate_plan: a NULL array, or a NaN dead_density");
         return R2_ERR_INVALID;
     }
@@ -391,7 +351,8 @@ extern "C" int r2_relocate_plan(int P, int n_new, const float *const *params, co
     const size_t rows = (size_t)P + (size_t)n_new;
     R2_HIP_TRY(hipMemsetAsync(w.words, 0, RW_COUNT * sizeof(uint32_t), s));
     R2_HIP_TRY(hipMemsetAsync(draws, 0, (size_t)P * sizeof(uint32_t), s));
-    relocate_classify_kernel<<<dim3(mc_blocks((size_t)P)), dim3(MC_THREADS), 0, s>>>(P, in, dead_density, w.w, w.dead, w.words);
+    relocate_classify_kernel<<<dim3(mc_blocks((size_t)P)), dim3(MC_THREADS), 0, s>>>(P, r, density_act, weights, dead_density, w.w, w.dead,
+                                                                                     w.words);
     relocate_weight_kernel<<<dim3(mc_blocks((size_t)P)), dim3(MC_THREADS), 0, s>>>(P, w.w, w.words, w.q);
     int rc = scan64(w.q, w.cdf, w.partial, P, s);
     if (rc) return rc;
@@ -426,21 +387,11 @@ extern "C" int r2_relocate_emit(int P, int n_new, const float *const *params, co
         return R2_ERR_INVALID;
     }
     if (P == 0) return 0;
-    RlIn in;
-    RlOut r;
-    bool ok = rl_in(params, density_act, nullptr, in) && params_out && sources && draws && spread >= 0.f && spread < INFINITY &&
-              (spread == 0.f || (scaling_act && rotation_act));
-    const bool moments = exp_avg && exp_avg_sq && exp_avg_out && exp_avg_sq_out;
-    ok = ok && (moments || (!exp_avg && !exp_avg_sq && !exp_avg_out && !exp_avg_sq_out));
-    const bool stats = max_radii2D && grad_accum && denom && max_radii2D_out && grad_accum_out && denom_out;
-    ok = ok && (stats || (!max_radii2D && !grad_accum && !denom && !max_radii2D_out && !grad_accum_out && !denom_out));
-    for (int a = 0; a < 4 && ok; ++a) {
-        r.po[a] = params_out[a];
-        r.m[a] = moments ? exp_avg[a] : nullptr; r.v[a] = moments ? exp_avg_sq[a] : nullptr;
-        r.mo[a] = moments ? exp_avg_out[a] : nullptr; r.vo[a] = moments ? exp_avg_sq_out[a] : nullptr;
-        ok = r.po[a] && (!moments || (r.m[a] && r.v[a] && r.mo[a] && r.vo[a]));
-    }
-    if (!ok) {
+    CloudRows r;
+    const CloudGiven g = cloud_rows(r, params, exp_avg, exp_avg_sq, max_radii2D, grad_accum, denom, params_out, exp_avg_out,
+                                     exp_avg_sq_out, max_radii2D_out, grad_accum_out, denom_out);
+    if (!g.params || !g.params_out || g.moments == CLOUD_PART || g.stats == CLOUD_PART || !density_act || !sources || !draws ||
+        !(spread >= 0.f && spread < INFINITY) || (spread != 0.f && !(scaling_act && rotation_act))) {
         set_error("r2_relocate_emit: a NULL array, moment or statistics arrays given in part, spread not in [0, inf), or "
                   "spread > 0 without the activated scaling and rotation");
         return R2_ERR_INVALID;
@@ -449,13 +400,11 @@ extern "C" int r2_relocate_emit(int P, int n_new, const float *const *params, co
         set_error("r2_relocate_emit: the workspace must hold %zu bytes", r2_relocate_workspace_bytes(P, n_new));
         return R2_ERR_INVALID;
     }
-    r.stat[0] = max_radii2D; r.stat[1] = grad_accum; r.stat[2] = denom;
-    r.stat_out[0] = max_radii2D_out; r.stat_out[1] = grad_accum_out; r.stat_out[2] = denom_out;
-    r.scaling_act = scaling_act; r.rotation_act = rotation_act;
     hipStream_t s = (hipStream_t)stream;
     const RlSpace w = rl_space(const_cast<void *>(workspace), P);
     relocate_emit_kernel<<<dim3(mc_blocks((size_t)P + (size_t)n_new)), dim3(MC_THREADS), 0, s>>>(
-        P, n_new, in, r, spread, (uint64_t)seed, (uint64_t)call, w.dead, w.deadpos, w.cdf, sources, draws);
+        P, n_new, r, density_act, scaling_act, rotation_act, spread, (uint64_t)seed, (uint64_t)call, w.dead, w.deadpos, w.cdf, sources,
+        draws);
     R2_STAGE_CHECK(0, s, "relocate emit");
     return 0;
 }

@@ -7,6 +7,7 @@
 // anisotropic covariance loses 3-4 digits in float32, and the edges are few (P * K).  Compiled with -ffp-contract=off.  No
 // atomics: every output word has one writer and every reduction a fixed order, so two calls give the same bits.
 #include "r2_common.hpp"
+#include "cloud_model.hpp"
 
 #include <climits>
 #include <cmath>
@@ -30,14 +31,6 @@ __device__ __forceinline__ double mg_mass(int i, const float *__restrict__ densi
 }
 __device__ __forceinline__ bool mg_mass_ok(double m) { return m > 0.0 && m < INFINITY; }
 
-// Sigma = R^T diag(s^2) R, R = quat_to_rot(r, x, y, z) of the quaternion as given (r2_math.hpp: cov3d_from_scale_rot, mod = 1)
-__device__ __forceinline__ void mg_rot(double r, double x, double y, double z, double R[3][3])
-{
-    R[0][0] = 1.0 - 2.0 * (y * y + z * z); R[0][1] = 2.0 * (x * y - r * z); R[0][2] = 2.0 * (x * z + r * y);
-    R[1][0] = 2.0 * (x * y + r * z); R[1][1] = 1.0 - 2.0 * (x * x + z * z); R[1][2] = 2.0 * (y * z - r * x);
-    R[2][0] = 2.0 * (x * z - r * y); R[2][1] = 2.0 * (y * z + r * x); R[2][2] = 1.0 - 2.0 * (x * x + y * y);
-}
-
 __device__ __forceinline__ MgGauss mg_load(int i, const float *__restrict__ means, const float *__restrict__ density,
                                            const float *__restrict__ scaling, const float *__restrict__ rotation)
 {
@@ -56,8 +49,8 @@ __device__ __forceinline__ MgGauss mg_load(int i, const float *__restrict__ mean
     for (int k = 0; k < 4; ++k) fin = fin && isfinite(q[k]);
     g.ok = fin && rho > 0.f && s[0] > 0.f && s[1] > 0.f && s[2] > 0.f;
     g.mass = (double)rho * (double)s[0] * (double)s[1] * (double)s[2];
-    double R[3][3];
-    mg_rot((double)q[0], (double)q[1], (double)q[2], (double)q[3], R);
+    double R[3][3];   // Sigma = R^T diag(s^2) R of the quaternion as given (r2_math.hpp: cov3d_from_scale_rot, mod = 1)
+    quat_rot((double)q[0], (double)q[1], (double)q[2], (double)q[3], R);
     const double v[3] = { (double)s[0] * (double)s[0], (double)s[1] * (double)s[1], (double)s[2] * (double)s[2] };
     g.cov[0] = (v[0] * R[0][0] * R[0][0] + v[1] * R[1][0] * R[1][0]) + v[2] * R[2][0] * R[2][0];
     g.cov[1] = (v[0] * R[0][0] * R[0][1] + v[1] * R[1][0] * R[1][1]) + v[2] * R[2][0] * R[2][1];
@@ -330,7 +323,7 @@ __global__ void __launch_bounds__(MG_THREADS) merge_emit_kernel(int P, int Pn, c
     const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
                        R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
     if (det < 0.0) { R[2][0] = -R[2][0]; R[2][1] = -R[2][1]; R[2][2] = -R[2][2]; }
-    // the quaternion of R (the inverse of mg_rot), from the largest of 4 r^2, 4 x^2, 4 y^2, 4 z^2
+    // the quaternion of R (the inverse of quat_rot), from the largest of 4 r^2, 4 x^2, 4 y^2, 4 z^2
     const double tr = R[0][0] + R[1][1] + R[2][2];
     const double fr = 1.0 + tr, fx = 1.0 + R[0][0] - R[1][1] - R[2][2], fy = 1.0 - R[0][0] + R[1][1] - R[2][2],
                  fz = 1.0 - R[0][0] - R[1][1] + R[2][2];

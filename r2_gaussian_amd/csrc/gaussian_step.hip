@@ -8,6 +8,7 @@
 // rounded on its own (built with -ffp-contract=off) in the order torch's CUDA kernels evaluate it, so the results are
 // torch's up to the last-bit differences listed in INTEGRATION.md.
 #include "r2_common.hpp"
+#include "cloud_model.hpp"
 
 namespace r2 {
 namespace {
@@ -34,9 +35,6 @@ struct StepArgs {
     Group g[4];           // xyz, density, scaling, rotation
 };
 
-__device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // Softplus(beta=1, threshold=20)
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // the Adam update of one value (torch/optim/adam.py, non-fused and non-capturable: _single_tensor_adam / _multi_tensor_adam)
 __device__ __forceinline__ void adam(float &p, float &m, float &v, float g, const Group &G)
 {
@@ -55,11 +53,6 @@ __device__ __forceinline__ float4 normalize4(float4 q, float &n, float &d)
     return make_float4(q.x / d, q.y / d, q.z / d, q.w / d);
 }
 
-__device__ __forceinline__ float scale_act(float x, const Act &a)
-{
-    return a.bounded ? sigmoid_f(x) * a.range + a.lo : expf(x);
-}
-
 __global__ void __launch_bounds__(256) gaussian_activate_kernel(int P, const float *__restrict__ density,
                                                                 const float *__restrict__ scaling,
                                                                 const float *__restrict__ rotation, Act act,
@@ -69,7 +62,7 @@ __global__ void __launch_bounds__(256) gaussian_activate_kernel(int P, const flo
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
     density_act[i] = softplus_f(density[i]);
-    for (int k = 0; k < 3; ++k) scaling_act[3 * (size_t)i + k] = scale_act(scaling[3 * (size_t)i + k], act);
+    for (int k = 0; k < 3; ++k) scaling_act[3 * (size_t)i + k] = scale_act(scaling[3 * (size_t)i + k], act.bounded, act.range, act.lo);
     float n, d;
     reinterpret_cast<float4 *>(rotation_act)[i] = normalize4(reinterpret_cast<const float4 *>(rotation)[i], n, d);
 }
@@ -121,7 +114,7 @@ __global__ void __launch_bounds__(256) gaussian_adam_kernel(int P, StepArgs s, A
                 adam(x, m, v, g, G);
                 G.param[i3 + k] = x; G.exp_avg[i3 + k] = m; G.exp_avg_sq[i3 + k] = v;
             }
-            scaling_act[i3 + k] = scale_act(x, act);
+            scaling_act[i3 + k] = scale_act(x, act.bounded, act.range, act.lo);
         }
     }
 

@@ -11,9 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._boundary import _F32, call, ptr_table, require_gpu
-
-NAMES = ("xyz", "density", "scaling", "rotation")
+from ._boundary import _F32, NAMES, call, require_gpu, rows_emit, rows_in
 
 
 def densification_stats(radii, viewspace_grad, max_radii2D, grad_accum, denom):
@@ -56,11 +54,10 @@ def densify_and_prune(params, moments, max_radii2D, grad_accum, denom, normals, 
     require_gpu(xyz, "xyz")
     dev, P = xyz.device, xyz.shape[0]
     L = _lib.lib()
-    ps = [params[n].detach().to(_F32).contiguous() for n in NAMES]
-    have_m = moments is not None and all(moments.get(n) is not None for n in NAMES)
-    ms = [moments[n][0].contiguous() for n in NAMES] if have_m else [None] * 4
-    vs = [moments[n][1].contiguous() for n in NAMES] if have_m else [None] * 4
-    ga, dn, mr = (t.reshape(-1).to(_F32).contiguous() for t in (grad_accum, denom, max_radii2D))
+    if moments is not None and any(moments.get(n) is None for n in NAMES):
+        moments = None
+    rows = rows_in(params, moments, (max_radii2D, grad_accum, denom), P, dev)
+    ps, (mr, ga, dn) = rows[0], rows[3]
     nrm = normals.to(device=dev, dtype=_F32).contiguous()
     assert nrm.shape == (2, P, 3)
     lo, hi = (float(scale_bound[0]), float(scale_bound[1])) if scale_bound is not None else (1.0, 0.0)
@@ -74,16 +71,8 @@ def densify_and_prune(params, moments, max_radii2D, grad_accum, denom, normals, 
     Pn = sum(cnt)
     if Pn == 0:
         raise ValueError("No Gaussian left. Change adaptive control hyperparameters!")   # train.py:169-172
-    widths = (3, 1, 3, 4)
-    po = [torch.empty((Pn, w), dtype=_F32, device=dev) for w in widths]
-    mo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
-    vo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in widths]
-    mro, gao, dno = (torch.empty(Pn, dtype=_F32, device=dev) for _ in range(3))
-    call("r2_densify_emit", dev, P, ptr_table(ps), ptr_table(ms) if have_m else None, ptr_table(vs) if have_m else None, mr, ga,
-         dn, nrm, *common, scratch, ptr_table(po), ptr_table(mo) if have_m else None, ptr_table(vo) if have_m else None, mro,
-         gao, dno)
-    new_params = dict(zip(NAMES, po))
-    new_moments = {n: (m, v) for n, m, v in zip(NAMES, mo, vo)} if have_m else None
+    new_params, new_moments, (mro, gao, dno) = rows_emit(Pn, dev, rows, lambda tin, tout, so: call(
+        "r2_densify_emit", dev, P, *tin, mr, ga, dn, nrm, *common, scratch, *tout, *so))
     return new_params, new_moments, mro, gao, dno, cnt
 
 

@@ -15,10 +15,8 @@ import torch
 from torch import nn
 
 from . import densify as D
-from ._boundary import _F32, call, ptr_table, require_gpu
+from ._boundary import _F32, NAMES, WIDTHS, call, ptr_table, require_gpu
 
-NAMES = ("xyz", "density", "scaling", "rotation")
-WIDTHS = {"xyz": 3, "density": 1, "scaling": 3, "rotation": 4}
 BETAS, ADAM_EPS = (0.9, 0.999), 1e-15      # gaussian_model.py:213 (torch.optim.Adam defaults, eps 1e-15)
 EPS = 1e-5                                  # gaussian_model.py:34: keeps the initial scales inside the bound
 
@@ -54,7 +52,7 @@ def activate(density, scaling, rotation, scale_bound=None):
     lo, hi = _bound(scale_bound)
     ins = [t.detach().to(_F32).contiguous() for t in (density, scaling, rotation)]
     assert [tuple(t.shape) for t in ins] == [(P, 1), (P, 3), (P, 4)]
-    outs = [torch.empty((P, w), dtype=_F32, device=dev) for w in (1, 3, 4)]
+    outs = [torch.empty((P, WIDTHS[n]), dtype=_F32, device=dev) for n in NAMES[1:]]
     call("r2_gaussian_activate", dev, P, *ins, lo, hi, *outs)
     return tuple(outs)
 
@@ -92,8 +90,31 @@ class GaussianModel:
 
     def _activate(self):
         d, s, r = activate(self._raw["density"], self._raw["scaling"], self._raw["rotation"], self.scale_bound) if self.P else (
-            torch.empty((0, w), dtype=_F32, device=self.device) for w in (1, 3, 4))
+            torch.empty((0, WIDTHS[n]), dtype=_F32, device=self.device) for n in NAMES[1:])
         self._act = {"density": d.requires_grad_(True), "scaling": s.requires_grad_(True), "rotation": r.requires_grad_(True)}
+
+    def _install(self, raw, moments, stats=None):
+        """The rows a surgery returned: raw parameters and Adam moments (dicts by name) and the statistics (max_radii2D,
+        grad_accum, denom; None: reset).  Step counts stay, the activations are refreshed."""
+        self._raw = {n: raw[n] for n in NAMES}
+        self._raw["xyz"].requires_grad_(True)
+        self.exp_avg = {n: moments[n][0] for n in NAMES}
+        self.exp_avg_sq = {n: moments[n][1] for n in NAMES}
+        if stats is None:
+            self._reset_stats()
+        else:
+            self.max_radii2D, self.xyz_gradient_accum, self.denom = stats[0], stats[1].reshape(-1, 1), stats[2].reshape(-1, 1)
+        self._activate()
+
+    def _raw_from_activated(self, density, scales):
+        """-> (raw density, raw scales) through the inverse activations as gaussian_model.py:133-164 forms them: the inverse
+        softplus, and the inverse scaling activation of the scales clamped EPS inside the bound.  On the inputs' devices."""
+        density = torch.log(torch.exp(density) - 1)                                     # inverse_softplus
+        if self.scale_bound is None:
+            return density, torch.log(scales)
+        lo, hi = self.scale_bound
+        scales = torch.relu((torch.clamp(scales, lo + EPS, hi - EPS) - lo) / (hi - lo))
+        return density, torch.log(scales / (1 - scales))                                # inverse_sigmoid
 
     def _reset_stats(self):
         self.max_radii2D = torch.zeros(self.P, dtype=_F32, device=self.device)
@@ -148,17 +169,9 @@ class GaussianModel:
         from ._C import distCUDA2
         self.spatial_lr_scale = spatial_lr_scale
         pts = torch.as_tensor(np.asarray(xyz), dtype=_F32).to(self.device).contiguous()
-        dens = torch.as_tensor(np.asarray(density), dtype=_F32).reshape(-1, 1)
-        dens = torch.log(torch.exp(dens) - 1).to(self.device)                       # inverse_softplus
         dist = torch.sqrt(torch.clamp_min(distCUDA2(pts), 0.001 ** 2))
-        if self.scale_bound is not None:
-            lo, hi = self.scale_bound
-            dist = torch.clamp(dist, lo + EPS, hi - EPS)
-            scales = torch.relu((dist - lo) / (hi - lo))
-            scales = torch.log(scales / (1 - scales))                                  # inverse_sigmoid
-        else:
-            scales = torch.log(dist)
-        scales = scales[..., None].repeat(1, 3)
+        dens, scales = self._raw_from_activated(torch.as_tensor(np.asarray(density), dtype=_F32).reshape(-1, 1), dist)
+        dens, scales = dens.to(self.device), scales[..., None].repeat(1, 3)
         rots = torch.zeros((pts.shape[0], 4), dtype=_F32, device=self.device)
         rots[:, 0] = 1
         self._set(pts, dens, scales, rots)
@@ -237,12 +250,7 @@ class GaussianModel:
             dict(self._raw), {n: (self.exp_avg[n], self.exp_avg_sq[n]) for n in NAMES}, self.max_radii2D,
             self.xyz_gradient_accum, self.denom, normals, max_grad, densify_scale_threshold, min_density, bbox,
             self.scale_bound, do_densify=self.P < max_num_gaussians, max_screen_size=max_screen_size, max_scale=max_scale)
-        self._raw = {n: new_p[n] for n in NAMES}
-        self._raw["xyz"].requires_grad_(True)
-        self.exp_avg = {n: new_m[n][0] for n in NAMES}
-        self.exp_avg_sq = {n: new_m[n][1] for n in NAMES}
-        self.max_radii2D, self.xyz_gradient_accum, self.denom = mr, ga.reshape(-1, 1), dn.reshape(-1, 1)
-        self._activate()
+        self._install(new_p, new_m, (mr, ga, dn))
 
     @torch.no_grad()
     def merge(self, max_cost, k=8, rounds=12):
@@ -263,20 +271,13 @@ class GaussianModel:
             return 0
         keep = src[:, 0].long()
         merged = (src[:, 1] >= 0)[:, None]
-        if self.scale_bound is not None:
-            lo, hi = self.scale_bound
-            s = torch.clamp(m_scal, lo + EPS, hi - EPS)
-            s = torch.relu((s - lo) / (hi - lo))
-            s = torch.log(s / (1 - s))                                                  # inverse_sigmoid
-        else:
-            s = torch.log(m_scal)
-        fresh = {"xyz": m_xyz, "density": torch.log(torch.exp(m_dens) - 1), "scaling": s, "rotation": m_rot}   # inverse_softplus
+        d, s = self._raw_from_activated(m_dens, m_scal)
+        fresh = {"xyz": m_xyz, "density": d, "scaling": s, "rotation": m_rot}
         zero = torch.zeros((), dtype=_F32, device=self.device)
         raw = {n: torch.where(merged, fresh[n], self._raw[n].detach()[keep]) for n in NAMES}
         moments = {n: (torch.where(merged, zero, self.exp_avg[n][keep]), torch.where(merged, zero, self.exp_avg_sq[n][keep]))
                    for n in NAMES}
-        self._set(raw["xyz"], raw["density"], raw["scaling"], raw["rotation"], moments=moments, steps=self.steps)
-        self._reset_stats()
+        self._install(raw, moments)
         return info["pairs"]
 
     @torch.no_grad()
@@ -310,12 +311,7 @@ class GaussianModel:
             {n: self._raw[n].detach() for n in NAMES}, {n: (self.exp_avg[n], self.exp_avg_sq[n]) for n in NAMES},
             (self.max_radii2D, self.xyz_gradient_accum, self.denom), dead_density, n_new=n_new, spread=spread, seed=seed,
             call=call, activated=(a["density"].detach(), a["scaling"].detach(), a["rotation"].detach()))
-        self._raw = {n: new_p[n] for n in NAMES}
-        self._raw["xyz"].requires_grad_(True)
-        self.exp_avg = {n: new_m[n][0] for n in NAMES}
-        self.exp_avg_sq = {n: new_m[n][1] for n in NAMES}
-        self.max_radii2D, self.xyz_gradient_accum, self.denom = st[0], st[1].reshape(-1, 1), st[2].reshape(-1, 1)
-        self._activate()
+        self._install(new_p, new_m, st)
         return n_new
 
     # ------------------------------------------------------------------------------------------------ files

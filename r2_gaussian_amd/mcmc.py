@@ -19,10 +19,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._boundary import _F32, call as _call, f32c, ptr_table, require_gpu, workspace
+from ._boundary import _F32, NAMES, WIDTHS, call as _call, cloud_checked, f32c, require_gpu, rows_emit, rows_in, workspace
 
-NAMES = ("xyz", "density", "scaling", "rotation")
-_WIDTHS = (3, 1, 3, 4)
 MAX_ROWS = 1 << 29
 
 
@@ -31,18 +29,6 @@ def _u64(v, name):
     if not 0 <= v < 1 << 64:
         raise ValueError("%s must fit 64 unsigned bits, got %r" % (name, v))
     return C.c_ulonglong(v)
-
-
-def _activated(P, dev, density, scaling, rotation):
-    out = []
-    for t, w, name in zip((density, scaling, rotation), (1, 3, 4), ("density", "scaling", "rotation")):
-        require_gpu(t, name)
-        if t.ndim == 1 and w == 1:
-            t = t[:, None]
-        if tuple(t.shape) != (P, w) or t.device != dev:
-            raise ValueError("activated %s must be [%d, %d] on %s, got %s on %s" % (name, P, w, dev, tuple(t.shape), t.device))
-        out.append(f32c(t.detach()))
-    return out
 
 
 def position_noise(xyz, density, scaling, rotation, lr, density_threshold=0.005, sharpness=0.5, seed=0, call=0):
@@ -56,7 +42,7 @@ def position_noise(xyz, density, scaling, rotation, lr, density_threshold=0.005,
         raise ValueError("xyz must be a contiguous float32 [P, 3] tensor (it is updated in place), got %s %s" % (
             tuple(xyz.shape), xyz.dtype))
     P, dev = xyz.shape[0], xyz.device
-    d, s, r = _activated(P, dev, density, scaling, rotation)
+    d, s, r = cloud_checked((density, scaling, rotation), P, dev, NAMES[1:])
     if P:
         _call("r2_gaussian_noise", dev, P, xyz.detach(), d, s, r, float(lr), float(density_threshold), float(sharpness),
               _u64(seed, "seed"), _u64(call, "call"))
@@ -88,21 +74,8 @@ def relocate(params, moments, stats, dead_density, n_new=0, weights=None, spread
     spread = float(spread)
     if not 0.0 <= spread < float("inf"):
         raise ValueError("spread must be in [0, inf), got %r" % (spread,))
-    ps = [f32c(params[n].detach()) for n in NAMES]
-    for n, t, w in zip(NAMES, ps, _WIDTHS):
-        if tuple(t.shape) != (P, w) or t.device != dev:
-            raise ValueError("%s must be [%d, %d] on %s, got %s" % (n, P, w, dev, tuple(t.shape)))
-    have_m = moments is not None
-    ms = [f32c(moments[n][0]) for n in NAMES] if have_m else [None] * 4
-    vs = [f32c(moments[n][1]) for n in NAMES] if have_m else [None] * 4
-    for t, w in zip(ms + vs, _WIDTHS + _WIDTHS):
-        if t is not None and (tuple(t.shape) != (P, w) or t.device != dev):
-            raise ValueError("a moment array is %s, not [%d, %d] on %s" % (tuple(t.shape), P, w, dev))
-    st = None
-    if stats is not None:
-        st = [f32c(t.detach()).reshape(-1) for t in stats]
-        if len(st) != 3 or any(t.numel() != P or t.device != dev for t in st):
-            raise ValueError("stats must be (max_radii2D, grad_accum, denom) with %d elements each" % P)
+    rows = rows_in(params, moments, stats, P, dev)
+    ps, st = rows[0], rows[3]
     if weights is not None:
         require_gpu(weights, "weights")
         weights = f32c(weights.detach()).reshape(-1)
@@ -111,34 +84,28 @@ def relocate(params, moments, stats, dead_density, n_new=0, weights=None, spread
     if activated is None:
         from .gaussians import activate
         activated = activate(ps[1], ps[2], ps[3], scale_bound) if P else tuple(
-            torch.empty((0, w), dtype=_F32, device=dev) for w in (1, 3, 4))
-    act = _activated(P, dev, *activated)
+            torch.empty((0, WIDTHS[n]), dtype=_F32, device=dev) for n in NAMES[1:])
+    act = cloud_checked(activated, P, dev, NAMES[1:])
     Pn = P + n_new
-    po = [torch.empty((Pn, w), dtype=_F32, device=dev) for w in _WIDTHS]
-    mo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in _WIDTHS]
-    vo = [torch.empty((Pn, w), dtype=_F32, device=dev) if have_m else None for w in _WIDTHS]
-    so = [torch.empty((Pn,), dtype=_F32, device=dev) for _ in range(3)] if st is not None else [None] * 3
     sources = torch.empty((Pn,), dtype=torch.int32, device=dev)     # both written in full by r2_relocate_plan
     draws = torch.empty((P,), dtype=torch.int32, device=dev)
     info = dict(P=Pn, sources=sources, draws=draws)
-    if P:
+    host = (C.c_uint * 3)() if counts else None
+
+    def emit(tin, tout, so):
+        if not P:
+            return
         nbytes = int(_lib.lib().r2_relocate_workspace_bytes(P, n_new))
         ws = workspace(nbytes, dev)
-        host = (C.c_uint * 3)() if counts else None
         sd, cl = _u64(seed, "seed"), _u64(call, "call")
-        _call("r2_relocate_plan", dev, P, n_new, ptr_table(ps), act[0], weights, float(dead_density), sd, cl, sources, draws, ws,
-              nbytes, host)
-        _call("r2_relocate_emit", dev, P, n_new, ptr_table(ps), ptr_table(ms) if have_m else None,
-              ptr_table(vs) if have_m else None, act[0], act[1], act[2], *(st if st is not None else [None] * 3), spread, sd, cl,
-              sources, draws, ws, nbytes, ptr_table(po), ptr_table(mo) if have_m else None, ptr_table(vo) if have_m else None,
-              *so)
-        if counts:
-            info.update(dead=int(host[0]), alive=int(host[1]), drawable=int(host[2]))
-    elif counts:
-        info.update(dead=0, alive=0, drawable=0)
-    new_params = dict(zip(NAMES, po))
-    new_moments = {n: (m, v) for n, m, v in zip(NAMES, mo, vo)} if have_m else None
-    return new_params, new_moments, (tuple(so) if st is not None else None), info
+        _call("r2_relocate_plan", dev, P, n_new, tin[0], act[0], weights, float(dead_density), sd, cl, sources, draws, ws, nbytes, host)
+        _call("r2_relocate_emit", dev, P, n_new, *tin, *act, *(st if st is not None else [None] * 3), spread, sd, cl, sources, draws,
+              ws, nbytes, *tout, *so)
+
+    new_params, new_moments, new_stats = rows_emit(Pn, dev, rows, emit)
+    if counts:
+        info.update(dead=int(host[0]), alive=int(host[1]), drawable=int(host[2]))
+    return new_params, new_moments, new_stats, info
 
 
 __all__ = ["position_noise", "relocate"]

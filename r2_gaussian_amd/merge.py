@@ -15,11 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._boundary import _F32, call, require_gpu, workspace
+from ._boundary import _F32, WIDTHS, call, cloud_checked, require_gpu, workspace
 from .graph import NeighbourGraph, knn_graph
 
 _I32 = torch.int32
-_WIDTHS = (("xyz", 3), ("density", 1), ("scaling", 3), ("rotation", 4))
 
 
 def _check_graph(graph):
@@ -31,17 +30,7 @@ def _check_graph(graph):
 def _params(graph, xyz, density, scaling, rotation):
     """The four activated tensors as contiguous float32 on the graph's device; density may be [P] or [P, 1]."""
     dev = _check_graph(graph)
-    out = []
-    for (name, w), t in zip(_WIDTHS, (xyz, density, scaling, rotation)):
-        require_gpu(t, name)
-        if name == "density" and t.ndim == 1:
-            t = t[:, None]
-        if t.ndim != 2 or tuple(t.shape) != (graph.P, w):
-            raise ValueError("%s must have dimensions (%d, %d) like the graph, got %s" % (name, graph.P, w, tuple(t.shape)))
-        if t.device != dev:
-            raise ValueError("%s and the graph live on different devices" % name)
-        out.append(t.detach().to(_F32).contiguous())
-    return out
+    return cloud_checked((xyz, density, scaling, rotation), graph.P, dev)
 
 
 def _edge_array(graph, t, name, dtype):
@@ -121,7 +110,7 @@ def merge_pairs(graph, cost, max_cost, mate, xyz, density, scaling, rotation):
          counts)
     pairs, n_open = int(counts[0]), int(counts[1])
     Pn = P - pairs
-    outs = [torch.empty((Pn, w), dtype=_F32, device=dev) for _n, w in _WIDTHS]
+    outs = [torch.empty((Pn, w), dtype=_F32, device=dev) for w in WIDTHS.values()]
     src = torch.empty((Pn, 2), dtype=_I32, device=dev)
     call("r2_merge_emit", dev, P, *p, scratch, Pn, *outs, src)
     return outs[0], outs[1], outs[2], outs[3], src, dict(pairs=pairs, open=n_open, P=Pn)

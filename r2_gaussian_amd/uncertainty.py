@@ -22,11 +22,11 @@ import numpy as np
 import torch
 
 from . import projector
-from ._boundary import _F32, call, cloud, f32c, require_gpu
+from ._boundary import _F32, NAMES, WIDTHS, call, cloud, f32c, require_gpu
 from .field import _check_cloud, inverse_permutation, morton_order
 from .gaussian_projector import _call_planned, _checked_plan, check_projection_arguments, world_ray_params
 
-CloudTuple = collections.namedtuple("CloudTuple", ("xyz", "density", "scaling", "rotation"))
+CloudTuple = collections.namedtuple("CloudTuple", NAMES)
 CloudTuple.__doc__ = "One float32 tensor per parameter group, in the shapes of the cloud: [P,3], [P,1], [P,3], [P,4]."
 
 
@@ -41,7 +41,7 @@ def _check_group_tuple(t, P, device, name):
     if not isinstance(t, (tuple, list)) or len(t) != 4:
         raise ValueError("%s must be a 4-tuple (xyz, density, scaling, rotation), got %r" % (name, type(t).__name__))
     out = []
-    for g, a, cols in zip(CloudTuple._fields, t, (3, 1, 3, 4)):
+    for (g, cols), a in zip(WIDTHS.items(), t):
         ok = isinstance(a, torch.Tensor) and (tuple(a.shape) == (P, cols) or (cols == 1 and tuple(a.shape) == (P,)))
         if not ok:
             raise ValueError("%s.%s must be a tensor [%d,%d], got %s" % (name, g, P, cols, tuple(getattr(a, "shape", ()))))
