@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Generates tests/golden/*.npz -- the committed golden vectors that pin the CPU oracle.
 
-Run in the build container only (it needs /root/reference):   python tests/golden/make_golden.py
+Run in the build container only (it needs /root/reference):   python tests/golden/make_golden.py [NAME_PREFIX ...]
+(with prefixes, only the fixtures whose file name starts with one of them are written)
 
 Two sources, both the REFERENCE ITSELF executed here:
 
@@ -41,7 +42,12 @@ def _load_ref_module(relpath, name):
     return m
 
 
+ONLY = tuple(sys.argv[1:])   # name prefixes: write these fixtures only (a new fixture must not rewrite the committed ones)
+
+
 def save(name, **arrays):
+    if ONLY and not name.startswith(ONLY):
+        return
     path = os.path.join(HERE, name)
     np.savez_compressed(path, **arrays)
     print("wrote %-34s %7.1f KiB" % (name, os.path.getsize(path) / 1024.0))
@@ -75,17 +81,27 @@ def raster_case(name, P, H, W, scanner, angle, seed, scale_mult=1.0, scale_modif
     save(name, num_rendered=np.array(st["num_rendered"]), **ins, **flat("fw_", st), **flat("bw_", g))
 
 
-def voxel_case(name, P, nVoxel, sVoxel, center, seed, scale_mult=1.0, scale_modifier=1.0):
+def voxel_case(name, P, nVoxel, sVoxel, center, seed, scale_mult=1.0, scale_modifier=1.0, precomp=False):
     c = S.make_cloud(P, seed=seed, scale_mult=scale_mult)
     xyz, rho, sc, q = (t.numpy().copy() for t in (c.xyz, c.density, c.scales, c.rotations))
-    st = Rf.voxel_forward(xyz, rho, sc, q, scale_modifier, None, nVoxel, sVoxel, center)
+    cov, q_fw, sc_bw, q_bw = None, q, sc, q
+    if precomp:
+        # cov3D_precomp path: the covariance of ANOTHER cloud's scales and rotations (the reference's own cov3D for them), so it
+        # cannot be recovered from in_scales.  The forward still reads the scales (radius from the raw scales, VOX/forward.cu:137-143)
+        # but no rotations; the backward reads neither.
+        d = S.make_cloud(P, seed=seed + 1000, scale_mult=scale_mult)
+        cov = Rf.voxel_forward(xyz, rho, d.scales.numpy().copy(), d.rotations.numpy().copy(), scale_modifier, None, nVoxel,
+                               sVoxel, center)["cov3D"]
+        q_fw, sc_bw, q_bw = None, None, None
+    st = Rf.voxel_forward(xyz, rho, sc, q_fw, scale_modifier, cov, nVoxel, sVoxel, center)
     g_ = torch.Generator().manual_seed(seed + 200)
     n = int(np.prod(nVoxel))
     dL = ((torch.rand(*nVoxel, generator=g_) * 2 - 1) / n).numpy()
-    g = Rf.voxel_backward(st, xyz, sc, q, scale_modifier, None, dL)
+    g = Rf.voxel_backward(st, xyz, sc_bw, q_bw, scale_modifier, cov, dL)
+    ins = {} if cov is None else dict(in_cov3D_precomp=cov)
     save(name, num_rendered=np.array(st["num_rendered"]), in_means3D=xyz, in_opacities=rho, in_scales=sc, in_rotations=q,
          in_dL_dvol=dL, in_nVoxel=np.array(nVoxel, np.int32), in_sVoxel=np.array(sVoxel, np.float64),
-         in_center=np.array(center, np.float64), in_params=np.array([scale_modifier], np.float64),
+         in_center=np.array(center, np.float64), in_params=np.array([scale_modifier], np.float64), **ins,
          **flat("fw_", st), **flat("bw_", g))
 
 
@@ -167,6 +183,10 @@ def main():
     voxel_case("voxel_200_20x16x24.npz", 200, (20, 16, 24), (2.0, 1.6, 2.4), (0.0, 0.0, 0.0), seed=7, scale_mult=2.0)
     voxel_case("voxel_tv_150_16x16x16.npz", 150, (16, 16, 16), (0.25, 0.25, 0.25), (0.2, -0.1, 0.3), seed=8, scale_mult=1.0,
                scale_modifier=1.0)
+    voxel_case("voxel_mod_180_20x16x24.npz", 180, (20, 16, 24), (2.0, 1.6, 2.4), (0.0, 0.0, 0.0), seed=9, scale_mult=2.0,
+               scale_modifier=0.7)
+    voxel_case("voxel_precomp_160_16x16x16.npz", 160, (16, 16, 16), (0.25, 0.25, 0.25), (0.2, -0.1, 0.3), seed=10,
+               scale_mult=1.0, scale_modifier=1.3, precomp=True)
     python_goldens()
 
 

@@ -125,17 +125,24 @@ def hip_raster_backward(h, c, v, dL, dev):
     return {n: t.cpu().numpy() for n, t in zip(names, res)}
 
 
-def oracle_voxel(O, c, nVoxel, sVoxel, center, scale_modifier=1.0, render=True):
+def oracle_voxel(O, c, nVoxel, sVoxel, center, scale_modifier=1.0, render=True, cov3D_precomp=None):
+    """cov3D_precomp: the covariance the forward uses in place of scales + rotations; the scales still go in (the reference takes
+    the radius from the raw scales, quirk Q5), the rotations do not."""
     xyz, rho, sc, q = cloud_np(c)
-    return O.voxel_forward(xyz, rho, sc, q, scale_modifier, None, nVoxel, sVoxel, center, render=render)
+    if cov3D_precomp is not None:
+        q = None
+    return O.voxel_forward(xyz, rho, sc, q, scale_modifier, cov3D_precomp, nVoxel, sVoxel, center, render=render)
 
 
-def hip_voxel(c, nVoxel, sVoxel, center, dev, debug=False, scale_modifier=1.0, slab=None):
+def hip_voxel(c, nVoxel, sVoxel, center, dev, debug=False, scale_modifier=1.0, slab=None, cov3D_precomp=None):
     """slab = (tile_x0, tile_x1): the x-slab call (r2_voxel_forward_slab) on those tile layers of the grid; the state and the
-    volume read back are then the slab's ([x1 - x0, ny, nz], tiles renumbered from the slab's first layer)."""
+    volume read back are then the slab's ([x1 - x0, ny, nz], tiles renumbered from the slab's first layer).
+    cov3D_precomp: the forward gets it with the scales and an empty `rotations` (the ABI requires the scales, csrc/voxel_api.hip)."""
     from r2_gaussian_amd import _C, _lib
     e = torch.empty(0)
-    args = (c.xyz.to(dev), c.density.to(dev), c.scales.to(dev), c.rotations.to(dev), scale_modifier, e,
+    q = c.rotations.to(dev) if cov3D_precomp is None else e
+    cp = e if cov3D_precomp is None else torch.as_tensor(cov3D_precomp).to(dev)
+    args = (c.xyz.to(dev), c.density.to(dev), c.scales.to(dev), q, scale_modifier, cp,
             nVoxel[0], nVoxel[1], nVoxel[2], sVoxel[0], sVoxel[1], sVoxel[2], center[0], center[1], center[2],
             False, debug)
     if slab is None:
@@ -247,6 +254,47 @@ def took_tile_first(h):
     return int(h["host_words"][3]) == TF_MARK
 
 
+def served(fn):
+    """Run fn(); -> (its result, {path counter of r2_path_stats: increment})."""
+    from r2_gaussian_amd import _lib
+    before = _lib.path_stats()
+    out = fn()
+    after = _lib.path_stats()
+    return out, {k: after[k] - before.get(k, 0) for k in after if after[k] != before.get(k, 0)}
+
+
+def voxel_chains(n):
+    """The production chains that can serve the grid n: the small-grid path and the general chain through x-slab calls up to
+    64 tiles, the stick-first and the general chain (r2_voxel_sticks_control) above."""
+    g = [(k + 7) // 8 for k in n]
+    if g[0] * g[1] * g[2] <= 64 and max(g) <= 8:
+        return ["small", "general-slab"]
+    return ["sticks", "general"]
+
+
+def run_voxel_chain(chain, c, n, s, ctr, gpu, sticks_mode, **inputs):
+    """One production forward on the named chain, asserted by its path counter; `inputs` (scale_modifier, cov3D_precomp) go to
+    hip_voxel.  -> (volume, forward state of a full call or None, path counter increments)."""
+    if chain == "general-slab":
+        gx = (n[0] + 7) // 8
+        assert gx >= 2
+        cut = gx // 2
+        parts, sv_all = [], {}
+        for t0, t1 in ((0, cut), (cut, gx)):
+            h, sv = served(lambda: hip_voxel(c, n, s, ctr, gpu, slab=(t0, t1), **inputs))
+            parts.append(h["vol"])
+            for k, v in sv.items():
+                sv_all[k] = sv_all.get(k, 0) + v
+        assert sv_all == {"voxel.general.slab": 2}, sv_all
+        return np.concatenate(parts, 0), None, sv_all
+    if chain in ("sticks", "general"):
+        sticks_mode(1 if chain == "sticks" else 0)
+    h, sv = served(lambda: hip_voxel(c, n, s, ctr, gpu, **inputs))
+    want = {"small": "voxel.small_grid", "sticks": "voxel.stick_first", "general": "voxel.general.switched_off"}[chain]
+    assert sv == {want: 1}, (chain, sv)
+    return h["vol"], h, sv
+
+
 def check_binning(h, o):
     """Bit-exact comparison of the binning pipeline with the oracle.  The HIP path sorts the Gaussians by depth
     first and emits instances in that order (then sorts by tile only), so its UNSORTED arrays are a per-Gaussian
@@ -354,7 +402,7 @@ def parity_raster_grads(O, o, gh, c, v, dL, label="", cov3D_precomp=None, scale_
                                                                      vm, pm, v.tanfovx, v.tanfovy))
 
 
-def parity_voxel_grads(O, o, gh, c, dL, label="", scale_modifier=1.0):
+def parity_voxel_grads(O, o, gh, c, dL, label="", scale_modifier=1.0, cov3D_precomp=None):
     from oracle import parity as Pz
-    return _log("voxel_grads", label, lambda: Pz.voxel_grad_parity(O, o, dL, gh, c.scales.numpy(), c.rotations.numpy(),
-                                                                   scale_modifier, None))
+    sc, q = (c.scales.numpy(), c.rotations.numpy()) if cov3D_precomp is None else (None, None)
+    return _log("voxel_grads", label, lambda: Pz.voxel_grad_parity(O, o, dL, gh, sc, q, scale_modifier, cov3D_precomp))

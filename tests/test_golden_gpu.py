@@ -71,16 +71,17 @@ def test_voxel_vs_reference_golden(path, gpu, oracle):
     nV = tuple(int(v) for v in z["in_nVoxel"])
     sV, ctr = tuple(float(v) for v in z["in_sVoxel"]), tuple(float(v) for v in z["in_center"])
     mod = float(z["in_params"][0])
+    cov = z["in_cov3D_precomp"] if "in_cov3D_precomp" in z.files else None
     c = _cloud(z)
-    h = Hh.hip_voxel(c, nV, sV, ctr, gpu, debug=True, scale_modifier=mod)
+    h = Hh.hip_voxel(c, nV, sV, ctr, gpu, debug=True, scale_modifier=mod, cov3D_precomp=cov)
     assert h["num_rendered"] == int(z["num_rendered"])
     for k in ("radii_x", "radii_y", "radii_z", "tiles_touched", "keys", "point_list", "ranges"):
         assert np.array_equal(h[k], z["fw_" + k]), k
-    o = Hh.oracle_voxel(oracle, c, nV, sV, ctr, scale_modifier=mod)
+    o = Hh.oracle_voxel(oracle, c, nV, sV, ctr, scale_modifier=mod, cov3D_precomp=cov)
     assert np.array_equal(o["vol"].view(np.uint32), z["fw_vol"].view(np.uint32))
     name = os.path.basename(path)[:-4]
     Hh.parity_volume(oracle, o, h["vol"], "golden " + name)
     g = Hh.hip_voxel_backward(h, c, nV, sV, ctr, z["in_dL_dvol"], gpu)
-    st = Hh.parity_voxel_grads(oracle, o, g, c, z["in_dL_dvol"], "golden " + name, scale_modifier=mod)
+    st = Hh.parity_voxel_grads(oracle, o, g, c, z["in_dL_dvol"], "golden " + name, scale_modifier=mod, cov3D_precomp=cov)
     for k in ("dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dscales", "dL_drotations"):
-        _grad_close(k, g[k], z["bw_" + k], st["_flagged"])
+        _grad_close(k, g[k], z["bw_" + k], st["_flagged"])   # under a precomputed covariance the last two are zero in the fixture

@@ -65,6 +65,75 @@ def test_voxel(P, n, sv, ctr, oracle):
         assert float(np.abs(go[k] - gr[k]).max()) <= 2e-5 * scale, k
 
 
+# The two optional inputs of the reference's ABI: a scale_modifier other than 1 and a precomputed covariance (`precomp`: built from
+# scales and rotations of ANOTHER cloud at the modifier of the call, so nothing can be recovered from the `scales` that are passed).
+OPTIONAL = [(0.7, False), (1.6, False), (1.3, True)]
+OPTIONAL_IDS = ["mod07", "mod16", "precomp"]
+
+
+def _decoupled_cov(oracle, P, seed, mod, **kw):
+    other = S.make_cloud(P, seed=seed + 1000, **kw)
+    return oracle.cov3d(other.scales.numpy(), mod, other.rotations.numpy())
+
+
+@pytest.mark.parametrize("mod,precomp", OPTIONAL, ids=OPTIONAL_IDS)
+def test_raster_optional_inputs(mod, precomp, oracle):
+    P, H, W, seed = 3000, 50, 70, 7
+    c = S.make_cloud(P, seed=seed, scale_mult=1.5)
+    v = S.make_view(2.1, (H, W))
+    xyz, rho, sc, q = Hh.cloud_np(c)
+    vm, pm = Hh.np_view(v)
+    cov = None
+    if precomp:   # the rasterizer reads neither scales nor rotations then
+        cov, sc, q = _decoupled_cov(oracle, P, seed, mod, scale_mult=1.5), None, None
+    r = ref.raster_forward(xyz, rho, sc, q, mod, cov, vm, pm, v.tanfovx, v.tanfovy, H, W, v.mode)
+    o = oracle.raster_forward(xyz, rho, sc, q, mod, cov, vm, pm, v.tanfovx, v.tanfovy, H, W, v.mode)
+    assert o["num_rendered"] == r["num_rendered"] > 0
+    for k in FW_RASTER:
+        assert _same(o[k], r[k]), k
+    dL = S.make_pixel_grad(H, W).numpy()
+    gr = ref.raster_backward(r, xyz, sc, q, mod, cov, vm, pm, v.tanfovx, v.tanfovy, dL)
+    go = oracle.raster_backward(o, xyz, sc, q, mod, cov, vm, pm, v.tanfovx, v.tanfovy, dL, acc64=False)
+    for k in gr:
+        scale = max(float(np.abs(gr[k]).max()), 1e-30)
+        assert float(np.abs(go[k] - gr[k]).max()) <= 2e-5 * scale, k
+    if precomp:
+        for k in ("dL_dscales", "dL_drotations"):
+            assert not gr[k].any() and not go[k].any(), k
+        assert np.abs(gr["dL_dcov3D"]).max() > 0
+
+
+@pytest.mark.parametrize("mod,precomp", OPTIONAL, ids=OPTIONAL_IDS)
+def test_voxel_optional_inputs(mod, precomp, oracle):
+    """The voxelizer takes its radii from the RAW scales whatever the modifier and whether or not a covariance is given (quirk
+    Q5), so under `precomp` the scales still go to the forward; the rotations do not, and neither backward gets the scales."""
+    P, n, sv, ctr, seed = 300, (20, 16, 24), (2.0, 1.6, 2.4), (0.0, 0.0, 0.0), 7
+    c = S.make_cloud(P, seed=seed, scale_mult=2.0)
+    xyz, rho, sc, q = Hh.cloud_np(c)
+    cov, sc_bw, q_bw = None, sc, q
+    if precomp:
+        cov, q, sc_bw, q_bw = _decoupled_cov(oracle, P, seed, mod, scale_mult=2.0), None, None, None
+    r = ref.voxel_forward(xyz, rho, sc, q, mod, cov, n, sv, ctr)
+    o = oracle.voxel_forward(xyz, rho, sc, q, mod, cov, n, sv, ctr)
+    assert o["num_rendered"] == r["num_rendered"] > 0
+    for k in FW_VOXEL:
+        assert _same(o[k], r[k]), k
+    base = oracle.voxel_forward(xyz, rho, sc, c.rotations.numpy(), 1.0, None, n, sv, ctr, render=False)
+    for k in ("radii_x", "radii_y", "radii_z"):   # Q5
+        assert np.array_equal(r[k], base[k]), k
+    rng = np.random.default_rng(1)
+    dL = ((rng.random(n, dtype=np.float32) * 2 - 1) / np.prod(n)).astype(np.float32)
+    gr = ref.voxel_backward(r, xyz, sc_bw, q_bw, mod, cov, dL)
+    go = oracle.voxel_backward(o, sc_bw, q_bw, mod, cov, dL, acc64=False)
+    for k in gr:
+        scale = max(float(np.abs(gr[k]).max()), 1e-30)
+        assert float(np.abs(go[k] - gr[k]).max()) <= 2e-5 * scale, k
+    if precomp:
+        for k in ("dL_dscales", "dL_drotations"):
+            assert not gr[k].any() and not go[k].any(), k
+        assert np.abs(gr["dL_dcov3D"]).max() > 0
+
+
 def test_empty_and_culled(oracle):
     v = S.make_view(0.4, (32, 32))
     vm, pm = Hh.np_view(v)

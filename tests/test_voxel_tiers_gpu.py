@@ -34,18 +34,7 @@ ARBITER_KEYS = {"tier": ("dL_dcov3D",), "subvoxel": ("dL_dcov3D", "dL_drotations
                 "faces": ("dL_dcov3D", "dL_dscales", "dL_drotations")}
 
 
-def _lib():
-    from r2_gaussian_amd import _lib as L
-    return L
-
-
-def _served(fn):
-    """Run fn(); -> (its result, {path counter: increment})."""
-    L = _lib()
-    before = L.path_stats()
-    out = fn()
-    after = L.path_stats()
-    return out, {k: after[k] - before.get(k, 0) for k in after if after[k] != before.get(k, 0)}
+_served = Hh.served
 
 
 def _dL(n, seed):
@@ -162,33 +151,8 @@ def _assert_coverage(name, sc, n, s, d, ref):
 sticks_mode = pytest.fixture(Hh.sticks_mode)
 
 
-def _chains(n):
-    g = [(k + 7) // 8 for k in n]
-    if g[0] * g[1] * g[2] <= 64 and max(g) <= 8:
-        return ["small", "general-slab"]
-    return ["sticks", "general"]
-
-
-def _run_chain(chain, c, n, s, ctr, gpu, sticks_mode):
-    """-> (volume, forward state of a full call or None, path counter increments)."""
-    if chain == "general-slab":
-        gx = (n[0] + 7) // 8
-        assert gx >= 2
-        cut = gx // 2
-        parts, served = [], {}
-        for t0, t1 in ((0, cut), (cut, gx)):
-            h, sv = _served(lambda: Hh.hip_voxel(c, n, s, ctr, gpu, slab=(t0, t1)))
-            parts.append(h["vol"])
-            for k, v in sv.items():
-                served[k] = served.get(k, 0) + v
-        assert served == {"voxel.general.slab": 2}, served
-        return np.concatenate(parts, 0), None, served
-    if chain in ("sticks", "general"):
-        sticks_mode(1 if chain == "sticks" else 0)
-    h, served = _served(lambda: Hh.hip_voxel(c, n, s, ctr, gpu))
-    want = {"small": "voxel.small_grid", "sticks": "voxel.stick_first", "general": "voxel.general.switched_off"}[chain]
-    assert served == {want: 1}, (chain, served)
-    return h["vol"], h, served
+_chains = Hh.voxel_chains
+_run_chain = Hh.run_voxel_chain
 
 
 @pytest.mark.parametrize("name", list(VS.SCENES))
