@@ -1091,6 +1091,48 @@ R2_API size_t r2_tv_prox_scratch_bytes(int nx, int ny, int nz);
 R2_API int r2_tv_prox(int nx, int ny, int nz, const float *y, float *x, const float *lambda /* device scalar */, int n_iter,
                       float lo, float hi, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- isosurface extraction (csrc/isosurface.hip, r2_gaussian_amd/mesh.py) -------------------------------------------------
+ * The level set {vol = level} of vol[nx][ny][nz] (z fastest; lattice point (i,j,k) has the linear index (i ny + j) nz + k) as an
+ * indexed triangle mesh, by marching tetrahedra on the Kuhn (Freudenthal) subdivision: every cell of the lattice is cut into
+ * the six tetrahedra 000 -> +e_a -> +e_a+e_b -> 111, one per permutation (a, b, c) of the axes.  All six share the body
+ * diagonal and the face diagonals of neighbouring cells agree, so the surface is watertight and there is no ambiguous case.
+ *   inside    a point is inside iff vol >= level (float32 compare).
+ *   invalid   a value that is NaN, +-inf or above 1e38 in magnitude (!(|v| <= 1e38f)); invalid values are counted, compare as
+ *             any float does (a NaN is outside), and the caller decides (mesh.py raises).  Without them fb - fa is finite.
+ *   edges     every edge of every tetrahedron runs from a lattice point p to p + d, d in {0,1}^3 \ {0}, both in the lattice;
+ *             its direction code is c = dx + 2 dy + 4 dz in 1..7, p OWNS it, and it is CROSSED iff exactly one end is inside.
+ *   vertices  one per crossed edge, ordered by (owner's linear index, direction code) ascending.  With fa the owner's value,
+ *             fb the other end's, every operation a separately rounded IEEE float32 one (no FMA, division correctly rounded):
+ *                 t = (level - fa) / (fb - fa);   index-space coordinate  p_x = float(i) + t dx  (float(i) where dx = 0),
+ *                 likewise y, z;   world coordinate  o_a + p_a * s_a  (a multiply, then an add).
+ *   normals   (optional) the lattice gradient at a point is (f(q + e_a) - f(q - e_a)) / (2 * s_a), and the one-sided difference
+ *             / s_a on a border; the edge gradient is g = ga + t * (gb - ga) (a subtraction, a multiply, an add), n =
+ *             sqrt((gx * gx + gy * gy) + gz * gz), and the normal is (-g_a) / n, one division per component; (0, 0, 0) unless
+ *             n > 0.  It points from inside to outside.
+ *   faces     int32 triples of vertex ids.  Seen from the outside (the low side) the vertices run counter-clockwise: the
+ *             geometric normal points from inside to outside.  A tetrahedron with one or three inside corners gives one
+ *             triangle, with two a quad split along a fixed diagonal.  Degenerate triangles (a corner value equal to level)
+ *             are kept, so that the surface stays closed.  Order: cells by their 000 corner's linear index, in a cell the
+ *             tetrahedra by permutation (xyz, xzy, yxz, yzx, zxy, zyx); that order and the first vertex of a face are fixed.
+ * A lattice with a dimension of 1 has no cells: no vertices and no faces (invalid values are still counted).
+ * r2_isosurface_count reads the volume once, leaves in `ws` (r2_isosurface_workspace_bytes(nx, ny, nz): about six bytes per
+ * lattice point, 128-byte aligned, prior contents never matter) every point's mask of crossed owned edges, its cell's triangle
+ * count and its first vertex id, and writes counts[0..2] = vertices, triangles, invalid values (device long long [3]).  The
+ * caller reads them -- the one host read of the operation -- allocates, and calls r2_isosurface_fill with the same volume,
+ * level and workspace (const there: as count left it) and with the world frame o, s (host floats, s_a != 0).  fill writes
+ * verts [n_verts,3], normals [n_verts,3] (NULL to skip) and faces [n_tris,3]; it never writes at or beyond row n_verts or
+ * n_tris and never reads outside the volume or the workspace, whatever the workspace holds.  No atomics, no allocation, no
+ * host synchronisation; two calls give identical bits.
+ * R2_ERR_INVALID, nothing written: a dimension below 1, nx ny nz >= 2^31, n_verts or n_tris outside [0, 2^31), a NULL volume,
+ * counts, workspace, or verts / faces that a non-zero count needs, too small a workspace. */
+R2_API size_t r2_isosurface_workspace_bytes(int nx, int ny, int nz);
+R2_API int r2_isosurface_count(int nx, int ny, int nz, const float *vol, float level, void *ws, size_t ws_bytes,
+                               long long *counts /* device [3]: vertices, triangles, invalid voxels */, void *stream);
+R2_API int r2_isosurface_fill(int nx, int ny, int nz, const float *vol, float level, float ox, float oy, float oz, float sx,
+                              float sy, float sz, const void *ws /* as count left it */, size_t ws_bytes, long long n_verts,
+                              long long n_tris, float *verts /* [n_verts,3] */, float *normals /* [n_verts,3] or NULL */,
+                              int *faces /* [n_tris,3] */, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

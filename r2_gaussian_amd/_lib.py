@@ -141,6 +141,10 @@ _SIGNATURES = {
     "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
     "r2_tv_prox_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
     "r2_tv_prox": (C.c_int, [_i, _i, _i, _fp, _fp, _fp, _i, _f, _f, _p, C.c_size_t, _p]),
+    "r2_isosurface_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "r2_isosurface_count": (C.c_int, [_i, _i, _i, _fp, _f, _p, C.c_size_t, _p, _p]),
+    "r2_isosurface_fill": (C.c_int, [_i, _i, _i, _fp, _f, _f, _f, _f, _f, _f, _f, _p, C.c_size_t, C.c_longlong, C.c_longlong,
+                                     _fp, _fp, _p, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_gaussian_adam_step": (C.c_int, [_i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),

@@ -81,6 +81,8 @@ SOURCES = {
     "tv_descent.hip": FAST,
     # EXACT: the per-voxel operation order is the one include/r2hip.h states and tests/tv_prox_ref.py follows bit for bit
     "tv_prox.hip": EXACT,
+    # EXACT: the per-vertex operation order is the one include/r2hip.h states and tests/isosurface_ref.py follows bit for bit
+    "isosurface.hip": EXACT,
     "dispatch.hip": FAST,
     "host_runtime.hip": FAST,
 }
