@@ -1133,6 +1133,59 @@ R2_API int r2_isosurface_fill(int nx, int ny, int nz, const float *vol, float le
                               long long n_tris, float *verts /* [n_verts,3] */, float *normals /* [n_verts,3] or NULL */,
                               int *faces /* [n_tris,3] */, void *stream);
 
+/* ---- cubic-spline resampling of volumes (csrc/spline.hip, r2_gaussian_amd/resample.py) -------------------------------------
+ * scipy.ndimage's zoom and map_coordinates for order = 3, mode = "nearest", prefilter = True, grid_mode = False, on
+ * vol[nx][ny][nz] (z fastest): a prefilter that turns the samples into the coefficients of the interpolating cubic B-spline,
+ * and two evaluators of that spline.  Every float32 operation below is a separately rounded IEEE one (no FMA, division correctly
+ * rounded) in the order written, which tests/resample_ref.py follows operation for operation.
+ *
+ * r2_spline_prefilter: coeffs[nx+24][ny+24][nz+24] from vol.  The input is edge-padded by R2_SPLINE_PAD = 12 on every side,
+ *     c(i,j,k) = vol(clamp(i-12, 0, nx-1), clamp(j-12, 0, ny-1), clamp(k-12, 0, nz-1)),
+ * (read through clamped indices by the first pass: no padded copy exists), and every line of the padded block is filtered
+ * along x, then along y, then along z.  With the pole z = sqrt(3) - 2 and, computed in double and rounded to float32 once each,
+ *     Z = z,   G = (1 - z)(1 - 1/z) (= 6),   A = z / (z - 1),   ZP_i = z^i  (i = 1 .. R2_SPLINE_HORIZON),
+ * a line c[0 .. n-1] (n >= 25) becomes
+ *     g_i = G * c_i                                                  (every i; each pass applies the gain to its own input)
+ *     s = g_0;   s = s + ZP_i * g_i  for i = 1 .. R2_SPLINE_HORIZON;   c_0 = g_0 + Z * s              (causal start)
+ *     c_i = g_i + Z * c_{i-1}                                        for i = 1 .. n-1
+ *     c_{n-1} = c_{n-1} * A                                                                           (anti-causal start)
+ *     c_i = Z * (c_{i+1} - c_i)                                      for i = n-2 .. 0.
+ * The two starts are those of a half-sample-symmetric extension of the line (what scipy's spline filter uses for "nearest":
+ * c_0 += z sum_{i=0}^{n-1} z^i (c_i + z^n c_{n-1-i}) / (1 - z^{2n})), with the start sum cut off after R2_SPLINE_HORIZON = 16
+ * terms and the z^n terms dropped: z^17 < 2^-32 and z^n <= z^25 < 2^-47 lie below the float32 rounding of the sum, and no power
+ * of the pole becomes denormal.  r2_spline_prefilter_pass runs one pass: axis 0 pads and filters along x (reads vol, writes all
+ * of coeffs), axes 1 and 2 filter coeffs in place (vol is not read); r2_spline_prefilter is passes 0, 1, 2.
+ * coeffs may not overlap vol.
+ *
+ * r2_spline_zoom: out[mx][my][mz] from the coefficients, scipy's zoom onto a grid whose first and last nodes are the input's.
+ * A first launch writes one table per axis into ws (r2_spline_zoom_workspace_bytes(mx, my, mz), 4-byte aligned, prior contents
+ * never matter), in double: for output index o of an axis with n inputs and m outputs
+ *     cc = o * ((n-1) / (m-1)) + 12   (the factor is 1 when m = 1),   start = floor(cc) - 1,   t = cc - floor(cc),
+ *     w1 = (t*t*(t-2)*3 + 4) / 6;   u = 1 - t;   w2 = (u*u*(u-2)*3 + 4) / 6;   w0 = u*u*u / 6;   w3 = 1 - w0 - w1 - w2,
+ * each product and sum left to right, each weight then rounded to float32 once.  Then, in float32,
+ *     out(a,b,c) = sum_i wx_i ( sum_j wy_j ( sum_k wz_k * coeffs(sx+i, sy+j, sz+k) ) ),   i, j, k = 0 .. 3,
+ * every sum from its first term to its last.  All taps lie inside the padded block.
+ *
+ * r2_spline_sample: out[N] at points[N][3], float32 index coordinates of the unpadded volume: scipy's map_coordinates.  Per
+ * axis, in float32: cc = p + 12, clamped to [-1, n + 24] (one beyond the padded block on either side, as scipy does);
+ * start = floor(cc) - 1, t = cc - floor(cc), the weights from t by the formulas above in float32, the tap indices
+ * start .. start+3 clamped to the padded block [0, n + 23], and the nesting above.  A point with a NaN or infinite coordinate
+ * gives NaN and reads nothing.  N = 0 is a no-op.
+ *
+ * No allocation, no atomics, no host synchronisation; two calls give identical bits.
+ * R2_ERR_INVALID, nothing written: a dimension or an output dimension below 1, (nx+24)(ny+24)(nz+24) >= 2^31, mx my mz >= 2^31,
+ * N < 0, an axis outside 0 .. 2, a NULL pointer that the call would use, too small a workspace. */
+#define R2_SPLINE_PAD 12
+#define R2_SPLINE_HORIZON 16
+R2_API int r2_spline_prefilter(int nx, int ny, int nz, const float *vol, float *coeffs /* [nx+24][ny+24][nz+24] */, void *stream);
+R2_API int r2_spline_prefilter_pass(int nx, int ny, int nz, const float *vol /* axis 0 only */, float *coeffs, int axis,
+                                    void *stream);
+R2_API size_t r2_spline_zoom_workspace_bytes(int mx, int my, int mz);
+R2_API int r2_spline_zoom(int nx, int ny, int nz, const float *coeffs, int mx, int my, int mz, float *out /* [mx][my][mz] */,
+                          void *ws, size_t ws_bytes, void *stream);
+R2_API int r2_spline_sample(int nx, int ny, int nz, const float *coeffs, int N, const float *points /* [N,3] */,
+                            float *out /* [N] */, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

@@ -25,6 +25,8 @@ R2_GRAPH_LOSS_HUB = 64     # incoming lists longer than this are summed by a who
 R2_MERGE_HUB = 64          # ... and walked by a whole wave in r2_graph_match / r2_merge_count
 R2_MERGE_JACOBI_SWEEPS = 8
 R2_RELOCATE_SCAN_TILE = 4096   # elements per workgroup of r2_relocate_plan's 64-bit scan
+R2_SPLINE_PAD = 12             # edge padding of r2_spline_prefilter's coefficient block, per side
+R2_SPLINE_HORIZON = 16         # terms of its start sum
 
 _f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
 
@@ -145,6 +147,11 @@ _SIGNATURES = {
     "r2_isosurface_count": (C.c_int, [_i, _i, _i, _fp, _f, _p, C.c_size_t, _p, _p]),
     "r2_isosurface_fill": (C.c_int, [_i, _i, _i, _fp, _f, _f, _f, _f, _f, _f, _f, _p, C.c_size_t, C.c_longlong, C.c_longlong,
                                      _fp, _fp, _p, _p]),
+    "r2_spline_prefilter": (C.c_int, [_i, _i, _i, _fp, _fp, _p]),
+    "r2_spline_prefilter_pass": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p]),
+    "r2_spline_zoom_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
+    "r2_spline_zoom": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _fp, _p, C.c_size_t, _p]),
+    "r2_spline_sample": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _fp, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_gaussian_adam_step": (C.c_int, [_i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),

@@ -83,6 +83,8 @@ SOURCES = {
     "tv_prox.hip": EXACT,
     # EXACT: the per-vertex operation order is the one include/r2hip.h states and tests/isosurface_ref.py follows bit for bit
     "isosurface.hip": EXACT,
+    # EXACT: the per-sample operation order is the one include/r2hip.h states and tests/resample_ref.py follows bit for bit
+    "spline.hip": EXACT,
     "dispatch.hip": FAST,
     "host_runtime.hip": FAST,
 }
