@@ -1186,6 +1186,51 @@ R2_API int r2_spline_zoom(int nx, int ny, int nz, const float *coeffs, int mx, i
 R2_API int r2_spline_sample(int nx, int ny, int nz, const float *coeffs, int N, const float *points /* [N,3] */,
                             float *out /* [N] */, void *stream);
 
+/* ---- conditioning of measured projections (csrc/projections.hip, r2_gaussian_amd/projections.py) -----------------------------
+ * What a measured projection stack src[V][H][W] (float32, W fastest) needs before it can be trained on: the resize of the
+ * reference's real-data converter (cv2.resize with its row shift, clamp and crop) and a median filter against isolated
+ * outliers.  Every float32 operation below is a separately rounded IEEE one (no FMA) in the order written, which
+ * tests/projections_ref.py follows operation for operation.
+ *
+ * r2_proj_resize: dst[V][oh][ow] from src, per view: shift, lower clamp, resize to mh x mw, crop -- fused, so that only the
+ * cropped outputs are computed and src is read once.
+ *   Prepared pixel.  P(r, c) = x < lo ? lo : x  with  x = src(r + sr, c + sc)  where 0 <= r + sr < H and 0 <= c + sc < W, else
+ *     P(r, c) = 0 (not lo).  lo = -inf switches the clamp off; a NaN stays a NaN.  sr = 5, lo = 0 is the reference's
+ *     proj[proj < 0] = 0; proj_new[:-5] = proj[5:].
+ *   Output pixel (i, j), 0 <= i < oh, 0 <= j < ow, is pixel (r0 + i, c0 + j) of the mh x mw resized image.
+ *   interp = 0, cv2's INTER_LINEAR for float images.  A first launch writes one table per axis into ws
+ *     (r2_proj_resize_workspace_bytes(mh, mw), 4-byte aligned, prior contents never matter; rows use n = H, m = mh, columns
+ *     n = W, m = mw).  In double:  inv = (double)m / n,  scale = 1.0 / inv;  for output index d of the axis
+ *         fx = (float)((d + 0.5) * scale - 0.5),   s = floor(fx),   f = fx - s  (float32);
+ *         s < 0 gives s = 0, f = 0;   s >= n - 1 gives s = n - 1, f = 0;   the taps are s and min(s + 1, n - 1).
+ *     Then, in float32, with rows r_0, r_1 and weights b0 = 1.f - f_row, b1 = f_row, columns c_0, c_1 and weights
+ *     a0 = 1.f - f_col, a1 = f_col:
+ *         h_i = P(r_i, c_0) * a0 + P(r_i, c_1) * a1   (i = 0, 1),       out = h_0 * b0 + h_1 * b1.
+ *   interp = 1, box mean; only for H % mh == 0 and W % mw == 0 (fy = H / mh, fx = W / mw; the choice for integer down-sampling
+ *     of noisy data).  Resized pixel (y, x):
+ *         acc = P(y fy, x fx);   acc = acc + P(y fy + i, x fx + j)  for the remaining (i, j) of the block, row after row, each
+ *         row from its first column to its last (i outer, j inner);   out = acc * (float)(1.0 / (fy fx)).
+ *     ws is not used and may be NULL.
+ *
+ * r2_proj_median: dst[V][H][W] from src (dst may not overlap src), per view the median filter of the k x k window, k in {3, 5},
+ * with replicated borders: scipy.ndimage.median_filter(size=k, mode="nearest").
+ *     m(r, c) = the element of rank k k / 2 (counted from 0, ascending) of the k k values src(clamp(r + i, 0, H - 1),
+ *     clamp(c + j, 0, W - 1)), |i|, |j| <= k / 2, a NaN among them read as +inf.
+ *     replace(r, c) = !(|x - m| <= threshold)  with x = src(r, c) as it is and the difference in float32: true for a NaN x.
+ *     conditional = 0: dst = m.   conditional = 1: dst = replace ? m : x.   flagged[V][H][W] (uint8, may be NULL) = replace,
+ *     in either mode.  Where a window holds both -0 and +0 at the rank, which of them comes back is unspecified.
+ *
+ * No allocation, no atomics, no host synchronisation; two calls give identical bits.  V = 0 is a no-op.
+ * R2_ERR_INVALID, nothing launched: V < 0; a dimension below 1; H W, mh mw >= 2^31; V H W or V oh ow >= 2^38; a crop window that
+ * is empty or leaves the resized image; |sr| or |sc| above 2^30; a NaN lo; interp outside {0, 1}; interp = 1 with a factor that
+ * is not an integer; k outside {3, 5}; conditional outside {0, 1}; a NaN threshold; 2^31 or more tiles of 64 x 16 pixels for the
+ * median; a NULL pointer that the call would use; too small a workspace. */
+R2_API size_t r2_proj_resize_workspace_bytes(int mh, int mw);
+R2_API int r2_proj_resize(int V, int H, int W, const float *src, int sr, int sc, float lo, int interp, int mh, int mw, int r0,
+                          int c0, int oh, int ow, float *dst /* [V][oh][ow] */, void *ws, size_t ws_bytes, void *stream);
+R2_API int r2_proj_median(int V, int H, int W, const float *src, int k, int conditional, float threshold,
+                          float *dst /* [V][H][W] */, unsigned char *flagged /* [V][H][W] or NULL */, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

@@ -85,6 +85,8 @@ SOURCES = {
     "isosurface.hip": EXACT,
     # EXACT: the per-sample operation order is the one include/r2hip.h states and tests/resample_ref.py follows bit for bit
     "spline.hip": EXACT,
+    # EXACT: the per-pixel operation order is the one include/r2hip.h states and tests/projections_ref.py follows bit for bit
+    "projections.hip": EXACT,
     "dispatch.hip": FAST,
     "host_runtime.hip": FAST,
 }
