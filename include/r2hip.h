@@ -1231,6 +1231,54 @@ R2_API int r2_proj_resize(int V, int H, int W, const float *src, int sr, int sc,
 R2_API int r2_proj_median(int V, int H, int W, const float *src, int k, int conditional, float threshold,
                           float *dst /* [V][H][W] */, unsigned char *flagged /* [V][H][W] or NULL */, void *stream);
 
+/* ---- stripe (ring-artefact) removal along the view axis (csrc/destripe.hip, r2_gaussian_amd/projections.py) -------------------
+ * A detector pixel whose gain or offset is slightly wrong adds the same constant to src(v, h, w) in every view v: invisible in
+ * one projection, a ring in the reconstruction.  Both entries compare, for a fixed detector row h, neighbouring detector
+ * columns w across all V views of src[V][H][W] (float32, W fastest).  They consist of comparisons, selections and the float32
+ * and double operations written out below, each separately rounded (no FMA), in the order written: tests/destripe_ref.py
+ * restates them in NumPy / SciPy and the results agree bit for bit.  k is the odd width of the window across the columns,
+ * 1 <= k <= 31; clamp(x) below is min(max(x, 0), W - 1) (the replicated border), and "the median" of k values is their element
+ * of rank k / 2, counted from 0 in ascending order.
+ *
+ * r2_proj_destripe_sort: dst[V][H][W] from src -- Vo, Atwood and Drakopoulos (2018), algorithm 3.  For every (h, w):
+ *     c_v = src(v, h, w), v = 0 .. V-1, a NaN read as +inf (and -0 as +0).
+ *     The column is ordered ascending; equal values are ordered by their view index (a stable sort: a clamped projection has
+ *     long runs of exact zeros, and which of those views gets which rank changes the result).  S(r, h, w) is the value of rank
+ *     r and I(r, h, w) the view it came from.
+ *     M(r, h, w) = the median of the k values S(r, h, clamp(w + j)), |j| <= k / 2:
+ *     scipy.ndimage.median_filter(S, size=(1, 1, k), mode="nearest").
+ *     dst(I(r, h, w), h, w) = M(r, h, w).
+ *   With k = 1 that is src itself (its NaNs as +inf), and it is written in one pass: nothing is sorted, ws is checked but not
+ *   used.  Which of -0 and +0 comes back where both tie is unspecified.  dst doubles as scratch space while the call runs (it holds the sorted sinogram [H][W][V] before it holds the result); ws needs
+ *   r2_proj_destripe_workspace_bytes(V, H, W, 0) = 6 V H W bytes, 4-byte aligned: the filtered sinogram [H][W][V] in float32
+ *   and I as uint16.  V <= R2_DESTRIPE_MAX_VIEWS = 4096: a column is sorted as 64-bit keys (the value's order-preserving bits
+ *   above the view index, so that the stable order is a plain integer order) in the LDS, padded to a power of two, and 4096
+ *   keys are 32 KiB -- five workgroups still share the 160 KiB of a compute unit, and one stays within the 64 KiB that a
+ *   workgroup may always have.
+ *
+ * r2_proj_destripe_mean: the classic normalisation by the mean profile.  For every (h, w):
+ *     acc = 0.0 (double);   acc = acc + (double)src(v, h, w)   for v = 0 .. V-1 in this order;   m(h, w) = (float)(acc / V).
+ *     s(h, w) = the median of the k values m(h, clamp(w + j)), |j| <= k / 2, a NaN among them read as +inf.
+ *     d(h, w) = m(h, w) - s(h, w)                  (float32).
+ *     dst(v, h, w) = src(v, h, w) - d(h, w)        (float32),   for every v.
+ *   offsets[H][W] = d when the pointer is not NULL: the detector's offsets, a diagnostic.  dst may be NULL when offsets is not:
+ *   then only the offsets are computed.  NaN inputs propagate: a pixel with a NaN in any view has a NaN m, hence a NaN d and a
+ *   NaN in every view of dst; its neighbours see it as +inf in their windows.  With k = 1, d = m - m (0 for a finite m) and dst
+ *   is src.  ws needs r2_proj_destripe_workspace_bytes(V, H, W, 1) = 8 H W bytes, 4-byte aligned (m and d).
+ *
+ * dst may not overlap src.  A workspace's prior contents never matter.  No allocation, no atomics, no host synchronisation;
+ * two calls give identical bits.  V = 0 is a no-op (offsets is not written either).
+ * R2_ERR_INVALID, nothing launched: V < 0; a dimension below 1; H W >= 2^31; V H W >= 2^38; k even or outside 1 .. 31;
+ * V > R2_DESTRIPE_MAX_VIEWS for the sort; a NULL src, a NULL dst for the sort, dst and offsets both NULL for the mean, a NULL ws;
+ * too small a workspace.  r2_proj_destripe_workspace_bytes returns 0 for arguments that the entries refuse. */
+#define R2_DESTRIPE_MAX_VIEWS 4096
+R2_API int r2_proj_destripe_max_views(void);   /* R2_DESTRIPE_MAX_VIEWS of the library that is loaded */
+R2_API size_t r2_proj_destripe_workspace_bytes(int V, int H, int W, int method /* 0 sort, 1 mean */);
+R2_API int r2_proj_destripe_sort(int V, int H, int W, const float *src, int k, float *dst /* [V][H][W] */, void *ws,
+                                 size_t ws_bytes, void *stream);
+R2_API int r2_proj_destripe_mean(int V, int H, int W, const float *src, int k, float *dst /* [V][H][W] or NULL */,
+                                 float *offsets /* [H][W] or NULL */, void *ws, size_t ws_bytes, void *stream);
+
 /* The forward passes order the Gaussians by depth with a bucket sort whose bucket boundaries follow the depth range seen
  * by the previous call with the same P (a per-thread hint: it saves five kernel launches and hides the num_rendered
  * read-back).  Results never depend on it -- both paths produce the exact (depth, id) order.  mode 0: never use hints,

@@ -155,6 +155,10 @@ _SIGNATURES = {
     "r2_proj_resize_workspace_bytes": (C.c_size_t, [_i, _i]),
     "r2_proj_resize": (C.c_int, [_i, _i, _i, _fp, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _fp, _p, C.c_size_t, _p]),
     "r2_proj_median": (C.c_int, [_i, _i, _i, _fp, _i, _i, _f, _fp, _p, _p]),
+    "r2_proj_destripe_max_views": (C.c_int, []),
+    "r2_proj_destripe_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
+    "r2_proj_destripe_sort": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _p, C.c_size_t, _p]),
+    "r2_proj_destripe_mean": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _fp, _p, C.c_size_t, _p]),
     "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_gaussian_adam_step": (C.c_int, [_i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
     "r2_profile_enable": (None, [C.c_ulonglong]),

@@ -87,6 +87,8 @@ SOURCES = {
     "spline.hip": EXACT,
     # EXACT: the per-pixel operation order is the one include/r2hip.h states and tests/projections_ref.py follows bit for bit
     "projections.hip": EXACT,
+    # EXACT: the mean method's operations are the ones include/r2hip.h states and tests/destripe_ref.py follows bit for bit
+    "destripe.hip": EXACT,
     "dispatch.hip": FAST,
     "host_runtime.hip": FAST,
 }

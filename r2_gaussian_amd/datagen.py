@@ -3,6 +3,7 @@ projector of projector.py.
 
     python -m r2_gaussian_amd.datagen --vol vol.npy --scanner cone_beam.yml --output data/case_dir [--n_train 50]
                                       [--n_test 100] [--seed 0] [--projection_type interpolated|siddon]
+                                      [--stripes N AMPLITUDE]
 
 writes ``{output}/{vol_name}_{mode}/`` with ``vol_gt.npy``, ``proj_train/proj_train_%04d.npy``,
 ``proj_test/proj_test_%04d.npy`` (float32 [H, W], the rasterizer's row order) and ``meta_data.json`` (keys scanner, vol,
@@ -65,10 +66,31 @@ def angles_for(cfg, n_train, n_test, rng):
     return train, test
 
 
-def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles_test, weights_train=None):
+STRIPE_STREAM = 0x57121E5   # the second seed word of the stripes' own generator
+
+
+def stripe_field(nDetector, n, amplitude, seed):
+    """The static offsets of ``n`` miscalibrated detector columns for ``nDetector`` = (H, W) -> (columns, field): the sorted
+    list of the n distinct columns and the float32 [H, W] field that every view gains, N(0, amplitude) per (row, column) of
+    those columns and 0 elsewhere.  Deterministic in ``seed`` through a RandomState of its own: first the columns, then the
+    offsets in C order."""
+    H, W = int(nDetector[0]), int(nDetector[1])
+    if int(n) != n or not 0 <= int(n) <= W:
+        raise ValueError("stripes must be an integer number of columns in [0, %d], got %r" % (W, n))
+    if not float(amplitude) >= 0.0:
+        raise ValueError("the stripes' amplitude must be >= 0, got %r" % (amplitude,))
+    rng = np.random.RandomState([int(seed) % 2 ** 32, STRIPE_STREAM])
+    columns = np.sort(rng.choice(W, size=int(n), replace=False))
+    field = np.zeros((H, W), np.float32)
+    field[:, columns] = rng.normal(0.0, float(amplitude), size=(H, int(n))).astype(np.float32)
+    return [int(c) for c in columns], field
+
+
+def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles_test, weights_train=None, stripe_columns=None):
     """The on-disk layout of generate_data.py:70-100 for given projections [V, H, W]; -> the meta dictionary written.
     ``weights_train`` ([H, W], shared by the training views, or [V, H, W]; None: the case records none and is the
-    reference's layout): saved as ``weights_train.npy`` and recorded under the key ``weights_train``."""
+    reference's layout): saved as ``weights_train.npy`` and recorded under the key ``weights_train``.  ``stripe_columns``: None,
+    or the list of miscalibrated detector columns to record under the key ``stripe_columns``."""
     os.makedirs(case_dir, exist_ok=True)
     np.save(osp.join(case_dir, "vol_gt.npy"), np.asarray(vol, dtype=np.float32))
     entries = {}
@@ -87,6 +109,8 @@ def write_case(case_dir, cfg, vol, projs_train, angles_train, projs_test, angles
             raise ValueError("weights_train is %s but the training projections are %s" % (w.shape, np.shape(projs_train)))
         np.save(osp.join(case_dir, "weights_train.npy"), w)
         meta["weights_train"] = "weights_train.npy"
+    if stripe_columns is not None:
+        meta["stripe_columns"] = [int(c) for c in stripe_columns]
     with open(osp.join(case_dir, "meta_data.json"), "w", encoding="utf-8") as f:
         json.dump(meta, f, indent=4)
     return meta
@@ -97,13 +121,15 @@ def recorded_projection_type(cfg):
     return P.check_projection_type(cfg.get("projection_type", "interpolated"))
 
 
-def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda", projection_type=None, defects=None):
+def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device="cuda", projection_type=None, defects=None,
+             stripes=None):
     """Project ``vol`` [nx,ny,nz] with the raw scanner config ``cfg`` and write the case ``{output}/{vol_name}_{mode}``;
     -> the case directory.  ``projection_type``: "interpolated" or "siddon", written into the case's saved scanner config;
     None takes the config's own ``projection_type`` ("interpolated" if absent) and saves the config as it is.
     ``defects``: None, or the keyword arguments of ``weights.defect_mask`` (dead_pixels, dead_lines, gap) for one static
     detector mask, drawn after every other draw: the training projections are written with 0 in the masked pixels and the mask
-    as the case's ``weights_train``."""
+    as the case's ``weights_train``.  ``stripes``: None, or (n, amplitude) for ``stripe_field``: its field is added to every
+    training view (after the noise, before the mask) and every test view."""
     if projection_type is None:
         projection_type = recorded_projection_type(cfg)
     else:
@@ -115,12 +141,16 @@ def generate(vol, cfg, output, vol_name, n_train=50, n_test=100, seed=0, device=
     train = noisy_train(train, cfg, rng)
     test = P.project(vol, test_angles, cfg, device=device, projection_type=projection_type).cpu().numpy()
     case_dir = osp.join(output, "%s_%s" % (vol_name, cfg["mode"]))
+    columns = None
+    if stripes is not None:
+        columns, field = stripe_field(cfg["nDetector"], stripes[0], stripes[1], seed)
+        train, test = (train + field[None]).astype(np.float32), (test + field[None]).astype(np.float32)
     mask = None
     if defects:
         from .weights import defect_mask
         mask = defect_mask(cfg["nDetector"], rng, **defects)
         train = np.where(mask > 0, train, np.float32(0)).astype(np.float32)
-    write_case(case_dir, cfg, vol, train, train_angles, test, test_angles, weights_train=mask)
+    write_case(case_dir, cfg, vol, train, train_angles, test, test_angles, weights_train=mask, stripe_columns=columns)
     return case_dir
 
 
@@ -139,7 +169,15 @@ def main(argv=None):
     ap.add_argument("--dead_lines", default=0, type=int, help="Number of dead detector rows or columns.")
     ap.add_argument("--gap", default=None, type=int, nargs=2, metavar=("C0", "C1"),
                     help="A band of unmeasured detector columns C0 <= c < C1.")
+    ap.add_argument("--stripes", default=None, nargs=2, metavar=("N", "AMPLITUDE"),
+                    help="N miscalibrated detector columns with offsets drawn from N(0, AMPLITUDE), the same in every view.")
     args = ap.parse_args(argv)
+    stripes = None
+    if args.stripes is not None:
+        try:
+            stripes = (int(args.stripes[0]), float(args.stripes[1]))
+        except ValueError:
+            ap.error("--stripes takes an integer N and a number AMPLITUDE, got %r" % (args.stripes,))
     import yaml
     with open(args.scanner, "r") as f:
         cfg = yaml.safe_load(f)
@@ -149,7 +187,7 @@ def main(argv=None):
     if args.dead_pixels > 0 or args.dead_lines > 0 or args.gap is not None:
         defects = dict(dead_pixels=args.dead_pixels, dead_lines=args.dead_lines, gap=None if args.gap is None else tuple(args.gap))
     case_dir = generate(np.load(args.vol), cfg, args.output, vol_name, args.n_train, args.n_test, args.seed,
-                        projection_type=args.projection_type, defects=defects)
+                        projection_type=args.projection_type, defects=defects, stripes=stripes)
     print("Generate data for case %s complete!" % osp.basename(case_dir))
     return case_dir
 

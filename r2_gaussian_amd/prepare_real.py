@@ -4,13 +4,18 @@ TIGRE's place).
 
     python -m r2_gaussian_amd.prepare_real --data fips/pine --output data/real/pine [--proj_subsample 4]
                                            [--interpolation {linear,area}] [--despeckle THRESH [--despeckle_size K]]
+                                           [--destripe K [--destripe_method {sort,mean}]]
 
 ``--data`` holds the FIPS ``config.txt`` and one projection per file: ``*.mat`` with the variable ``img`` (read with
 ``scipy.io.loadmat``), or ``*.npy`` when there is no ``.mat``.  Per projection, in the reference's order:
 ``/ proj_rescale * object_scale`` and the float32 cast on the host; then on the device values below 0 become 0, the image moves
 up by five rows (the dataset's description; zeros come in below), and with ``--proj_subsample`` other than 1 it is resized to
 ``int(h / s) x int(w / s)`` and cropped to the reference's centred square.  ``--despeckle THRESH`` first replaces, at full
-resolution, every pixel further than THRESH from the median of its K x K window (and every NaN) by that median.  The
+resolution, every pixel further than THRESH from the median of its K x K window (and every NaN) by that median.
+``--destripe K`` removes the stripes of miscalibrated detector pixels, the rings of the reconstruction
+(``projections.destripe``, a median across K detector columns): that needs all views of a detector row at once, so it runs on
+the whole conditioned stack -- after the resize, through which a gain error survives as the mean over the merged pixels, and
+before anything is written -- in bands of detector rows where the stack is larger than the device.  The
 projections go to ``proj_all/``, the reference's choice of training and test views also to ``proj_train/`` and ``proj_test/``,
 ``vol_gt.npy`` is the FDK reconstruction of all of them clamped at 0 (kept when it exists), and ``meta_data.json`` holds the
 reference's scanner block.
@@ -123,6 +128,24 @@ def condition(projs, proj_subsample=4, interpolation="linear", despeckle=None, d
     return PJ.resize(projs, (mh, mw), interpolation, shift=(ROW_SHIFT, 0), lo=0.0, crop=crop_window(mh, mw))
 
 
+def destripe_rows(stack, size, method="sort", device="cuda", rows=None):
+    """``projections.destripe`` of a host stack [V,H,W] (float32) -> a new host stack.  Stripe removal needs all views of a
+    detector row at once but rows are independent, so the stack visits the device in bands of ``rows`` detector rows: by default
+    as many as fit in four fifths of the device's free memory (a band, its result and the sort method's workspace are 14 bytes
+    per value)."""
+    V, H, W = stack.shape
+    if rows is None:
+        free = torch.cuda.mem_get_info(torch.device(device))[0]
+        rows = int(free * 4 // 5 // max(14 * V * W, 1))
+        if rows < 1:
+            raise ValueError("one detector row of %d views x %d columns does not fit on the device" % (V, W))
+    out = np.empty(stack.shape, dtype=np.float32)
+    for h0 in range(0, H, rows):
+        band = torch.from_numpy(np.ascontiguousarray(stack[:, h0:h0 + rows], dtype=np.float32)).to(device)
+        out[:, h0:h0 + rows] = PJ.destripe(band, size, method).cpu().numpy()
+    return out
+
+
 def projection_paths(data):
     paths = sorted(glob.glob(osp.join(data, "*.mat")))
     return paths if paths else sorted(glob.glob(osp.join(data, "*.npy")))
@@ -143,22 +166,33 @@ def convert(args, device="cuda"):
         raise ValueError("no *.mat or *.npy projections in %s" % args.data)
     train_ids, test_ids = select_ids(cfg["n_proj"], args.n_train, args.n_test)
     projection_train_list, projection_test_list = [], []
+
+    def save(i_proj, path, image):
+        name = osp.basename(path).split(".")[0] + ".npy"
+        np.save(osp.join(all_save_path, name), image)
+        if i_proj in train_ids:
+            np.save(osp.join(train_save_path, name), image)
+            projection_train_list.append({"file_path": osp.join(osp.basename(train_save_path), name), "angle": float(angles[i_proj])})
+        elif i_proj in test_ids:
+            np.save(osp.join(test_save_path, name), image)
+            projection_test_list.append({"file_path": osp.join(osp.basename(test_save_path), name), "angle": float(angles[i_proj])})
+
+    conditioned = []   # with --destripe: the conditioned stack, which is written only once all of its views are known
     # a few projections at a time: a full-resolution stack is larger than the device
     for i0 in range(0, len(paths), args.batch):
         batch = paths[i0:i0 + args.batch]
         host = np.stack([load_projection(p, args.proj_rescale, args.object_scale) for p in batch])
         out = condition(torch.from_numpy(host).to(device), args.proj_subsample, args.interpolation, args.despeckle,
                         args.despeckle_size).cpu().numpy()
+        if args.destripe is not None:
+            conditioned.append(out)
+            continue
         for k, path in enumerate(batch):
-            i_proj = i0 + k
-            name = osp.basename(path).split(".")[0] + ".npy"
-            np.save(osp.join(all_save_path, name), out[k])
-            if i_proj in train_ids:
-                np.save(osp.join(train_save_path, name), out[k])
-                projection_train_list.append({"file_path": osp.join(osp.basename(train_save_path), name), "angle": float(angles[i_proj])})
-            elif i_proj in test_ids:
-                np.save(osp.join(test_save_path, name), out[k])
-                projection_test_list.append({"file_path": osp.join(osp.basename(test_save_path), name), "angle": float(angles[i_proj])})
+            save(i0 + k, path, out[k])
+    if args.destripe is not None:
+        stack = destripe_rows(np.concatenate(conditioned), args.destripe, args.destripe_method, device)
+        for i_proj, path in enumerate(paths):
+            save(i_proj, path, stack[i_proj])
     if not projection_train_list:
         raise ValueError("no training projection among the %d files of %s" % (len(paths), args.data))
 
@@ -228,6 +262,10 @@ def parser():
     ap.add_argument("--despeckle", default=None, type=float, metavar="THRESH",
                     help="Replace pixels further than THRESH from their window's median, at full resolution (off by default).")
     ap.add_argument("--despeckle_size", default=3, type=int, choices=(3, 5), help="Side of the despeckle window.")
+    ap.add_argument("--destripe", default=None, type=int, metavar="K",
+                    help="Remove stripes (rings) from the conditioned stack with a median of K detector columns (off by default).")
+    ap.add_argument("--destripe_method", default="sort", choices=sorted(PJ.DESTRIPE_METHODS),
+                    help="sort: sorting-based (Vo et al. 2018), also partial stripes; mean: the mean profile, full stripes only.")
     ap.add_argument("--batch", default=8, type=int, help="Projections on the device at a time.")
     ap.add_argument("--device", default="cuda", type=str)
     return ap
@@ -239,6 +277,8 @@ def main(argv=None):
         raise SystemExit("--data and --output are required")
     if args.batch < 1:
         raise SystemExit("--batch must be at least 1")
+    if args.destripe is not None and (args.destripe % 2 != 1 or not 1 <= args.destripe <= 31):
+        raise SystemExit("--destripe takes an odd window width in 1 .. 31")
     return convert(args, args.device)
 
 

@@ -1,13 +1,15 @@
-"""Conditioning of measured projections on the MI355X (csrc/projections.hip; include/r2hip.h: r2_proj_resize,
-r2_proj_median): what the reference's real-data converter does to a measured stack with cv2 and numpy -- lower clamp, row
-shift, ``cv2.resize``, crop -- as one fused pass, and a median filter against the isolated outliers of measured data (zingers,
-hot pixels, NaN read-outs), which ``weights.fill_unmeasured`` only handles once they are known.  ``prepare_real.py`` is the
-command line on top of these.
+"""Conditioning of measured projections on the MI355X (csrc/projections.hip, csrc/destripe.hip; include/r2hip.h:
+r2_proj_resize, r2_proj_median, r2_proj_destripe_sort, r2_proj_destripe_mean): what the reference's real-data converter does to
+a measured stack with cv2 and numpy -- lower clamp, row shift, ``cv2.resize``, crop -- as one fused pass, a median filter
+against the isolated outliers of measured data (zingers, hot pixels, NaN read-outs), which ``weights.fill_unmeasured`` only
+handles once they are known, and stripe removal against the defect that no single projection shows: a detector pixel that is
+slightly off in every view, a ring in the reconstruction.  ``prepare_real.py`` is the command line on top of these.
 
 Projections are [H,W] or [V,H,W] tensors on the GPU and so are the results: a host array raises, there is no CPU fallback.
 Inputs of another dtype or layout are converted to contiguous float32 first.  No host synchronisation.
 """
 import math
+import operator
 
 import torch
 
@@ -16,6 +18,12 @@ from ._boundary import call, f32c, require_gpu, workspace
 
 _F32 = torch.float32
 INTERPOLATIONS = {"linear": 0, "area": 1}
+DESTRIPE_METHODS = {"sort": 0, "mean": 1}
+
+
+def destripe_max_views():
+    """R2_DESTRIPE_MAX_VIEWS of the loaded library: the views that method="sort" orders in the LDS."""
+    return int(_lib.lib().r2_proj_destripe_max_views())
 
 
 def _stack(projs, name="projs"):
@@ -125,6 +133,53 @@ def despeckle(projs, threshold, size=3, return_mask=False):
     shape.  -> despeckled, or (despeckled, mask)."""
     dst, mask = _median(projs, size, True, threshold, return_mask)
     return (dst, mask.bool()) if return_mask else dst
+
+
+def _destripe(projs, size, method, want_dst, want_offsets):
+    try:
+        k = None if isinstance(size, bool) else operator.index(size)
+    except TypeError:
+        k = None
+    if k is None or k % 2 != 1 or not 1 <= k <= 31:
+        raise ValueError("size must be an odd integer in 1 .. 31, got %r" % (size,))
+    size = k
+    if method not in DESTRIPE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(DESTRIPE_METHODS), method))
+    if want_offsets and method != "mean":
+        raise ValueError("the offsets are a by-product of method=\"mean\"; method=%r has none" % (method,))
+    p, single = _stack(projs)
+    V, H, W = p.shape
+    if method == "sort" and V > destripe_max_views():
+        raise ValueError("method=\"sort\" orders at most %d views, got %d: use method=\"mean\"" % (destripe_max_views(), V))
+    if want_offsets and V == 0:
+        raise ValueError("a stack without views has no offsets")
+    ws = workspace(int(_lib.lib().r2_proj_destripe_workspace_bytes(V, H, W, DESTRIPE_METHODS[method])), p.device, at_least=1)
+    dst = torch.empty_like(p) if want_dst else None
+    offsets = torch.empty((H, W), dtype=_F32, device=p.device) if want_offsets else None
+    if method == "sort":
+        call("r2_proj_destripe_sort", p.device, V, H, W, p, size, dst, ws, ws.numel())
+    else:
+        call("r2_proj_destripe_mean", p.device, V, H, W, p, size, dst, offsets, ws, ws.numel())
+    return (dst[0] if single and want_dst else dst), offsets
+
+
+def destripe(projs, size=9, method="sort", return_offsets=False):
+    """Removes the stripes of the sinogram, the rings of the reconstruction: what a detector pixel adds to every view.  Works
+    along the view axis, so ``projs`` holds all views of the detector rows it covers ([H,W] is one view); rows are independent.
+    ``size``: the odd width, 1 .. 31, of the median across detector columns.  ``method``: "sort" (r2_proj_destripe_sort: Vo,
+    Atwood, Drakopoulos 2018, algorithm 3 -- every pixel's values sorted along the views, stably, a NaN as +inf, the sorted
+    sinogram median-filtered across the columns, every value put back at the view its rank came from; handles partial and
+    intensity-dependent stripes, at most ``destripe_max_views()`` views) or "mean" (r2_proj_destripe_mean: the mean over the views minus
+    its median across the columns is the pixel's offset, which every view loses; full-length constant stripes only; a NaN
+    spreads to its pixel in every view).  ``return_offsets``: with "mean", also the [H,W] offsets.
+    -> float32 of projs' shape, or (that, offsets)."""
+    dst, offsets = _destripe(projs, size, method, True, bool(return_offsets))
+    return (dst, offsets) if return_offsets else dst
+
+
+def stripe_offsets(projs, size=9):
+    """The [H,W] offsets that ``destripe(projs, size, "mean")`` subtracts, alone: a diagnostic of the detector."""
+    return _destripe(projs, size, "mean", False, True)[1]
 
 
 def normalize(raw, flat, dark=None, eps=1e-6):
