@@ -1,183 +1,98 @@
-"""ctypes binding of libr2hip.so (the C ABI declared in include/r2hip.h).
+"""ctypes binding of libr2hip.so, derived from the C ABI's one declaration, include/r2hip.h.
+
+The header is parsed once, at import: every ``R2_API`` prototype becomes an entry of ``_SIGNATURES`` and every integer
+``#define R2_*`` a module attribute (``parse_header``).  Adding an entry point means declaring it in the header; nothing here
+changes.
 
 The product path has NO fallback: if the HIP library is missing or fails to load, importing the ops
 raises.  Build it with ``python -m r2_gaussian_amd.build`` (or ``__graft_entry__.build()``).
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # R2HIP_LIB selects an experiment build (profiling ablations); the default is the product library
 LIB_PATH = os.environ.get("R2HIP_LIB") or os.path.join(_HERE, "libr2hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "r2hip.h")
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
-
-R2_ABI_VERSION = 3
-R2_ERR_INVALID = -10001
-R2_ERR_ALLOC = -10002
-R2_METRIC_SSIM = 1
-R2_METRIC_NORMALIZE = 2
-R2_LOSS_BATCH_CHUNK = 16
-R2_KNN_GRAPH_MAX_K = 16
-R2_GRAPH_KIND_L1, R2_GRAPH_KIND_L2, R2_GRAPH_KIND_HUBER = 0, 1, 2
-R2_GRAPH_LOSS_CHAIN = 17   # longest chain of float roundings in r2_graph_loss's reduction (include/r2hip.h)
-R2_GRAPH_LOSS_HUB = 64     # incoming lists longer than this are summed by a whole wave in r2_graph_loss_backward
-R2_MERGE_HUB = 64          # ... and walked by a whole wave in r2_graph_match / r2_merge_count
-R2_MERGE_JACOBI_SWEEPS = 8
-R2_RELOCATE_SCAN_TILE = 4096   # elements per workgroup of r2_relocate_plan's 64-bit scan
-R2_SPLINE_PAD = 12             # edge padding of r2_spline_prefilter's coefficient block, per side
-R2_SPLINE_HORIZON = 16         # terms of its start sum
-
-_f, _i, _p, _fp = C.c_float, C.c_int, C.c_void_p, C.c_void_p
-
-_SIGNATURES = {
-    "r2_abi_version": (C.c_int, []),
-    "r2_last_error": (C.c_char_p, []),
-    "r2_raster_forward": (C.c_int, [ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p, _i, _i, _i, _fp, _fp, _fp, _f, _fp, _fp,
-                                    _fp, _fp, _fp, _f, _f, _i, _i, _fp, _p, _i, _p]),
-    "r2_raster_backward": (C.c_int, [_i, _i, _i, _i, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _f, _f, _p, _p, _p, _p,
-                                     _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _p]),
-    "r2_mark_visible": (C.c_int, [_i, _fp, _fp, _fp, _p, _p]),
-    "r2_raster_forward_batch": (C.c_int, [ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p, _i, _i, _i, _i, _fp, _fp, _fp, _f, _fp,
-                                          _fp, _fp, _fp, _f, _f, _i, _fp, _p, _i, _p]),
-    "r2_raster_backward_batch": (C.c_int, [_i, _i, _i, _i, _i, _fp, _fp, _f, _fp, _fp, _fp, _fp, _f, _f, _p, _p, _p, _p,
-                                           _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _p]),
-    "r2_voxel_forward": (C.c_int, [ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f,
-                                   _fp, _fp, _fp, _f, _fp, _fp, _i, _fp, _p, _p, _p, _i, _p]),
-    "r2_voxel_backward": (C.c_int, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _fp, _fp, _f, _fp, _fp, _p, _p, _p,
-                                    _p, _p, _p, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _p]),
-    "r2_voxel_forward_slab": (C.c_int, [ALLOC_FN, _p, ALLOC_FN, _p, ALLOC_FN, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i,
-                                        _fp, _fp, _fp, _f, _fp, _fp, _i, _fp, _p, _p, _p, _i, _p]),
-    "r2_voxel_backward_slab": (C.c_int, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _fp, _fp, _f, _fp, _fp, _p, _p, _p,
-                                         _p, _p, _p, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _p]),
-    "r2_knn_dist2": (C.c_int, [_i, _fp, _fp, _p]),
-    "r2_knn_workspace_bytes": (C.c_size_t, [_i]),
-    "r2_knn_dist2_ws": (C.c_int, [_i, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_knn_graph_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_knn_graph": (C.c_int, [_i, _fp, _i, _p, _fp, _p, C.c_size_t, _p]),
-    "r2_graph_transpose_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_graph_transpose": (C.c_int, [_i, _i, _p, _p, _p, _p, C.c_size_t, _p]),
-    "r2_graph_loss_scratch_floats": (C.c_size_t, [_i, _i]),
-    "r2_graph_loss": (C.c_int, [_i, _i, _fp, _p, _fp, _i, _f, _f, _fp, _fp, _p]),
-    "r2_graph_loss_backward": (C.c_int, [_i, _i, _fp, _p, _fp, _p, _p, _i, _f, _f, _fp, _fp, _p]),
-    "r2_merge_cost": (C.c_int, [_i, _i, _p, _fp, _fp, _fp, _fp, _f, _fp, _p]),
-    "r2_graph_match_workspace_bytes": (C.c_size_t, [_i]),
-    "r2_graph_match": (C.c_int, [_i, _i, _p, _p, _p, _fp, _f, _i, _p, _p, C.c_size_t, _p]),
-    "r2_merge_scratch_bytes": (C.c_size_t, [_i]),
-    "r2_merge_count": (C.c_int, [_i, _i, _p, _p, _p, _fp, _f, _p, _fp, _fp, _p, _p, _p]),
-    "r2_merge_emit": (C.c_int, [_i, _fp, _fp, _fp, _fp, _p, _i, _fp, _fp, _fp, _fp, _p, _p]),
-    "r2_gaussian_noise": (C.c_int, [_i, _fp, _fp, _fp, _fp, C.c_double, _f, _f, C.c_ulonglong, C.c_ulonglong, _p]),
-    "r2_relocate_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_relocate_plan": (C.c_int, [_i, _i, _p, _fp, _fp, _f, C.c_ulonglong, C.c_ulonglong, _p, _p, _p, C.c_size_t, _p, _p]),
-    "r2_relocate_emit": (C.c_int, [_i, _i, _p, _p, _p, _fp, _fp, _fp, _fp, _fp, _fp, _f, C.c_ulonglong, C.c_ulonglong, _p, _p,
-                                   _p, C.c_size_t, _p, _p, _p, _fp, _fp, _fp, _p]),
-    "r2_tile_first_stats": (None, [C.POINTER(C.c_longlong), _i]),
-    "r2_defer_count_control": (None, [_i]),
-    "r2_defer_count_resolve": (C.c_int, [_i, C.POINTER(C.c_int), _p]),
-    "r2_defer_count_stats": (None, [C.POINTER(C.c_longlong), _i]),
-    "r2_voxel_sticks_control": (None, [_i]),
-    "r2_voxel_sticks_limits": (None, [C.c_longlong, C.c_longlong]),
-    "r2_voxel_sticks_stats": (None, [C.POINTER(C.c_longlong), _i]),
-    "r2_thread_release": (None, []),
-    "r2_path_stat_count": (C.c_int, []),
-    "r2_path_stat_name": (C.c_char_p, [_i]),
-    "r2_path_stats": (C.c_int, [C.POINTER(C.c_longlong), _i, _i]),
-    "r2_densify_stats": (C.c_int, [_i, _p, _fp, _fp, _fp, _fp, _p]),
-    "r2_densify_stats_batch": (C.c_int, [_i, _i, _p, _fp, _f, _fp, _fp, _fp, _p]),
-    "r2_densify_scratch_bytes": (C.c_size_t, [_i]),
-    "r2_densify_classify": (C.c_int, [_i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _f, _p, _f, _f, _i, _f, _f, _p, _p, _p]),
-    "r2_densify_emit": (C.c_int, [_i, _p, _p, _p, _fp, _fp, _fp, _fp, _f, _f, _f, _p, _f, _f, _i, _f, _f, _p, _p, _p, _p, _fp,
-                                  _fp, _fp, _p]),
-    "r2_loss_l1_ssim_scratch_floats": (C.c_size_t, [_i, _i]),
-    "r2_loss_l1_ssim": (C.c_int, [_i, _i, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
-    "r2_loss_l1_ssim_batch_scratch_floats": (C.c_size_t, [_i, _i, _i]),
-    "r2_loss_l1_ssim_batch": (C.c_int, [_i, _i, _i, _fp, _p, _f, _f, _fp, _fp, _fp, _p]),
-    "r2_loss_l1_ssim_weighted_scratch_floats": (C.c_size_t, [_i, _i]),
-    "r2_loss_l1_ssim_weighted": (C.c_int, [_i, _i, _fp, _fp, _fp, _f, _f, _fp, _fp, _fp, _p]),
-    "r2_loss_l1_ssim_weighted_batch_scratch_floats": (C.c_size_t, [_i, _i, _i]),
-    "r2_loss_l1_ssim_weighted_batch": (C.c_int, [_i, _i, _i, _fp, _p, _p, _f, _f, _fp, _fp, _fp, _p]),
-    "r2_loss_tv3d_scratch_floats": (C.c_size_t, [_i, _i, _i]),
-    "r2_loss_tv3d": (C.c_int, [_i, _i, _i, _fp, _f, _fp, _fp, _fp, _p]),
-    "r2_metric_slices_scratch_floats": (C.c_size_t, [_i, _i, _i, _i]),
-    "r2_metric_slices": (C.c_int, [_i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _p]),
-    "r2_fdk_filter": (C.c_int, [_i, _i, _i, _fp, _fp, _f, _i, _f, _f, _f, _fp, _p]),
-    "r2_fdk_backproject": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _f, _i, _i, _i, _f, _f, _f, _f, _f, _f, _fp, _p]),
-    "r2_project_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
-    "r2_backproject_volume": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _p]),
-    "r2_project_volume_siddon": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _p]),
-    "r2_backproject_volume_siddon": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _i, _f, _f, _f, _fp, _fp, _p]),
-    "r2_project_gaussians": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
-    "r2_project_gaussians_backward": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
-    "r2_project_gaussians_rays_backward_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "r2_project_gaussians_rays_backward": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_query_gaussians": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
-    "r2_query_gaussians_workspace_bytes": (C.c_size_t, [_i]),
-    "r2_query_gaussians_backward": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_integrate_gaussians": (C.c_int, [_i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_integrate_gaussians_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_integrate_gaussians_backward": (C.c_int, [_i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _p,
-                                                  C.c_size_t, _p]),
-    "r2_integrate_gaussians_leaves": (C.c_int, [_i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_integrate_gaussians_leaves_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_integrate_gaussians_leaves_backward": (C.c_int, [_i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _p,
-                                                         C.c_size_t, _p]),
-    "r2_project_gaussians_fisher": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
-    "r2_query_gaussians_variance": (C.c_int, [_i, _fp, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
-    "r2_project_gaussians_variance": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
-    "r2_project_gaussians_jvp": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp, _p]),
-    "r2_project_gaussians_ray_jacobian": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p]),
-    "r2_project_gaussians_plan_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
-    "r2_project_gaussians_plan_count": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _p, _p, C.c_size_t, _p]),
-    "r2_project_gaussians_plan_fill": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _p, _p, C.c_longlong, _p,
-                                                 C.c_size_t, _p]),
-    "r2_project_gaussians_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, _p, C.c_longlong, _p]),
-    "r2_project_gaussians_rays_backward_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _p,
-                                                             C.c_size_t, _p, _p, C.c_longlong, _p]),
-    "r2_project_gaussians_variance_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp,
-                                                        _p, _p, C.c_longlong, _p]),
-    "r2_project_gaussians_jvp_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _fp, _fp, _fp, _fp,
-                                                   _p, _p, C.c_longlong, _p]),
-    "r2_project_gaussians_ray_jacobian_planned": (C.c_int, [_i, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _f, _fp, _fp, _p, _p,
-                                                            C.c_longlong, _p]),
-    "r2_tv_descent_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
-    "r2_tv_descent": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p, C.c_size_t, _p]),
-    "r2_tv_prox_scratch_bytes": (C.c_size_t, [_i, _i, _i]),
-    "r2_tv_prox": (C.c_int, [_i, _i, _i, _fp, _fp, _fp, _i, _f, _f, _p, C.c_size_t, _p]),
-    "r2_isosurface_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "r2_isosurface_count": (C.c_int, [_i, _i, _i, _fp, _f, _p, C.c_size_t, _p, _p]),
-    "r2_isosurface_fill": (C.c_int, [_i, _i, _i, _fp, _f, _f, _f, _f, _f, _f, _f, _p, C.c_size_t, C.c_longlong, C.c_longlong,
-                                     _fp, _fp, _p, _p]),
-    "r2_spline_prefilter": (C.c_int, [_i, _i, _i, _fp, _fp, _p]),
-    "r2_spline_prefilter_pass": (C.c_int, [_i, _i, _i, _fp, _fp, _i, _p]),
-    "r2_spline_zoom_workspace_bytes": (C.c_size_t, [_i, _i, _i]),
-    "r2_spline_zoom": (C.c_int, [_i, _i, _i, _fp, _i, _i, _i, _fp, _p, C.c_size_t, _p]),
-    "r2_spline_sample": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _fp, _p]),
-    "r2_proj_resize_workspace_bytes": (C.c_size_t, [_i, _i]),
-    "r2_proj_resize": (C.c_int, [_i, _i, _i, _fp, _i, _i, _f, _i, _i, _i, _i, _i, _i, _i, _fp, _p, C.c_size_t, _p]),
-    "r2_proj_median": (C.c_int, [_i, _i, _i, _fp, _i, _i, _f, _fp, _p, _p]),
-    "r2_proj_destripe_max_views": (C.c_int, []),
-    "r2_proj_destripe_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i]),
-    "r2_proj_destripe_sort": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _p, C.c_size_t, _p]),
-    "r2_proj_destripe_mean": (C.c_int, [_i, _i, _i, _fp, _i, _fp, _fp, _p, C.c_size_t, _p]),
-    "r2_gaussian_activate": (C.c_int, [_i, _fp, _fp, _fp, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
-    "r2_gaussian_adam_step": (C.c_int, [_i, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_double, _fp, _fp, _fp, _p]),
-    "r2_profile_enable": (None, [C.c_ulonglong]),
-    "r2_profile_stage_count": (C.c_int, []),
-    "r2_profile_stage_name": (C.c_char_p, [_i]),
-    "r2_profile_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_longlong), _i]),
-    "r2_sync_wait_stats": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_longlong), _i]),
-    "r2_depth_hint_control": (None, [_i]),
-    "r2_tile_first_control": (None, [_i]),
-    "r2_profile_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong), _i]),
-    "r2_raster_state_offset": (C.c_longlong, [_i, _i, C.c_longlong, _i, _i, C.POINTER(C.c_int)]),
-    "r2_voxel_state_offset": (C.c_longlong, [_i, _i, C.c_longlong, _i, _i, _i, C.POINTER(C.c_int)]),
-}
-
-_lib = None
 
 
 class R2HipError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char *": C.c_char_p})
+_PARAMS = dict(_SCALARS, r2_alloc_fn=ALLOC_FN)
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(R2_\w+)[ \t]+(?:(-?\d+)|\([ \t]*(-?\d+)[ \t]*\))[ \t]*$", re.M)
+_PROTOTYPE = re.compile(r"R2_API\s+([\w\s*]+?)\b(r2_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def parse_header(text):
+    """-> ({name: (restype, [argtypes])}, {R2_NAME: int}) of a header written like include/r2hip.h.
+
+    Comments and preprocessor lines are dropped; what remains is matched as ``R2_API <ret> r2_name(<params>);``.  The types:
+
+        parameter with ``*`` or an array declarator                      c_void_p
+            (``long long out[3]``, ``const char *``, ``const float *const *``)
+        int / float / double                                              c_int / c_float / c_double
+        size_t / long long / unsigned long long                           c_size_t / c_longlong / c_ulonglong
+        r2_alloc_fn                                                       ALLOC_FN
+        return void / const char * / one of the scalar types              None / c_char_p / as above
+
+    Anything else raises R2HipError naming the declaration: a type that is not listed (add it to the rule with the header),
+    a parameter without a name, an ``R2_API`` the pattern does not consume.  Nothing is guessed.
+
+    Every pointer is c_void_p because the header cannot tell a host pointer from a device pointer: the out-parameters of the
+    stats, profile and offset calls are host pointers and take ``byref(...)``, a ctypes array, ``pointer(...)``, None or an
+    address like any other.
+
+    Constants: ``#define R2_<NAME> <integer>``, the integer decimal, possibly negative and parenthesised; other defines
+    (``R2_API`` itself, non-integers) are not constants."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2) or m.group(3)) for m in _DEFINE.finditer(text)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    signatures = {}
+    for at in re.finditer(r"\bR2_API\b", text):
+        m = _PROTOTYPE.match(text, at.start())
+        if m is None:
+            raise R2HipError("r2hip.h: cannot parse the declaration `%s ...`" % " ".join(text[at.start():at.start() + 120].split()))
+        ret, name, params = " ".join(m.group(1).replace("*", " * ").split()), m.group(2), m.group(3).split(",")
+        if ret not in _RETURNS:
+            raise R2HipError("r2hip.h: return type `%s` of %s is not in the binding's type rule" % (ret, name))
+        args = []
+        for p in [] if m.group(3).strip() == "void" else params:
+            if "*" in p or p.rstrip().endswith("]"):
+                args.append(C.c_void_p)
+                continue
+            ctype = " ".join(p.split()[:-1])   # the last word is the parameter's name
+            if ctype not in _PARAMS:
+                raise R2HipError("r2hip.h: parameter `%s` of %s is not in the binding's type rule" % (" ".join(p.split()), name))
+            args.append(_PARAMS[ctype])
+        signatures[name] = (_RETURNS[ret], args)
+    return signatures, constants
+
+
+with open(HEADER_PATH, "r", encoding="utf-8") as _fh:
+    _SIGNATURES, _CONSTANTS = parse_header(_fh.read())
+globals().update(_CONSTANTS)   # R2_ABI_VERSION, R2_ERR_INVALID, ... under the header's names
+
+_lib = None
+
+
+def bind(path):
+    """CDLL(path) with the header's restype / argtypes on every symbol and the ABI version checked: this build or another one."""
+    L = C.CDLL(path)
+    for name, (res, args) in _SIGNATURES.items():
+        fn = getattr(L, name)   # AttributeError if a declared symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    if L.r2_abi_version() != R2_ABI_VERSION:
+        raise R2HipError("%s ABI %d != expected %d" % (os.path.basename(path), L.r2_abi_version(), R2_ABI_VERSION))
+    return L
 
 
 def lib():
@@ -188,14 +103,7 @@ def lib():
             raise R2HipError(
                 "libr2hip.so not found at %s -- the HIP extension is required (no fallback). "
                 "Run `python -m r2_gaussian_amd.build`." % LIB_PATH)
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)   # AttributeError if a declared symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
-        if L.r2_abi_version() != R2_ABI_VERSION:
-            raise R2HipError("libr2hip.so ABI %d != expected %d" % (L.r2_abi_version(), R2_ABI_VERSION))
-        _lib = L
+        _lib = bind(LIB_PATH)
     return _lib
 
 

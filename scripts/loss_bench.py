@@ -15,7 +15,6 @@ the weighted kernels on unit weights).  Metric variants: r2_metric_slices with R
 R2_METRIC_SSIM | R2_METRIC_NORMALIZE along axis 0.  Prints one line per variant and one JSON line; exit status 1 if any bit
 differs; nothing is asserted about the weighted cost."""
 import argparse
-import ctypes as C
 import json
 import statistics
 import sys
@@ -26,17 +25,6 @@ import torch
 sys.path.insert(0, ".")
 from r2_gaussian_amd import _lib
 from r2_gaussian_amd._boundary import ptr_table
-
-NAMES = [n for n in _lib._SIGNATURES if n.startswith("r2_loss_l1_ssim")] + ["r2_metric_slices_scratch_floats", "r2_metric_slices"]
-
-
-def load_other(path):
-    """Another build of the library with the loss and metric entries' ctypes signatures of this one."""
-    L = C.CDLL(path)
-    for n in NAMES:
-        fn = getattr(L, n)
-        fn.restype, fn.argtypes = _lib._SIGNATURES[n]
-    return L
 
 
 def time_rounds(variants, calls, rounds):
@@ -90,7 +78,7 @@ def main(argv=None):
     here = _lib.lib()
     libs = {"this": here}
     if args.parent:
-        libs["parent"] = load_other(args.parent)
+        libs["parent"] = _lib.bind(args.parent)
     n, lam = args.size, 0.25
     gen = torch.Generator().manual_seed(0)
     result = {"size": n, "volume": list(args.volume), "calls": args.calls, "rounds": args.rounds, "variants": {}}

@@ -34,7 +34,6 @@ fista_tv with 50 iterations over a decade grid of lam (relative to |A^T b|_inf) 
 against the phantom and the TV of the result, next to SART-10 on the same data.
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -52,13 +51,6 @@ from r2_gaussian_amd import scene as S        # noqa: E402
 
 COPY_BW = 6.29e12   # bytes / s: the chip's measured float4 copy rate
 FLOATS_PER_ITER = {"one_launch": 13, "two_launch": 18}
-
-
-def bind(path):
-    L = C.CDLL(path)
-    res, args = _lib._SIGNATURES["r2_tv_prox"]
-    L.r2_tv_prox.restype, L.r2_tv_prox.argtypes = res, args
-    return L
 
 
 def event_ms(fn):
@@ -173,9 +165,9 @@ def main():
     if a.sweep:
         print(json.dumps(sweep(dev)))
         return
-    libs = {"one_launch": bind(_lib.LIB_PATH)}
+    libs = {"one_launch": _lib.bind(_lib.LIB_PATH)}
     if a.alt_lib:
-        libs["two_launch"] = bind(os.path.abspath(a.alt_lib))
+        libs["two_launch"] = _lib.bind(os.path.abspath(a.alt_lib))
     res = {"rounds": a.rounds, "iters": a.iters}
     for n in a.sizes:
         res["prox_%d" % n] = time_prox(libs, n, a.iters, a.rounds, dev)

@@ -42,6 +42,98 @@ def test_ctypes_binding_matches_header():
     _lib.lib()   # sets argtypes on every symbol; raises on a missing one
 
 
+SYNTHETIC_HEADER = """
+/* a header in the style of r2hip.h: one declaration per case of the rule */
+#ifndef X_H
+#define X_H
+#if defined(__GNUC__)
+#define R2_API __attribute__((visibility("default")))
+#else
+#define R2_API
+#endif
+#define R2_PLAIN 7
+#define R2_NEGATIVE (-10003) /* parenthesised, with a comment */
+#define R2_BARE_NEGATIVE -4
+#define R2_RATIO 1.5
+#define R2_NAME "text"
+typedef char *(*r2_alloc_fn)(size_t bytes, void *user);
+R2_API int r2_no_args(void);
+R2_API const char *r2_message(int code);
+R2_API void r2_control(int on, const char *label);
+R2_API size_t r2_sizes(size_t bytes, double x, unsigned long long seed, r2_alloc_fn grow, void *user, long long n);
+R2_API long long r2_offsets(const float *const *tables, long long out[5], float scale);
+R2_API int r2_spread(
+    int P,
+    const float *means3D,      /* [P,3] (x, y, z), row-major */
+    float *out /* [P] */,
+    void *stream);
+R2_API double r2_ratio(unsigned long long a);
+"""
+
+
+def test_parser_maps_every_declaration_form():
+    """_lib.parse_header on a synthetic header: the exact (restype, argtypes) of every case of the type rule, comments with
+    commas and parentheses inside a parameter list, a declaration over several lines, and which #defines are constants."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p
+    from r2_gaussian_amd import _lib
+    sigs, consts = _lib.parse_header(SYNTHETIC_HEADER)
+    assert sigs == {
+        "r2_no_args": (c_int, []),
+        "r2_message": (c_char_p, [c_int]),
+        "r2_control": (None, [c_int, c_void_p]),
+        "r2_sizes": (c_size_t, [c_size_t, c_double, c_ulonglong, _lib.ALLOC_FN, c_void_p, c_longlong]),
+        "r2_offsets": (c_longlong, [c_void_p, c_void_p, c_float]),
+        "r2_spread": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+        "r2_ratio": (c_double, [c_ulonglong]),
+    }
+    assert list(sigs) == ["r2_no_args", "r2_message", "r2_control", "r2_sizes", "r2_offsets", "r2_spread", "r2_ratio"]
+    assert consts == {"R2_PLAIN": 7, "R2_NEGATIVE": -10003, "R2_BARE_NEGATIVE": -4}
+
+
+@pytest.mark.parametrize("name, decl", [
+    ("r2_unsigned", "R2_API int r2_unsigned(int n, unsigned x);"),
+    ("r2_fixed_width", "R2_API int r2_fixed_width(int64_t n);"),
+    ("r2_unnamed", "R2_API int r2_unnamed(int);"),
+    ("r2_returns_unsigned", "R2_API unsigned r2_returns_unsigned(int n);"),
+    ("r2_returns_pointer", "R2_API float *r2_returns_pointer(int n);"),
+    ("r2_callback", "R2_API int r2_callback(int (*cb)(int), void *user);"),
+    ("r2_unterminated", "R2_API int r2_unterminated(int n)\nR2_API int r2_next(void);"),
+])
+def test_parser_refuses_what_the_rule_does_not_cover(name, decl):
+    """A type outside the rule, or an R2_API the pattern does not consume, raises and names the function: nothing is guessed
+    and nothing is skipped."""
+    from r2_gaussian_amd import _lib
+    with pytest.raises(_lib.R2HipError, match=r"\b%s\b" % name):
+        _lib.parse_header("R2_API int r2_before(void);\n" + decl + "\nR2_API int r2_after(void);\n")
+
+
+def test_binding_is_the_header():
+    """The real header: every declared symbol is bound, with nothing but the rule's ten types, and every integer R2_* #define
+    (found by this test's own regex) is the module attribute of that name."""
+    import ctypes as C
+    from r2_gaussian_amd import _lib
+    assert set(declared_symbols()) <= set(_lib._SIGNATURES) and len(declared_symbols()) > 100
+    scalars = {C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_longlong, C.c_ulonglong}
+    for name, (res, args) in _lib._SIGNATURES.items():
+        assert res in scalars | {None, C.c_char_p}, name
+        assert all(a in scalars | {C.c_void_p, _lib.ALLOC_FN} for a in args), name
+    defines = re.findall(r"^#define\s+(R2_[A-Z0-9_]+)\s+\(?(-?[0-9]+)\)?\s*(?:/\*.*)?$", open(HEADER).read(), flags=re.M)
+    assert len(defines) >= 18 and {"R2_ABI_VERSION", "R2_ERR_INVALID", "R2_SPLINE_PAD", "R2_DESTRIPE_MAX_VIEWS"} <= dict(defines).keys()
+    for name, value in defines:
+        assert getattr(_lib, name) == int(value), name
+    assert _lib.R2_ERR_INVALID == -10001 and _lib.R2_ABI_VERSION == 3
+
+
+def test_bind_types_any_build_of_the_library(tmp_path):
+    import ctypes as C
+    from r2_gaussian_amd import _lib
+    L = _lib.bind(_lib.LIB_PATH)
+    assert L.r2_abi_version() == _lib.R2_ABI_VERSION
+    assert L.r2_knn_workspace_bytes.argtypes == [C.c_int] and L.r2_knn_workspace_bytes.restype is C.c_size_t
+    with pytest.raises(OSError):
+        _lib.bind(str(tmp_path / "nope.so"))
+
+
 def test_only_declared_symbols_are_exported():
     """-fvisibility=hidden: nothing but the r2_* C ABI leaks out of the library."""
     from r2_gaussian_amd import _lib
