@@ -643,6 +643,61 @@ R2_API int r2_project_volume(int V, int H, int W, const float *rays /* [V,12] */
                              float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy, const float *vol /* [nx,ny,nz] */,
                              float *out /* [V,H,W] */, void *stream);
 
+/* ---- direct volume rendering (pyvista's plotter.add_volume as scripts/plot_volume.py and data_generator/check_volume.py call
+ * it to look at a volume; csrc/volume_render.hip) ------------------------------------------------------------------------------
+ * The rays, the coordinates, the clip [t0, t1], n, dt = (t1 - t0)/n, wlen = |d_world| and the sample positions
+ * q_k = q(t0 + (k + 1/2) dt), k = 0..n-1, are those of r2_project_volume, word for word (the same csrc/ray_sampling.hpp), and
+ * f(q_k) is its trilinear value (csrc/trilinear.hpp): a renderer sample is a projector sample.
+ *
+ * r2_volume_bricks: bricks[bx][by][bz][2], b_a = ceil(n_a / R2_RENDER_BRICK).  Entry (i, j, k) holds the min and the max of vol
+ * over the voxel indices [8 b, min(8 b + 8, n_a - 1)] of each axis (nine per axis: the footprint of every trilinear cell whose
+ * floor index lies in the brick), widened to contain 0 where the brick touches a face of the volume on any axis (b = 0 or
+ * 8 b + 8 > n_a - 1: a sample there mixes in the zero outside), a zero stored as +0; NaN voxels are ignored (fminf / fmaxf).
+ * A sample whose floor index on an axis is i belongs to brick clamp(i, 0, n_a - 1) >> 3 of that axis.  The table does not
+ * depend on any transfer function and may be reused for as long as vol is unchanged.  No atomics; bit-identical to its NumPy
+ * restatement (tests/volume_render_ref.py).  At most 2^31 - 1 bricks; bricks 8-byte aligned.
+ *
+ * r2_render_volume: out[V][H][W][4] = the emission-absorption image of vol under the transfer function lut[K][4] = rows
+ * (r, g, b, ext), row j standing at the value lo + j (hi - lo)/(K - 1) and linear between rows; ext is an extinction per world
+ * length.  With scale = (float)(K - 1) / (hi - lo) (float32, computed once), dl = dt * wlen (one product), C = (0, 0, 0), T = 1,
+ * per sample k in order, every operation a separately rounded float32 one:
+ *     f = f(q_k)
+ *     x = fminf(fmaxf((f - lo) * scale, 0), K - 1)          (a NaN lands on 0 and can never index outside the table)
+ *     i = min((int)floorf(x), K - 2),   w = x - i
+ *     c = lut[i][ch] + w * (lut[i+1][ch] - lut[i][ch])      for ch = r, g, b, ext: a difference, a product, a sum
+ *     e = expf(-(ext * dl))                                 (the accurate expf)
+ *     C_ch = C_ch + (T * (1 - e)) * c_ch                    for ch = r, g, b
+ *     T = T * e
+ * and the loop ends after the first sample that leaves T < t_stop (t_stop = 0: never).  out = (C_r, C_g, C_b, 1 - T):
+ * premultiplied colour and opacity.  A ray that misses writes four exact zeros.
+ * bricks: NULL, or the table of r2_volume_bricks for this vol.  With a table, samples of EMPTY bricks are passed over: a brick
+ * with entry (mn, mx) is empty iff every row that the values [mn - 8 u M, mx + 8 u M] can reach has ext == 0, where u = 2^-24,
+ * M = max(|mn|, |mx|), both ends are float32 sums rounded outwards by one more float32 where M > 0, and are mapped through the
+ * index arithmetic above to the positions xa <= xb in the cells ia <= ib: the rows ia .. ib, and ib + 1 where xb > ib (a brick of
+ * exact zeros at x = 0 thus reads row 0 alone, which is what makes air empty under a ramp that starts at 0).  8 u M bounds what
+ * the float32 interpolant can exceed its eight voxels by
+ * (tests/projector_ref.py).  A passed-over sample would have contributed exactly nothing (ext = 0, e = expf(-0) = 1,
+ * T * 1 = T, T * 0 * c = 0), so the output with a table equals the output without, bit for bit; this needs a finite lut, finite
+ * dl and NaN-free vol.  The sample index only moves forward, and only over samples whose own brick tested empty.
+ * Limits: K in [2, 1024] (the table lives in LDS); hi > lo, both finite; t_stop in [0, 1); lut and out 16-byte aligned;
+ * otherwise, and beyond the limits of r2_project_volume, R2_ERR_INVALID with nothing written.  ext >= 0 is the caller's to keep.
+ * No atomics, no allocation, no host synchronisation; bit-reproducible, and a view's output does not depend on the other views
+ * of the call.
+ *
+ * r2_render_volume_mip: out[V][H][W] = max_k f(q_k) over the same samples (fmaxf from -inf; a miss writes 0).  With a table a
+ * brick is passed over iff mx + 8 u M, rounded outwards as above, <= the running maximum; same bits with and without. */
+#define R2_RENDER_BRICK 8
+R2_API int r2_volume_bricks(int nx, int ny, int nz, const float *vol /* [nx,ny,nz] */, float *bricks /* [bx,by,bz,2] */,
+                            void *stream);
+R2_API int r2_render_volume(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                            float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy, const float *vol /* [nx,ny,nz] */,
+                            const float *bricks /* [bx,by,bz,2] or NULL */, int K, const float *lut /* [K,4] = r, g, b, ext */,
+                            float lo, float hi, float t_stop, float *out /* [V,H,W,4] */, void *stream);
+R2_API int r2_render_volume_mip(int V, int H, int W, const float *rays /* [V,12] */, int cone, int nx, int ny, int nz,
+                                float dVoxel_x, float dVoxel_y, float dVoxel_z, float accuracy,
+                                const float *vol /* [nx,ny,nz] */, const float *bricks /* [bx,by,bz,2] or NULL */,
+                                float *out /* [V,H,W] */, void *stream);
+
 /* r2_project_volume_siddon: the same rays, coordinates and arguments (no `accuracy`) with the Siddon ray-voxel intersection
  * model: voxel (i,j,k) is the index-space cube [i - 1/2, i + 1/2]^3 with the constant value vol[i][j][k], the volume is
  * [-1/2, n_a - 1/2] on each axis and zero outside, and out = the exact integral of that piecewise-constant function along

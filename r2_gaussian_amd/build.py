@@ -53,6 +53,9 @@ SOURCES = {
     "fdk.hip": FAST,
     "projector.hip": EXACT,
     "backprojector.hip": EXACT,
+    # EXACT: the walk is the projector's, bit for bit, and the per-sample operations are the ones include/r2hip.h states and
+    # tests/volume_render_ref.py restates
+    "volume_render.hip": EXACT,
     "projector_siddon.hip": EXACT,
     "backprojector_siddon.hip": EXACT,
     # EXACT: the per-pair arithmetic is then, operation for operation, the float32 restatement whose measured error sets the

@@ -21,7 +21,7 @@
 // This TU is compiled with -ffp-contract=off (build.py: EXACT): the clip points and n are separately rounded float32
 // operations, so the float64 restatement (tests/projector_ref.py) can tell which pixels sit on a decision boundary.  The
 // sampling loop contracts by hand (fmaf), where the restatement's bound covers it.
-#include "ray_sampling.hpp"
+#include "trilinear.hpp"
 #include "volume_entry.hpp"
 #include <math.h>
 
@@ -55,17 +55,7 @@ __global__ void __launch_bounds__(PB) project_kernel(int H, int W, const float *
     for (int k = 0; k < ns; ++k) {
         const float t = sample_t(k, dt, t0);
         const Axis X = axis_of(fmaf(t, dx, sx), nx), Y = axis_of(fmaf(t, dy, sy), ny), Z = axis_of(fmaf(t, dz, sz), nz);
-        const OFF x0 = (OFF)X.i0 * sxy, x1 = X.i1 != X.i0 ? x0 + sxy : x0;
-        const unsigned y0 = (unsigned)Y.i0 * (unsigned)nz, y1 = Y.i1 != Y.i0 ? y0 + (unsigned)nz : y0;
-        const unsigned z0 = (unsigned)Z.i0, z1 = (unsigned)Z.i1;
-        // the clamped neighbours are always inside the volume: load all eight unconditionally (no branches around the
-        // gathers); a neighbour outside it has weight 0
-        const float v000 = vol[x0 + (y0 + z0)], v001 = vol[x0 + (y0 + z1)], v010 = vol[x0 + (y1 + z0)], v011 = vol[x0 + (y1 + z1)];
-        const float v100 = vol[x1 + (y0 + z0)], v101 = vol[x1 + (y0 + z1)], v110 = vol[x1 + (y1 + z0)], v111 = vol[x1 + (y1 + z1)];
-        const float c00 = fmaf(Z.w1, v001, Z.w0 * v000), c01 = fmaf(Z.w1, v011, Z.w0 * v010);
-        const float c10 = fmaf(Z.w1, v101, Z.w0 * v100), c11 = fmaf(Z.w1, v111, Z.w0 * v110);
-        const float c0 = fmaf(Y.w1, c01, Y.w0 * c00), c1 = fmaf(Y.w1, c11, Y.w0 * c10);
-        acc += fmaf(X.w1, c1, X.w0 * c0);
+        acc += trilinear<OFF>(vol, X, Y, Z, sxy, nz);
     }
     *o = acc * (dt * wlen);
 }

@@ -213,7 +213,7 @@ def pick_views(stack, n_views, count, rng):
 def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry, init_points, opt, model_path,
              scale_bound=None, test_iterations=(), save_iterations=(), checkpoint_iterations=(), start_checkpoint=None,
              seed=0, log=print, device="cuda", views_per_step=1, eval_exact=False, save_uncertainty=None, train_weights=None,
-             save_mesh=None):
+             save_mesh=None, save_render=None):
     """The training loop of train.py:34-216.  views: scene.View lists; projections: [V, H, W] in scene units (times
     scene_scale); vol_gt [nx, ny, nz]; geometry: the NORMALISED scanner config (nVoxel, sVoxel, offOrigin, dVoxel);
     init_points [N, 4] = xyz | density; scale_bound: (lo, hi) in scene units or None.  Randomness (view order, TV patch centres,
@@ -229,6 +229,9 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
     save_mesh = level (None: off, mesh.py is then never imported): after the last iteration ``mesh.model_isosurface`` of the
     final model at that level, on the evaluation grid, snapped onto the field and closed at the grid's border, goes into
     mesh.ply next to the predicted volume (scene units, with normals); training itself is untouched.
+    save_render = (H, W) (None: off, volume_render.py is then never imported): after the last iteration the final model's
+    volume on the evaluation grid goes through ``volume_render.picture`` at its defaults (plot_volume.py's half-cut viridis
+    view) into render.png next to the predicted volume; training itself is untouched.
     opt.lambda_graph > 0 (absent = 0: off, the loop is then the one above and graph.py is never called): the loss gains
     lambda_graph * graph.graph_smoothness(density[:, 0], G, kind="l1"), G = the opt.graph_k (8) nearest neighbours of
     xyz.detach(), rebuilt every opt.graph_every (100) iterations and whenever the number of Gaussians changed.
@@ -385,6 +388,14 @@ def training(train_views, train_projs, test_views, test_projs, vol_gt, geometry,
                                              geometry["sVoxel"])
         MS.write_ply(osp.join(model_path, "point_cloud", "iteration_%d" % opt.iterations, "mesh.ply"), mv, mf, mn)
         log("mesh.ply: %d vertices, %d triangles at level %g" % (mv.shape[0], mf.shape[0], float(save_mesh)))
+    if save_render is not None:
+        from . import volume_render as VR
+        with torch.no_grad():
+            x, d, s, r = (t.detach() for t in gaussians.activated())
+            vol = _query(x, d, s, r, geometry["offOrigin"], geometry["nVoxel"], geometry["sVoxel"])
+            img = VR.picture(vol, geometry["sVoxel"], geometry["offOrigin"], size=save_render)[0]
+        VR.write_png(osp.join(model_path, "point_cloud", "iteration_%d" % opt.iterations, "render.png"), img)
+        log("render.png: %d x %d" % (img.shape[1], img.shape[0]))
     out["it_per_s"] = n_timed / t_train if t_train > 0 else float("nan")
     out["views_per_s"] = W * out["it_per_s"]
     out["model"] = gaussians
@@ -499,6 +510,10 @@ def build_parser():
                     help="after the last iteration write mesh.ply into the last point_cloud/iteration_N: the isosurface of the "
                          "final model's density at LEVEL (scene units), extracted on the evaluation grid, moved onto the "
                          "continuous field's level set and closed at the grid's border (mesh.model_isosurface)")
+    ap.add_argument("--save_render", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="after the last iteration write render.png, H rows by W columns, into the last "
+                         "point_cloud/iteration_N: the final model's volume on the evaluation grid by direct volume rendering "
+                         "at the defaults of volume_render.py (half cut away along x, viridis, linear opacity)")
     return ap
 
 
@@ -545,7 +560,7 @@ def main(argv=None):
                    case["geometry"], case["init_points"], opt, args.model_path, scale_bound, set(args.test_iterations),
                    set(args.save_iterations), set(args.checkpoint_iterations), args.start_checkpoint, log=log,
                    views_per_step=args.views_per_step, eval_exact=args.eval_exact, save_uncertainty=args.save_uncertainty,
-                   train_weights=case["train_weights"], save_mesh=args.save_mesh)
+                   train_weights=case["train_weights"], save_mesh=args.save_mesh, save_render=args.save_render)
     print("Training complete. " + _rate(out, args.views_per_step))
     return out
 
