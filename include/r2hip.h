@@ -270,7 +270,9 @@ R2_API int r2_metric_slices(int n0, int n1, int n2, int axis, const float *gt, c
  * N(0,1) samples indexed by the PARENT's row (only rows of split parents are read).  scale_lo < scale_hi: bounded-sigmoid
  * scaling activation, else exp.  max_screen_size / max_scale: the reference's optional prune thresholds (rows whose
  * max_radii2D / largest activated scale exceed them are pruned, gaussian_model.py:540-545); <= 0 switches them off (None).
- * params / exp_avg / exp_avg_sq (+ _out): 4 device pointers each in the order xyz[.,3], density[.,1], scaling[.,3], rotation[.,4]. */
+ * params / exp_avg / exp_avg_sq (+ _out): 4 device pointers each in the order xyz[.,3], density[.,1], scaling[.,3], rotation[.,4].
+ * The moment tables may be NULL; an array's moments move when its four moment arrays (in and out) are all there.  P <= 0, a
+ * NULL array, or an array with some but not all four of its moment arrays: R2_ERR_INVALID before anything is launched. */
 R2_API int r2_densify_stats(int P, const int *radii, const float *dL_dmeans2D /* [P,3] */, float *max_radii2D, float *grad_accum,
                             float *denom, void *stream);
 R2_API int r2_densify_stats_batch(int P, int V, const int *radii /* [V,P] */, const float *dL_dmeans2D /* [V,P,3] */,

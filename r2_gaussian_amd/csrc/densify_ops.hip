@@ -258,7 +258,9 @@ extern "C" int r2_densify_emit(int P, const float *const *params, const float *c
                                float *grad_accum_out, float *denom_out, void *stream)
 {
     using namespace r2;
-    if (P <= 0 || !params || !params_out || !max_radii2D || !max_radii2D_out || !grad_accum_out || !denom_out || !scratch) {
+    // decide() reads grad_accum, denom and normals on the device and make_cfg reads bbox_host here: as in r2_densify_classify
+    if (P <= 0 || !params || !params_out || !max_radii2D || !grad_accum || !denom || !normals || !bbox_host || !max_radii2D_out ||
+        !grad_accum_out || !denom_out || !scratch) {
         set_error("r2_densify_emit: invalid argument");
         return R2_ERR_INVALID;
     }
@@ -266,10 +268,9 @@ extern "C" int r2_densify_emit(int P, const float *const *params, const float *c
     const CloudGiven g = cloud_rows(r, params, exp_avg, exp_avg_sq, max_radii2D, grad_accum, denom, params_out, exp_avg_out,
                                      exp_avg_sq_out, max_radii2D_out, grad_accum_out, denom_out);
     bool ok = g.params && g.params_out;
-    for (int a = 0; a < 4; ++a) {   // an array's moments move when all four of its moment arrays are there
-        const bool hm = r.m[a] && r.mo[a], hv = r.v[a] && r.vo[a];
-        ok = ok && hm == hv;
-        if (!hm) r.mo[a] = r.vo[a] = nullptr;
+    for (int a = 0; a < 4; ++a) {   // an array's moments move when all four of its moment arrays are there; none, or nothing moves
+        const int n = (r.m[a] != nullptr) + (r.v[a] != nullptr) + (r.mo[a] != nullptr) + (r.vo[a] != nullptr);
+        ok = ok && (n == 0 || n == 4);   // exp_avg without exp_avg_sq, or an input without its output, would drop state silently
     }
     if (!ok) {
         set_error("r2_densify_emit: NULL parameter array / inconsistent moment arrays");
